@@ -6,11 +6,15 @@ batch 32 per GPU (BASELINE.json configs[2]; with --gpus N it is configs[3], weak
 One "step" = one D-step + one G-step on two independent resident batches, exactly the work of
 one iteration of main_procedure.train (reference main_procedure.py:178-232).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+--steps steps and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, ...).  --full adds what
+takes runs of its own:
   roofline     : the dominant implicit-GEMM kernel's algorithmic TFLOP/s from HIP events, vs the
                  157.3 TFLOP/s fp32 MFMA peak of MI355X
   cpu_baseline : the torch-CPU fp32 oracle (a port of the reference arithmetic; TensorFlow is not
-                 installable here) timed on this host's cores on a bounded sample.
+                 installable here) timed on this host's cores on a bounded sample
+  generator_fwd_bwd, the exact-fp32 step and the secondary workloads (see main()).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs()).
 """
 import argparse
 import json
@@ -24,7 +28,7 @@ import time
 import torch
 
 T_START = time.time()
-# Optional sections of the default run (larger-batch generator graphs, the exact-fp32 step, the secondary workloads) start only
+# Optional sections of a --full run (larger-batch generator graphs, the exact-fp32 step, the secondary workloads) start only
 # while the run is younger than this: on a box where every fresh process takes a minute to page in, the headline line still
 # arrives within minutes.  What was skipped is named in the line (`skipped_for_time`).
 TIME_BUDGET_S = float(os.environ.get('SSC_BENCH_TIME_BUDGET_S', '420'))
@@ -219,6 +223,49 @@ def run_forward_workload(args):
     print(json.dumps(out))
 
 
+# A run that writes its outputs preheats a fixed number of steps instead of a wall time: every step updates the model, so the
+# outputs of the last timed step depend only on the arguments (75 steps per second, about the headline step's rate).
+DUMP_PREHEAT_STEPS_PER_S = 75
+DUMP_SAMPLE = 1 << 22       # at most this many elements per output array (16 MB in float32): a fixed, seeded sample beyond it
+
+
+def _sample(t, seed):
+    """``t`` flattened when it has at most DUMP_SAMPLE elements, else the elements at DUMP_SAMPLE sorted indices drawn with
+    ``seed`` (the same indices for the same size in every run)."""
+    import numpy as np
+    a = t.detach().reshape(-1)
+    if a.numel() <= DUMP_SAMPLE:
+        return a.cpu().numpy()
+    idx = np.sort(np.random.RandomState(seed).choice(a.numel(), DUMP_SAMPLE, replace=False))
+    return a[torch.from_numpy(idx).to(a.device)].cpu().numpy()
+
+
+def dump_outputs(tr, directory):
+    """What the last timed train step computed, as a caller of GanTrainer.train_iteration receives it: the two losses it
+    returns, the generator output of its G-step and the variables it updated (float32; losses float64).  Arrays above
+    DUMP_SAMPLE elements are written as a fixed, seeded sample of their flattened values (`*_sample`): about 42 MB in all
+    at batch 32, 192x192."""
+    import numpy as np
+    torch.cuda.synchronize()
+    loss_g, loss_d = tr.loss.detach().cpu().numpy().astype(np.float64)
+    fake = tr.G.output_nchw(tr.last['gctx'])            # [N, 3, H, W] of the last G-step (its buffers are the graph's)
+    s = tr.store
+    arrays = {'loss_g': np.array([loss_g]), 'loss_d': np.array([loss_d])}
+    for name, t, seed in (('generated_images', fake, 1), ('generator_variables', s.generator.flat, 2),
+                          ('discriminator_variables', s.discriminator.flat, 3)):
+        a = _sample(t, seed).astype(np.float32)
+        if a.size == t.numel():
+            arrays[name] = a.reshape(t.shape)
+        else:
+            arrays[name + '_sample'] = a
+    if s.nontrainable:
+        arrays['spectral_norm_u'] = np.concatenate([v.detach().reshape(-1).cpu().numpy() for v in s.nontrainable.values()])
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def generator_fwd_bwd(tr, batch, args, iters=30):
     """The quantity BASELINE.json's target is stated on: generator forward + backward alone (no discriminator, no
     optimizer), batch and image size of the train step, one hipGraph of G.forward + G.backward replayed ``iters`` times.
@@ -282,7 +329,8 @@ def secondary_workloads(args):
         if not _in_budget('secondary.' + name):
             out[name] = {'error': 'skipped: the run was older than SSC_BENCH_TIME_BUDGET_S = %.0f s' % TIME_BUDGET_S}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), '--no-cpu-baseline', '--no-secondary'] + extra
+        # --full: the train steps' lines carry their executed-FLOP fraction (eager, event-timed steps after the timed ones)
+        cmd = [sys.executable, os.path.abspath(__file__), '--full', '--no-cpu-baseline', '--no-secondary'] + extra
         t0 = time.time()
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, universal_newlines=True)
@@ -468,10 +516,18 @@ def main():
     ap.add_argument('--block-type', default='Pix2Pix', choices=['Pix2Pix', 'Residual', 'MRU'],
                     help='train workload: Pix2Pix = the headline metric; Residual (108.8 GFLOP/img-iteration) and MRU (767) '
                          'are secondary')
+    ap.add_argument('--full', action='store_true',
+                    help='train workload: after the headline also measure what takes runs of its own -- eager event-timed '
+                         'steps (roofline, per-kernel figures), the generator forward + backward graph, the arithmetic error '
+                         'table, the exact-fp32 step, the secondary workloads and the CPU baseline (each can be left out with '
+                         'the --no-* options below)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='train workload: after the timed steps write what the last one computed as DIR/<name>.npy '
+                         '(losses, generator output, updated variables; the untimed preheat then runs a fixed step count)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='skip the secondary workloads (fg_infer, bg768, MRU / Residual train steps, BG train step) that the '
-                         'default single-GPU run times after the headline and reports under "secondary"')
+                    help='skip the secondary workloads (fg_infer, bg768, MRU / Residual train steps, BG train step) that a '
+                         '--full single-GPU run times after the headline and reports under "secondary"')
     ap.add_argument('--no-kernel-events', action='store_true')
     ap.add_argument('--no-gen-fb', action='store_true', help='skip the generator forward + backward graph (kernel-trace runs)')
     ap.add_argument('--no-graphs', action='store_true', help='launch every kernel eagerly (no hipGraph replay)')
@@ -491,6 +547,8 @@ def main():
     under_launcher = 'WORLD_SIZE' in os.environ
     if args.stub_cpu:
         return run_stub_cpu(args, rank, world)
+    if args.dump_outputs and args.workload != 'train':
+        raise SystemExit('bench.py: --dump-outputs writes the outputs of the train workload only')
     if args.workload != 'train':
         assert world == 1, 'forward workloads are single-GPU'
         torch.cuda.set_device(0)
@@ -553,8 +611,13 @@ def main():
     barrier()
     _phase('warmup_and_capture', _t)
     preheat_steps = 0
+    if args.dump_outputs:           # a fixed count: the model the timed steps start from depends on the arguments alone
+        for _ in range(int(round(args.preheat_seconds * DUMP_PREHEAT_STEPS_PER_S / 10.0)) * 10):
+            tr.train_iteration(bd, bg, counter=args.warmup, next_batch_d=bd)
+            preheat_steps += 1
+        barrier()
     t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < args.preheat_seconds:       # untimed; same step count on every rank
+    while not args.dump_outputs and time.perf_counter() - t_pre < args.preheat_seconds:   # untimed; same step count on every rank
         for _ in range(10):
             tr.train_iteration(bd, bg, counter=args.warmup, next_batch_d=bd)
         preheat_steps += 10
@@ -565,9 +628,9 @@ def main():
             if float(flag) == 0.0:
                 break
     # timed region.  With hipGraph replay individual kernels cannot be bracketed by events, so the per-kernel
-    # roofline leg runs `--prof-steps` extra EAGER steps (same kernels, same shapes) right after the timed
+    # roofline leg (--full) runs `--prof-steps` extra EAGER steps (same kernels, same shapes) right after the timed
     # region; with --no-graphs the events are recorded inside the timed region itself.
-    prof = None if args.no_kernel_events else []
+    prof = None if (args.no_kernel_events or not args.full) else []
     if args.no_graphs:
         hip.PROFILE = prof
     # one event per step boundary on the launch stream (no host sync inside the region): per-step durations for the median
@@ -582,6 +645,13 @@ def main():
     dt = time.perf_counter() - t0
     PHASES['timed_region'] = round(dt, 3)
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    dumped = None
+    if args.dump_outputs and rank == 0:         # before anything else runs a step
+        keep, hip.PROFILE = hip.PROFILE, None
+        _t = time.time()
+        dumped = dump_outputs(tr, args.dump_outputs)
+        _phase('dump_outputs', _t)
+        hip.PROFILE = keep
     prof_steps = args.steps
     if not args.no_graphs and prof is not None:
         hip.PROFILE = prof
@@ -595,7 +665,7 @@ def main():
     launches_per_step = None if args.no_graphs else _graph_launches(list(tr._graphs.values()))
     hip.check_sk('bench.py timed region')       # a conv launch that stored a partial sum (hand-off timeout) fails the run
     gen_fb = None
-    if args.block_type == 'Pix2Pix' and not args.no_graphs and world == 1 and not args.no_gen_fb:
+    if args.full and args.block_type == 'Pix2Pix' and not args.no_graphs and world == 1 and not args.no_gen_fb:
         _t = time.time()
         gen_fb = generator_fwd_bwd(tr, bg, args)
         _phase('generator_fwd_bwd', _t)
@@ -701,55 +771,58 @@ def main():
                                                   'flop_per_launch': v[0] / v[2],
                                                   'algorithmic_bytes_per_launch': v[3] / v[2]}
                                               for k, v in sorted(agg.items(), key=lambda kv: -kv[1][1])}}
-        # The quantities BASELINE.json's target is stated on go INSIDE `roofline` (the driver's record keeps that object whole
-        # and only the names of other extra keys): the train step's and the generator forward + backward graph's fraction of
-        # the fp32-MFMA peak on executed FLOPs at the configured batch, and one line per secondary workload.
-        rl = out.setdefault('roofline', {'bound': 'mfma', 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s'})
-        rl['peak_is'] = ('the fp32-MFMA dense peak, as in rounds 1-4: FLOPs are fp32-equivalent (2 x MAC of the fp32 contraction).  The '
-                         'bf16x6 kernels run on the bf16 pipe (%.0f TFLOP/s dense = %.1f fp32-equivalent at six products), so a fraction '
-                         'above 1.0 of this peak would be legitimate for them' % (PEAK_BF16_MFMA_TFLOPS, PEAK_BF16_MFMA_TFLOPS / 6))
-        # ... and beside it the fraction of the pipe the dominant kernel actually runs on: the bf16 MFMA at six products per
-        # fp32 product (the issue-bound staging beside the MFMAs, not the matrix pipe, is what bounds these kernels: DESIGN 3.0)
-        if 'bf16x6' in str(rl.get('kernel', '')) and rl.get('achieved'):
-            rl['peak_bf16x6_fp32_equivalent'] = PEAK_BF16_MFMA_TFLOPS / 6
-            rl['frac_of_bf16x6_peak'] = rl['achieved'] / (PEAK_BF16_MFMA_TFLOPS / 6)
-        rl['arithmetic'] = out['dtype']
-        if world == 1 and not under_launcher:
-            _t = time.time()
-            try:
-                rl['arithmetic_error_vs_f64'] = arithmetic_error_table()
-            except Exception as e:     # noqa: BLE001 -- never cost the headline line
-                rl['arithmetic_error_vs_f64'] = {'error': repr(e)[:200]}
-            _phase('arithmetic_error_table', _t)
-        tg = rl['targets'] = {'step_frac_of_fp32_peak_executed': out.get('step_frac_of_fp32_peak'),
-                              'step_ms': ms, 'step_images_per_sec': value, 'batch_per_gpu': args.batch}
-        if gen_fb is not None:
-            out['generator_fwd_bwd'] = gen_fb
-            tg['generator_fwd_bwd_frac_executed'] = gen_fb['frac_of_fp32_mfma_peak_executed']
-            tg['generator_fwd_bwd_ms'] = gen_fb['ms']
-            tg['generator_fwd_bwd_tflops_executed'] = gen_fb['tflops_executed']
-            if 'by_batch' in gen_fb:
-                tg['generator_fwd_bwd_frac_executed_by_batch'] = {
-                    k: v['frac_of_fp32_mfma_peak_executed'] for k, v in gen_fb['by_batch'].items()}
-        if (not args.no_secondary and world == 1 and not under_launcher and args.block_type == 'Pix2Pix' and
-                args.batch == 32 and args.img == 192 and not args.no_graphs):
-            del tr
-            torch.cuda.empty_cache()
-            if _dtype_label() != 'fp32' and _in_budget('exact_fp32_step'):
+        if args.full:       # everything beyond the headline: runs of its own
+            # The quantities BASELINE.json's target is stated on go INSIDE `roofline` (a record of the line may keep that object
+            # whole and only the names of other extra keys): the train step's and the generator forward + backward graph's fraction
+            # of the fp32-MFMA peak on executed FLOPs at the configured batch, and one line per secondary workload.
+            rl = out.setdefault('roofline', {'bound': 'mfma', 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s'})
+            rl['peak_is'] = ('the fp32-MFMA dense peak, as in rounds 1-4: FLOPs are fp32-equivalent (2 x MAC of the fp32 contraction).  The '
+                             'bf16x6 kernels run on the bf16 pipe (%.0f TFLOP/s dense = %.1f fp32-equivalent at six products), so a fraction '
+                             'above 1.0 of this peak would be legitimate for them' % (PEAK_BF16_MFMA_TFLOPS, PEAK_BF16_MFMA_TFLOPS / 6))
+            # ... and beside it the fraction of the pipe the dominant kernel actually runs on: the bf16 MFMA at six products per
+            # fp32 product (the issue-bound staging beside the MFMAs, not the matrix pipe, is what bounds these kernels: DESIGN 3.0)
+            if 'bf16x6' in str(rl.get('kernel', '')) and rl.get('achieved'):
+                rl['peak_bf16x6_fp32_equivalent'] = PEAK_BF16_MFMA_TFLOPS / 6
+                rl['frac_of_bf16x6_peak'] = rl['achieved'] / (PEAK_BF16_MFMA_TFLOPS / 6)
+            rl['arithmetic'] = out['dtype']
+            if world == 1 and not under_launcher:
                 _t = time.time()
-                tg['exact_fp32_step'] = exact_fp32_step(args)       # SSC_ARITH=fp32: the same step on the exact-fp32 MFMA
-                _phase('exact_fp32_step', _t)
-            _t = time.time()
-            out['secondary'] = secondary_workloads(args)
-            _phase('secondary', _t)
-            rl['secondary'] = {k: ({'images_per_sec': v['images_per_sec'], 'ms': v['ms'], 'frac_executed': v.get('frac_executed'),
-                                    'launches_per_step': v.get('launches_per_step')}
-                                   if 'error' not in v else {'error': v['error'][:120]})
-                               for k, v in out['secondary'].items()}
-        if not args.no_cpu_baseline and world == 1 and args.block_type == 'Pix2Pix':
-            _t = time.time()
-            out['cpu_baseline'] = cpu_baseline(args.img)
-            _phase('cpu_baseline', _t)
+                try:
+                    rl['arithmetic_error_vs_f64'] = arithmetic_error_table()
+                except Exception as e:     # noqa: BLE001 -- never cost the headline line
+                    rl['arithmetic_error_vs_f64'] = {'error': repr(e)[:200]}
+                _phase('arithmetic_error_table', _t)
+            tg = rl['targets'] = {'step_frac_of_fp32_peak_executed': out.get('step_frac_of_fp32_peak'),
+                                  'step_ms': ms, 'step_images_per_sec': value, 'batch_per_gpu': args.batch}
+            if gen_fb is not None:
+                out['generator_fwd_bwd'] = gen_fb
+                tg['generator_fwd_bwd_frac_executed'] = gen_fb['frac_of_fp32_mfma_peak_executed']
+                tg['generator_fwd_bwd_ms'] = gen_fb['ms']
+                tg['generator_fwd_bwd_tflops_executed'] = gen_fb['tflops_executed']
+                if 'by_batch' in gen_fb:
+                    tg['generator_fwd_bwd_frac_executed_by_batch'] = {
+                        k: v['frac_of_fp32_mfma_peak_executed'] for k, v in gen_fb['by_batch'].items()}
+            if (not args.no_secondary and world == 1 and not under_launcher and args.block_type == 'Pix2Pix' and
+                    args.batch == 32 and args.img == 192 and not args.no_graphs):
+                del tr
+                torch.cuda.empty_cache()
+                if _dtype_label() != 'fp32' and _in_budget('exact_fp32_step'):
+                    _t = time.time()
+                    tg['exact_fp32_step'] = exact_fp32_step(args)       # SSC_ARITH=fp32: the same step on the exact-fp32 MFMA
+                    _phase('exact_fp32_step', _t)
+                _t = time.time()
+                out['secondary'] = secondary_workloads(args)
+                _phase('secondary', _t)
+                rl['secondary'] = {k: ({'images_per_sec': v['images_per_sec'], 'ms': v['ms'], 'frac_executed': v.get('frac_executed'),
+                                        'launches_per_step': v.get('launches_per_step')}
+                                       if 'error' not in v else {'error': v['error'][:120]})
+                                   for k, v in out['secondary'].items()}
+            if not args.no_cpu_baseline and world == 1 and args.block_type == 'Pix2Pix':
+                _t = time.time()
+                out['cpu_baseline'] = cpu_baseline(args.img)
+                _phase('cpu_baseline', _t)
+        if dumped is not None:
+            out['outputs_dumped'] = {'dir': os.path.abspath(args.dump_outputs), 'arrays': dumped}
         PHASES['total'] = round(time.time() - T_START, 2)
         out['phase_wall_s'] = PHASES
         out['skipped_for_time'] = SKIPPED

@@ -8,5 +8,5 @@ case $W in
   fg_infer) ARGS="--workload fg_infer --steps 100 --warmup 10";;
 esac
 for rep in 1 2; do for v in "$@"; do
-  echo -n "[$W $v] "; env $v timeout 600 python bench.py --no-cpu-baseline --no-secondary $ARGS 2>/dev/null | python -c "import json,sys; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(b['value'],1), 'img/s', round(b['ms_per_step'],3), 'ms; frac', round(b.get('step_frac_of_fp32_peak') or 0,4), '; launches', b.get('launches_per_step'))"
+  echo -n "[$W $v] "; env $v timeout 600 python bench.py --full --no-cpu-baseline --no-secondary $ARGS 2>/dev/null | python -c "import json,sys; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(b['value'],1), 'img/s', round(b['ms_per_step'],3), 'ms; frac', round(b.get('step_frac_of_fp32_peak') or 0,4), '; launches', b.get('launches_per_step'))"
 done; done

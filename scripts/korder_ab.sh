@@ -10,6 +10,6 @@ done
 for r in 1 2; do
   for K in 0 default; do
     if [ $K = default ]; then unset SSC_BF_KORDER; else export SSC_BF_KORDER=$K; fi
-    echo "== step, SSC_BF_KORDER=$K"; python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-kernel-events 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['value'], d['generator_fwd_bwd'].get('ms') if isinstance(d.get('generator_fwd_bwd'), dict) else None)"
+    echo "== step, SSC_BF_KORDER=$K"; python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-kernel-events 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['value'], d['generator_fwd_bwd'].get('ms') if isinstance(d.get('generator_fwd_bwd'), dict) else None)"
   done
 done

@@ -1,9 +1,9 @@
-# Round-2 PMC passes of the headline step (separate passes, kernel trace only; never TA_*/TCP_* counters: they hang on this
-# pool) + the bench line they are matched with.  Run through gpurun from the repo root; the summary lands in
-# gpurun_out/r02_pmc.json (copy to profiles/r02_pmc.json: bench.py attaches it when the kernel-source hash matches).
-R=$(pwd)
-mkdir -p gpurun_out
-timeout 600 python bench.py --no-cpu-baseline > gpurun_out/bench_for_pmc.json 2>/dev/null
+# Round-2 PMC passes of the headline step (separate passes, kernel trace only; never TA_*/TCP_* counters: they have hung the
+# GPU) + the bench line they are matched with.  Run from the repo root; the summary lands in
+# $OUT/r02_pmc.json (default profile_out/; copy to profiles/r02_pmc.json: bench.py attaches it when the kernel-source hash matches).
+R=$(pwd); OUT=${OUT:-$R/profile_out}
+mkdir -p $OUT
+timeout 600 python bench.py --full --no-cpu-baseline > $OUT/bench_for_pmc.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 CMD="python $R/bench.py --steps 2 --warmup 1 --preheat-seconds 0 --no-graphs --no-kernel-events --no-cpu-baseline"
 for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_INSTS_VALU"; do
@@ -14,4 +14,4 @@ for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES G
   mkdir -p /tmp/pmcflat/pmc_final_$tag; cp $(find /tmp/pmc_final_$tag -name '*.db' | head -1) /tmp/pmcflat/pmc_final_$tag/p_results.db
 done
 cd $R
-python scripts/pmc_summary.py /tmp/pmcflat gpurun_out/r02_pmc.json gpurun_out/bench_for_pmc.json | tail -16
+python scripts/pmc_summary.py /tmp/pmcflat $OUT/r02_pmc.json $OUT/bench_for_pmc.json | tail -16

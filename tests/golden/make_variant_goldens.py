@@ -39,6 +39,8 @@ if __name__ == '__main__':
     # Residual: forward + one float64 training graph
     p = R.init_params('fg', seed=0, with_discriminator=True, img=64)
     gen = R.generate_residual(p, b['sketches'], b['text'], b['noise_vec'])
+    # and in float64: the host-independent pin (the fp32 image moves by ~5e-5 with the CPU's thread count and instruction set)
+    gen64 = R.generate_residual(to_f64(p), b['sketches'].double(), b['text'], b['noise_vec'].double())
     r = R.build_single_graph_f64(p, **b)
     # MRU generator forward (labels = class ids)
     pm = M.init_params(0, img=64)
@@ -51,7 +53,7 @@ if __name__ == '__main__':
     # 2e-3 from it on this 96x96 batch-norm stack, and by how much depends on the CPU's instruction set)
     img_b64, seg_b64 = R.create_residual_generator(to_f64(pb), x.double(), text)
     np.savez_compressed(os.path.join(HERE, 'variants_seed0_42.npz'),
-                        residual_gen=gen.numpy(), residual_loss_g=np.float64(r['loss_g']),
+                        residual_gen=gen.numpy(), residual_gen_f64=gen64.numpy(), residual_loss_g=np.float64(r['loss_g']),
                         residual_loss_d=np.float64(r['loss_d']), residual_fake_disc=r['fake_disc'].numpy(),
                         residual_real_logit=r['real_logit'].numpy(), mru_gen=gen_m.numpy(),
                         bg_image=img_b.numpy(), bg_region_logits=seg_b.numpy(),

@@ -83,7 +83,14 @@ def test_variant_oracles_reproduce_frozen_outputs():
     m, z = _variants()
     b = m.inputs(64)
     p = R.init_params('fg', seed=0, with_discriminator=True, img=64)
-    assert np.abs(R.generate_residual(p, b['sketches'], b['text'], b['noise_vec']).numpy() - z['residual_gen']).max() < 5e-5
+    # fp32 reduction order follows the host's thread count and instruction set: the float64 graph is pinned, the fp32 image is held
+    # to the frozen one within 5e-5 or within 1.5 x its own distance from float64 (as the BG clause below)
+    gen = R.generate_residual(p, b['sketches'], b['text'], b['noise_vec'])
+    gen64 = R.generate_residual(m.to_f64(p), b['sketches'].double(), b['text'], b['noise_vec'].double())
+    assert np.abs(gen64.numpy() - z['residual_gen_f64']).max() < 1e-9
+    own = float((gen.double() - gen64).abs().max())
+    assert own < 1e-3 and float(np.abs(z['residual_gen'] - gen64.numpy()).max()) < 1e-3
+    assert float(np.abs(gen.numpy() - z['residual_gen']).max()) < max(5e-5, 1.5 * own)
     disc, logit = R.discriminate_residual(p, b['sketches'], b['images_d'])
     assert np.abs(logit.numpy() - z['residual_real_logit']).max() < 5e-5
     pm = M.init_params(0, img=64)
