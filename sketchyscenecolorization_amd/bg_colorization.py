@@ -15,6 +15,17 @@ from .params import Buffers, ParamStore
 from .residual import ResidualGenerator
 
 _TOWERS = {}
+MASK_CLASSES = 3        # data_processing.image_processing.load_region_mask writes the classes 0, 1, 2
+
+
+def check_seg_classes(seg_classes):
+    """The region-mask loss indexes a row of ``seg_classes`` logits with the mask's label (tf.nn.sparse_softmax_cross_entropy_
+    with_logits raises -- on a GPU: answers NaN -- for a label outside them).  The masks carry classes 0 .. 2 and the kernel
+    holds at most four logits per row, so a trainer for fewer or more classes is refused where it is built; a label that is
+    out of range all the same (a mask from elsewhere) makes ssc_seg_ce_loss answer NaN instead of reading past the row."""
+    if not MASK_CLASSES <= int(seg_classes) <= 4:
+        raise ValueError('seg_classes = %s: the region masks carry the classes 0 .. %d and the loss kernel takes at most 4 '
+                         'logits per pixel, so seg_classes must be %d or 4' % (seg_classes, MASK_CLASSES - 1, MASK_CLASSES))
 
 
 def get_tower(image_size=768, vocab_size=18, ngf=64, seg_classes=3, seed=0, device='cuda'):
@@ -66,6 +77,7 @@ class BGTrainer(object):
 
     def __init__(self, image_size=768, vocab_size=18, ngf=64, ndf=64, seg_classes=3, lr=2e-4, max_steps=100000,
                  gan_weight=1.0, l1_weight=100.0, seg_weight=100.0, beta1=0.5, seed=0, device='cuda', use_graphs=True):
+        check_seg_classes(seg_classes)
         if not torch.cuda.is_available():
             raise RuntimeError('BGTrainer needs an MI355X (HIP) device: there is no CPU fallback')
         if ngf != 64 or ndf != 64:

@@ -318,23 +318,32 @@ static inline void col_grid(int64_t M, int C, int& tcg, int& rl, int& nblk_rows,
     nblk_rows = (int)nb;
 }
 
+// shift != NULL: the sums are taken of x - shift[c] (ssc_bn_stats hands in row 0 of x).  q/M - mean^2 over fp32 partials of the
+// raw values loses (mean/std)^2 * 2^-24 of the variance -- 6 % at mean/std = 1000; around a value of the channel itself the
+// squares are of the order of the variance and nothing cancels.  The finalize kernel adds the shift back to the mean.
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __restrict__ x, long M, int C, int ldx,
-                                                                int tcg, float* __restrict__ partial) {
+                                                                int tcg, float* __restrict__ partial,
+                                                                const float* __restrict__ shift) {
     __shared__ float4 sh[2][256];
     const int rl = 256 / tcg;
     const int cgi = blockIdx.y * tcg + (threadIdx.x % tcg);
     const int rlane = threadIdx.x / tcg;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
     if (cgi * 4 < C) {
+        const float4 k = shift != nullptr ? *reinterpret_cast<const float4*>(shift + cgi * 4) : s;
         // 4 rows in flight per thread: the walk is a chain of strided loads, one accumulator pair would serialise them
         const long step = (long)gridDim.x * rl;
         long r = (long)blockIdx.x * rl + rlane;
         float4 s1 = s, q1 = s, s2 = s, q2 = s, s3 = s, q3 = s;
         for (; r + 3 * step < M; r += 4 * step) {
-            const float4 v0 = *reinterpret_cast<const float4*>(x + r * ldx + cgi * 4);
-            const float4 v1 = *reinterpret_cast<const float4*>(x + (r + step) * ldx + cgi * 4);
-            const float4 v2 = *reinterpret_cast<const float4*>(x + (r + 2 * step) * ldx + cgi * 4);
-            const float4 v3 = *reinterpret_cast<const float4*>(x + (r + 3 * step) * ldx + cgi * 4);
+            float4 v0 = *reinterpret_cast<const float4*>(x + r * ldx + cgi * 4);
+            float4 v1 = *reinterpret_cast<const float4*>(x + (r + step) * ldx + cgi * 4);
+            float4 v2 = *reinterpret_cast<const float4*>(x + (r + 2 * step) * ldx + cgi * 4);
+            float4 v3 = *reinterpret_cast<const float4*>(x + (r + 3 * step) * ldx + cgi * 4);
+            v0.x -= k.x; v0.y -= k.y; v0.z -= k.z; v0.w -= k.w;
+            v1.x -= k.x; v1.y -= k.y; v1.z -= k.z; v1.w -= k.w;
+            v2.x -= k.x; v2.y -= k.y; v2.z -= k.z; v2.w -= k.w;
+            v3.x -= k.x; v3.y -= k.y; v3.z -= k.z; v3.w -= k.w;
             s.x += v0.x; s.y += v0.y; s.z += v0.z; s.w += v0.w;
             q.x += v0.x * v0.x; q.y += v0.y * v0.y; q.z += v0.z * v0.z; q.w += v0.w * v0.w;
             s1.x += v1.x; s1.y += v1.y; s1.z += v1.z; s1.w += v1.w;
@@ -345,7 +354,8 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
             q3.x += v3.x * v3.x; q3.y += v3.y * v3.y; q3.z += v3.z * v3.z; q3.w += v3.w * v3.w;
         }
         for (; r < M; r += step) {
-            const float4 v = *reinterpret_cast<const float4*>(x + r * ldx + cgi * 4);
+            float4 v = *reinterpret_cast<const float4*>(x + r * ldx + cgi * 4);
+            v.x -= k.x; v.y -= k.y; v.z -= k.z; v.w -= k.w;
             s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
             q.x += v.x * v.x; q.y += v.y * v.y; q.z += v.z * v.z; q.w += v.w * v.w;
         }
@@ -416,13 +426,15 @@ static inline unsigned fold_grid(int C, int wpc) { return wpc == 4 ? (unsigned)C
 __global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const float* __restrict__ partial, int nblk, int C,
                                                                  long M, const float* __restrict__ scale,
                                                                  const float* __restrict__ offset, float eps,
-                                                                 float* __restrict__ ab, float* __restrict__ stats, int wpc) {
+                                                                 float* __restrict__ ab, float* __restrict__ stats, int wpc,
+                                                                 const float* __restrict__ shift) {
     int c;
     double s, q;
     if (!fold_rows(partial, nblk, C, wpc, c, s, q)) return;
-    const double mean = s / (double)M;
-    double var = q / (double)M - mean * mean;
+    const double ms = s / (double)M;        // mean of x - shift
+    double var = q / (double)M - ms * ms;
     if (var < 0.0) var = 0.0;
+    const double mean = ms + (shift != nullptr ? (double)shift[c] : 0.0);
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     const float a = rstd * scale[c];
     ab[c] = a;
@@ -438,16 +450,16 @@ extern "C" int ssc_bn_stats(const float* x, int64_t M, int C, int ldx, const flo
     col_grid(M, C, tcg, rl, nbr, nbc);
     if ((int64_t)nbr * 2 * C * (int64_t)sizeof(float) > ws_bytes) return -2;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nbr, nbc), dim3(256), 0, st, x, (long)M, C, ldx, tcg, ws);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nbr, nbc), dim3(256), 0, st, x, (long)M, C, ldx, tcg, ws, x);
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(fold_grid(C, fold_wpc(nbr))), dim3(256), 0, st, ws, nbr, C, (long)M, scale,
-                       offset, eps, ab, stats, fold_wpc(nbr));
+                       offset, eps, ab, stats, fold_wpc(nbr), x);
     return CHECK_LAUNCH();
 }
 
 extern "C" int ssc_bn_finalize(const float* partial, int nblk, int C, int64_t M, const float* scale, const float* offset,
                                float eps, float* ab, float* stats, void* stream) {
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(fold_grid(C, fold_wpc(nblk))), dim3(256), 0, (hipStream_t)stream, partial,
-                       nblk, C, (long)M, scale, offset, eps, ab, stats, fold_wpc(nblk));
+                       nblk, C, (long)M, scale, offset, eps, ab, stats, fold_wpc(nblk), (const float*)nullptr);
     return CHECK_LAUNCH();
 }
 
@@ -541,7 +553,8 @@ extern "C" int ssc_colsum(const float* x, int ld, int64_t M, int C, float* out, 
     col_grid(M, Cv, tcg, rl, nbr, nbc);
     if ((int64_t)nbr * 2 * Cv * (int64_t)sizeof(float) > workspace_bytes) return -2;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nbr, nbc), dim3(256), 0, st, x, (long)M, Cv, ld, tcg, workspace);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nbr, nbc), dim3(256), 0, st, x, (long)M, Cv, ld, tcg, workspace,
+                       (const float*)nullptr);
     hipLaunchKernelGGL(colsum_fold_kernel, dim3((C + 3) / 4), dim3(256), 0, st, workspace, nbr, Cv, C, out, accumulate);
     return CHECK_LAUNCH();
 }

@@ -561,7 +561,9 @@ extern "C" int ssc_bg_gan_loss(const float* z, int64_t n, int mode, float scale,
     return CHECK_LAUNCH();
 }
 
-// count[0] = number of labels != 0 (the pixels the L1 term averages over, :612-616)
+// count[0] = number of labels != 0 (the pixels the L1 term averages over, :612-616).  The count is kept in float: every partial
+// and the total are integers below 2^24 = 16 777 216, so the result is exact up to that many non-zero labels (batch 4 of 768^2 is
+// 2 359 296); above it float steps by 2 and the count would round.
 __global__ __launch_bounds__(256) void count_nonzero_kernel(const int* __restrict__ labels, long n, float* __restrict__ part) {
     __shared__ float sh[4];
     float s = 0.f;
@@ -640,8 +642,12 @@ __global__ __launch_bounds__(256) void seg_ce_loss_kernel(const float* __restric
         float se = 0.f;
         for (int k = 0; k < K; ++k) { z[k] = expf(z[k] - m); se += z[k]; }
         const int y = labels[r];
-        s += -(logits[r * K + y] - m - logf(se));
-        for (int k = 0; k < ldg; ++k) dlogits[r * ldg + k] = k < K ? inv * (z[k] / se - (k == y ? 1.f : 0.f)) : 0.f;
+        // a label outside [0, K) never indexes the row: its loss and gradient row are NaN, as TF's GPU kernel of
+        // sparse_softmax_cross_entropy_with_logits answers (hosts refuse such a configuration, bg_colorization.check_seg_classes)
+        const bool ok = (unsigned)y < (unsigned)K;
+        s += ok ? -(logits[r * K + y] - m - logf(se)) : NAN;
+        for (int k = 0; k < ldg; ++k)
+            dlogits[r * ldg + k] = k < K ? (ok ? inv * (z[k] / se - (k == y ? 1.f : 0.f)) : NAN) : 0.f;
     }
     const float t = block_sum_256(s, sh);
     if (threadIdx.x == 0) atomicAdd(loss_acc, (double)inv * (double)t);

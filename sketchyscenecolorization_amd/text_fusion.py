@@ -38,6 +38,13 @@ UNFUSED_ROWS = int(_dev_env('SSC_LSTM_UNFUSED_ROWS', '2048'))
 PINNED_PREP = _dev_env('SSC_PINNED_PREP', '1') != '0'       # caption tokens to the device through pinned memory (A/B: 0)
 
 
+def check_tokens(text, vocab):
+    """ssc_embedding_gather reads table[token] with no clamp (tf.nn.embedding_lookup raises for an id outside the table): the
+    ids are host data here, so an id outside [0, vocab) is refused before it reaches the device."""
+    if text.size and (int(text.min()) < 0 or int(text.max()) >= vocab):
+        raise ValueError('caption token ids must lie in [0, %d): got %d .. %d' % (vocab, int(text.min()), int(text.max())))
+
+
 class TextFusion(object):
     def __init__(self, store, bufs, scope='generator/TextLSTM'):
         """scope: 'generator/TextLSTM' (FG, models_collection.py:159) or 'generator/mLSTM_G' (BG,
@@ -56,7 +63,8 @@ class TextFusion(object):
         text = np.asarray(text.cpu() if isinstance(text, torch.Tensor) else text).astype(np.int32)
         N = text.shape[0]
         text = text.reshape(N, -1)
-        steps = [t for t in range(text.shape[1]) if (text[:, t] != 0).any()]
+        check_tokens(text, self.s[self.emb_name].shape[0])
+        steps =[t for t in range(text.shape[1]) if (text[:, t] != 0).any()]
         S = len(steps)
         prep = {'S': S, 'N': N}
         if S > 0:

@@ -1,0 +1,93 @@
+"""Helpers of the kernel-level tests of the small kernels (tests/test_gpu_small_kernels*.py): seeded CPU inputs, NaN-filled
+device outputs, the raw return code of an entry point, and the two comparison rules those tests use.
+
+  check      |device - float64 oracle| <= tol * max(1, max|oracle|)            (the close() convention of test_gpu_igemm.py)
+  check_fp32 per element max(that floor, 4 x |float32 oracle - float64 oracle|): for formulas that lose digits in float32 by
+             construction, the same way in the reference (the factor 4 allows for expf / logf / tanhf a few ulp off libm)
+
+Both print the measured distance before they assert and log it with conftest.parity_log (variant='kernel', never forward=True:
+these are not network outputs)."""
+import torch
+
+from conftest import parity_log
+
+NAN = float('nan')
+
+
+def hip():
+    from sketchyscenecolorization_amd import hip as h
+    return h
+
+
+def rnd(*shape, seed=0, std=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g) * std
+
+
+def randint(lo, hi, *shape, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(lo, hi, shape, generator=g, dtype=torch.int32)
+
+
+def nan(*shape):
+    return torch.full(shape, NAN, device='cuda')
+
+
+def acc(*values):
+    """A loss accumulator: double device scalars that the kernels add into."""
+    return torch.tensor(values, dtype=torch.float64, device='cuda')
+
+
+def rc(name, *args):
+    """The return code of an entry point called through lib() directly (argument checks answer without launching)."""
+    h = hip()
+    conv = [h.ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
+    code = getattr(h.lib(), name)(*conv, h.stream_ptr())
+    torch.cuda.synchronize()
+    return code
+
+
+def all_nan(t):
+    return bool(torch.isnan(t).all().item())
+
+
+def _f64(t):
+    return t.detach().cpu().double()
+
+
+def check(test, config, got, ref, tol=1e-5, what=''):
+    got, ref = _f64(got), _f64(ref)
+    assert got.shape == ref.shape, (test, what, got.shape, ref.shape)
+    assert bool(torch.isfinite(got).all()), (test, what, config, 'non-finite output')
+    bound = tol * max(1.0, float(ref.abs().max()) if ref.numel() else 0.0)
+    err = float((got - ref).abs().max()) if ref.numel() else 0.0
+    print('%s %s %s: err %.3e bound %.3e' % (test, what, config, err, bound))
+    parity_log(test, dict(config, what=what), err, bound, variant='kernel')
+    assert err <= bound, (test, what, config, err, bound)
+    return err
+
+
+def check_scalar(test, config, got, ref, tol=1e-5, what='loss'):
+    """Loss scalars: relative to the oracle's value."""
+    got, ref = float(got), float(ref)
+    bound = tol * abs(ref)
+    err = abs(got - ref)
+    print('%s %s %s: got %.9g ref %.9g err %.3e bound %.3e' % (test, what, config, got, ref, err, bound))
+    parity_log(test, dict(config, what=what), err, bound, variant='kernel')
+    assert err == err and err <= bound, (test, what, config, got, ref)
+    return err
+
+
+def check_fp32(test, config, got, ref64, ref32, tol=1e-5, what=''):
+    got, ref64, ref32 = _f64(got), _f64(ref64), _f64(ref32)
+    assert got.shape == ref64.shape == ref32.shape, (test, what, got.shape, ref64.shape, ref32.shape)
+    assert bool(torch.isfinite(got).all()), (test, what, config, 'non-finite output')
+    floor = tol * max(1.0, float(ref64.abs().max()))
+    cpu = (ref32 - ref64).abs()
+    bound = torch.clamp(4.0 * cpu, min=floor)
+    err = (got - ref64).abs()
+    k = int(torch.argmax(err / bound))
+    e, b, c = float(err.reshape(-1)[k]), float(bound.reshape(-1)[k]), float(cpu.max())
+    print('%s %s %s: err %.3e (bound there %.3e, max err %.3e), fp32 oracle vs f64 %.3e' % (test, what, config, e, b, float(err.max()), c))
+    parity_log(test, dict(config, what=what), e, b, variant='kernel', cpu_fp32_vs_f64=c, max_err_anywhere=float(err.max()))
+    assert bool((err <= bound).all()), (test, what, config, e, b)

@@ -343,3 +343,32 @@ def test_pending_losses_are_settled_in_launch_order(capsys):
     assert _settle_first(pending, 3) == -1
     assert 'NaN occurred during training G' in capsys.readouterr().out
     assert pending == [] and not z.read
+
+
+def test_region_class_count_below_the_masks_classes_is_refused_where_the_trainer_is_built():
+    """--seg_classes 2 with the shipped masks (classes 0, 1, 2) would hand ssc_seg_ce_loss a label outside its row of logits;
+    the oracle's cross-entropy raises for such a label, so the trainer is refused on the host (before any device is touched)."""
+    import pytest
+    from sketchyscenecolorization_amd import bg_colorization as B
+    for ok in (3, 4):
+        B.check_seg_classes(ok)
+    for bad in (0, 1, 2, 5):
+        with pytest.raises(ValueError):
+            B.check_seg_classes(bad)
+        with pytest.raises(ValueError):
+            B.BGTrainer(image_size=64, seg_classes=bad)
+
+
+def test_caption_token_outside_the_vocabulary_is_refused_on_the_host():
+    """ssc_embedding_gather does not clamp: TextFusion.prepare checks the (host) token ids against the embedding table."""
+    import numpy as np
+    import pytest
+    from sketchyscenecolorization_amd.text_fusion import check_tokens
+    check_tokens(np.array([[0, 1, 57]], dtype=np.int32), 58)
+    check_tokens(np.zeros((0, 15), dtype=np.int32), 58)
+    for bad in ([[0, 58]], [[-1, 3]]):
+        with pytest.raises(ValueError):
+            check_tokens(np.array(bad, dtype=np.int32), 58)
+    import inspect
+    from sketchyscenecolorization_amd import text_fusion
+    assert 'check_tokens(' in inspect.getsource(text_fusion.TextFusion.prepare)
