@@ -8,6 +8,10 @@ Same flags and defaults as the reference (bg_colorization_main.py:978-1003), sam
 Data layout under --data_base_dir (reference :739-750): ``foreground/<mode>/*.png``, ``background/<mode>/*.png``,
 ``segment/<mode>/*.png`` and ``captions/<mode>.json`` (records with fg_name, bg_name, color_text).  When the caption
 file is missing the run uses seeded synthetic scenes, so the CLI can be exercised without the dataset.
+
+--batch_size N trains on N scenes per step (the reference's placeholders are fixed at 1, :765-768; nothing else in its graph
+is): the norms' statistics, the loss means and the masked-L1 pixel count then run over the whole batch.  Test mode stays at
+one image per forward pass, because those batch statistics would make every output depend on its batch mates.
 """
 import argparse
 import json
@@ -25,7 +29,8 @@ FLAGS = [
     ('resume_from', str, '', None, 'stamp of an earlier run under outputs/'),
     ('data_base_dir', str, 'data', None, 'dataset root'),
     ('image_size', int, 768, None, 'square image size'),
-    ('batch_size', int, 1, None, 'images per step (the reference graph is built for 1)'),
+    ('batch_size', int, 1, None, 'scenes per training step; norm statistics and loss means run over the batch '
+                                 '(test mode always feeds one image per pass: batch statistics would change every output)'),
     ('max_steps', int, 100000, None, 'training steps'),
     ('lr', float, 0.0002, None, 'initial Adam step size'),
     ('l1_weight', float, 100.0, None, 'weight of the masked L1 term'),
@@ -96,13 +101,18 @@ class Scenes(object):
 
 
 def to_unit(u8):
-    """uint8 [0,255] -> float [-1,1] (convert_image_dtype + preprocess, :30-33, 100-113)."""
+    """uint8 [0,255] -> float [-1,1] (convert_image_dtype + preprocess, :30-33, 100-113) in torch arithmetic: what float callers
+    of BGTrainer.train_step feed it with.  The command line itself stages its uint8 arrays with hip.bg_stage_u8."""
     u8 = u8 if torch.is_tensor(u8) else torch.from_numpy(u8)
-    return u8.to('cuda', torch.float32) / 255.0 * 2.0 - 1.0
+    x = u8.to('cuda', torch.float32)
+    # the divisor is a (0-dim) device tensor: torch turns a division by a Python number into a multiplication by its rounded
+    # reciprocal, which is one ulp away from x / 255 for 111 of the 256 byte values
+    return x / torch.full((), 255.0, dtype=torch.float32, device=x.device) * 2.0 - 1.0
 
 
 def to_u8(x):
-    """[-1,1] -> uint8 with saturation (deprocess + convert_image_dtype(saturate=True), :36-39, 785-786)."""
+    """[-1,1] -> uint8 with saturation (deprocess + convert_image_dtype(saturate=True), :36-39, 785-786) in torch arithmetic;
+    the command line's test mode runs the same operations in hip.bg_finish_u8."""
     y = ((x + 1.0) / 2.0).clamp(0.0, 1.0) * 255.0
     return (y + 0.5).floor().clamp(0, 255).to(torch.uint8).cpu().numpy()
 
@@ -145,15 +155,25 @@ def bg_colorization(**p):
         from PIL import Image
         res_dir = os.path.join(out_dir, 'results')
         os.makedirs(res_dir, exist_ok=True)
+        from sketchyscenecolorization_amd import hip
+        size = p['image_size']
+        x = torch.empty((1, size, size, 3), dtype=torch.float32, device='cuda')
+        y, xd, cnt = torch.empty_like(x), torch.empty((1, size, size, 8), dtype=torch.float32, device='cuda'), torch.empty(1, device='cuda')
+        lab0 = torch.zeros((1, size, size), dtype=torch.int32, device='cuda')
+        # one image per forward pass whatever --batch_size says: the norms are batch statistics
         for i in range(len(scenes)):
             print('Processing', i, '/', len(scenes))
             fg, bg, tok, lab, fg_name, bg_name = scenes.get(i, is_test=True)
-            gctx = tr.G.forward(to_unit(fg), tok, None, 'bg')
-            out = to_u8(gctx['image'])
+            fg_d = torch.from_numpy(fg).cuda()
+            # the forward pass reads the stage's float inputs only: the foreground stands in for the background and a constant
+            # array for the labels, so nothing but the foreground is uploaded (y, xd and cnt are the kernel's other outputs, unread)
+            hip.bg_stage_u8(fg_d, fg_d, lab0, x, y, xd, cnt)
+            gctx = tr.G.forward(x, tok, None, 'bg')
             seg_path = os.path.join(scenes.dirs['segment'], fg_name)
+            inner = None
             if os.path.exists(seg_path):        # paste the foreground (segment value 0) back over the generation
-                inner = np.array(Image.open(seg_path).convert('RGB'), np.uint8)[:, :, 0]
-                out[0][inner == 0] = fg[0][inner == 0]
+                inner = torch.from_numpy(np.ascontiguousarray(np.array(Image.open(seg_path).convert('RGB'), np.uint8)[:, :, 0])).cuda()
+            out = hip.bg_finish_u8(gctx['image'], fg_d, inner).cpu().numpy()
             for kind, arr in (('inputs', fg), ('outputs', out), ('targets', bg)):
                 Image.fromarray(arr[0], 'RGB').save(os.path.join(res_dir, bg_name[:-4] + '_' + kind + '.png'), 'PNG')
         return
@@ -162,43 +182,57 @@ def bg_colorization(**p):
     os.makedirs(log_dir, exist_ok=True)
     start = time.time()
     ema = None
-    # The examples of the next steps are loaded ahead (two 768 x 768 images and a region mask per step: ~60 ms of decoding on
-    # one thread against a 22 ms device step) by a few threads, in the order the indices are drawn -- one draw per step, as
-    # before; SSC_BG_PREFETCH=0: loaded where they are used.
+    # The examples of the next steps are loaded ahead (two 768 x 768 images and a region mask per scene: ~60 ms of decoding on
+    # one thread against a 22 ms device step) by a few threads, in the order the indices are drawn -- batch_size draws per step,
+    # one random.randint each, so the sequence at batch 1 is the one of one draw per step; SSC_BG_PREFETCH=0: loaded where they
+    # are used.
     import collections
     from concurrent.futures import ThreadPoolExecutor
+    nb = p['batch_size']
     depth = int(os.environ.get('SSC_BG_PREFETCH', '4'))
-    pool = ThreadPoolExecutor(max_workers=max(depth, 1)) if depth > 0 else None
+    pool = ThreadPoolExecutor(max_workers=max(depth, 1) * min(nb, 4)) if depth > 0 else None
     ahead, drawn = collections.deque(), [iter_from]
+
+    def draw_batch():
+        return [random.randint(0, len(scenes) - 1) for _ in range(nb)]
 
     def draw_more():
         while pool is not None and len(ahead) < depth and drawn[0] < p['max_steps']:
-            ahead.append(pool.submit(scenes.get, random.randint(0, len(scenes) - 1)))
+            ahead.append([pool.submit(scenes.get, i) for i in draw_batch()])
             drawn[0] += 1
 
-    # host arrays go to the device through a ring of pinned staging buffers allocated once (pinning a fresh 1.7 MB array costs
-    # 3.5 ms a time; a copy from pageable memory returns only when it has happened, behind the step that is running)
+    # the scenes of a step are stacked into pinned staging buffers of the batch shape, allocated once and used in turn (pinning
+    # a fresh 1.7 MB array costs 3.5 ms a time; a copy from pageable memory returns only when it has happened, behind the step
+    # that is running).  A buffer is written again only when the copy that last read it has happened (its event).
     ring, ring_i = {}, [0]
 
-    def pinned(a, slot):
-        key = (slot, a.shape, a.dtype.str)
-        if key not in ring:
-            ring[key] = [torch.from_numpy(np.empty_like(a)).pin_memory() for _ in range(4)]
-        buf = ring[key][ring_i[0] % 4]
-        buf.numpy()[...] = a
-        return buf.to('cuda', non_blocking=True)
+    def staged(parts, slot, dtype):
+        if slot not in ring:
+            shape = (nb,) + tuple(parts[0].shape[1:])
+            ring[slot] = [(torch.empty(shape, dtype=dtype).pin_memory(), torch.cuda.Event()) for _ in range(4)]
+        buf, ev = ring[slot][ring_i[0] % 4]
+        ev.synchronize()
+        view = buf.numpy()
+        for i, a in enumerate(parts):
+            view[i] = a[0]
+        return buf, ev
 
     for step in range(iter_from, p['max_steps']):
         def should(freq):
             return freq > 0 and ((step + 1) % freq == 0 or step == p['max_steps'] - 1)
         if pool is not None:
             draw_more()
-            fg, bg, tok, lab, _, _ = ahead.popleft().result()
+            batch = [f.result() for f in ahead.popleft()]
             draw_more()
         else:
-            fg, bg, tok, lab, _, _ = scenes.get(random.randint(0, len(scenes) - 1))
+            batch = [scenes.get(i) for i in draw_batch()]
         ring_i[0] += 1
-        tr.train_step(to_unit(pinned(fg, 'fg')), to_unit(pinned(bg, 'bg')), tok, pinned(lab, 'lab'))
+        fg, ev_fg = staged([b[0] for b in batch], 'fg', torch.uint8)
+        bg, ev_bg = staged([b[1] for b in batch], 'bg', torch.uint8)
+        lab, ev_lab = staged([b[3] for b in batch], 'lab', torch.int32)
+        tr.train_step_u8(fg, bg, np.concatenate([b[2] for b in batch], 0), lab)
+        for ev in (ev_fg, ev_bg, ev_lab):
+            ev.record()
         if should(p['progress_freq']) or should(p['summary_freq']):
             vals = tr.loss_values()
             # tf.train.ExponentialMovingAverage(0.99) of the five losses (:657-658), updated when they are read
@@ -229,8 +263,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.mode == 'test':
         assert args.resume_from != ''
-    if args.batch_size != 1:
-        raise NotImplementedError('the reference graph feeds one image per step (placeholders of batch 1, :765-768)')
+    if args.batch_size < 1:
+        raise ValueError('--batch_size %d: at least one scene per step' % args.batch_size)
     bg_colorization(**{name: getattr(args, name) for name, _t, _d, _c, _h in FLAGS})
 
 

@@ -258,6 +258,19 @@ int ssc_nhwc_to_nchw(const float* src, float* dst, int N, int C, int HW, int ldc
 int ssc_sketch_preprocess_u8(const uint8_t* src, int N, int H, int W, int thicken, float* dst, void* stream);
 /* src float NHWC rows of ldc floats, image in channels [coff, coff+3) -> dst uint8 [M,3] = ((x+1)/2*255) truncated */
 int ssc_image_postprocess_u8(const float* src, int ldc, int coff, int64_t M, uint8_t* dst, void* stream);
+/* --- the Background module's uint8 boundary (bg_io.hip) ---
+ * One pass from the loader's arrays to what a train step reads (bg_colorization_main.py:30-33, 100-113, 765-768): fg, bg uint8
+ * [M,3], labels int32 [M] -> inputs, targets float [M,3] = u8/255*2-1 (divide, multiply, subtract, each rounded to fp32),
+ * xd_real float [M,8] = [inputs | targets | 0 0] (the discriminator's real pair, :596-600) and count[0] = #(labels != 0) as a
+ * float (:612-616), summed as an integer: exact and the same for every launch geometry.  M <= 2^24.  workspace: 8 bytes,
+ * 8-byte aligned (zeroed on the stream by this call).  fg / bg 4-byte, the other arrays 16-byte aligned. */
+int ssc_bg_stage_u8(const uint8_t* fg, const uint8_t* bg, const int32_t* labels, int64_t M, float* inputs, float* targets,
+                    float* xd_real, float* count, void* workspace, int64_t workspace_bytes, void* stream);
+/* img float rows of ldc >= 3 floats (the generator's tanh image) -> out uint8 [M,3] = floor(clamp((x+1)/2, 0, 1)*255 + 0.5)
+ * clamped to 0..255 (deprocess + convert_image_dtype(saturate=True), :36-39, 785-786); where mask uint8 [M] (may be NULL) is 0
+ * the pixel of fg uint8 [M,3] is written instead (the paste-back of test mode, :861-871).  fg may be NULL without a mask. */
+int ssc_bg_finish_u8(const float* img, int ldc, const uint8_t* fg, const uint8_t* mask, int64_t M, uint8_t* out,
+                     void* stream);
 /* PIL.Image.resize of an 8-bit image on the device (resize_and_padding_mask_image, input_pipeline.py:199-239: ANTIALIAS =
  * LANCZOS; reverse_resize_image, Pipeline_utils/fg_color_utils.py:137-160: scipy.misc.imresize = PIL bilinear): Pillow's
  * two-pass 8-bit resampler, horizontal then vertical, bit for bit.  src uint8 [H,W,C]; chan >= 0: only that channel,

@@ -1,9 +1,18 @@
-"""Background_Colorization generator (bg_colorization_main.py:302-420) behind the reference's function name.
+"""Background_Colorization module (bg_colorization_main.py:302-726): the generator behind the reference's function name and
+the whole train step.
 
-Only ``create_residual_generator`` (forward) is built: BASELINE.json config 5, the 768x768 large-activation stress
-case.  The BG module's discriminator, losses, feed_dict trainer and PNG writer are out of scope (SURVEY.md 8, row
-A13 "next").  The reference builds the variables under tf.variable_scope('generator') (:582-586); they live in a
-``ParamStore('BG')`` keyed by those TF names so a converted checkpoint loads with ``store.load_dict``.
+``create_residual_generator`` is the forward pass (BASELINE.json config 5, the 768x768 large-activation stress case).  The
+reference builds the variables under tf.variable_scope('generator') (:582-586); they live in a ``ParamStore('BG')`` keyed by
+those TF names so a converted checkpoint loads with ``store.load_dict``.
+
+``BGTrainer`` is ``create_model`` in train mode: generator with region branch, residual discriminator, the three loss terms,
+Adam(beta1 = 0.5) with the polynomial step size, one ``sess.run(model.train)`` per ``train_step``, replayed from a hipGraph.
+``train_step`` takes float images; ``train_step_u8`` takes the loader's uint8 arrays and makes the float images, the
+discriminator's real pair and the masked-L1 pixel count from them in one launch inside the graph (csrc/bg_io.hip).  Both take
+any batch N: the reference's placeholders are fixed at 1 (:765-768), nothing else in its graph is, and at N > 1 the norms'
+statistics, the loss means and the masked-L1 count run over the whole batch -- what the float64 oracle computes
+(tests/test_gpu_residual.py holds the trainer to it at N = 2).  The command line (bg_colorization_main.py of this repository)
+drives ``train_step_u8`` at ``--batch_size N`` and writes test-mode PNGs through ``hip.bg_finish_u8``.
 """
 import numpy as np
 import os
@@ -123,9 +132,11 @@ class BGTrainer(object):
         hip.call('ssc_strided_copy', second, 3, xd.view(-1)[3:], 8, M, 3, 0)
         return xd
 
-    def gradients(self, inputs, targets, text, labels_gt):
+    def gradients(self, inputs, targets, text, labels_gt, xd_real=None, count=None):
         """inputs / targets NHWC [N,H,W,3] in [-1,1], text int [N,T] (host), labels_gt int32 [N,H,W].
-        Fills both flat gradient buffers and ``self.losses``; returns the generator context."""
+        Fills both flat gradient buffers and ``self.losses``; returns the generator context.
+        xd_real [N,H,W,8] = the packed real pair [inputs | targets | 0 0] and count [1] = the number of labels != 0, when the
+        caller has them already (``train_step_u8``: hip.bg_stage_u8 writes both); otherwise they are made here."""
         B = self.bufs
         inputs, targets = inputs.contiguous(), targets.contiguous()
         labels = labels_gt.to(device=inputs.device, dtype=torch.int32).contiguous()
@@ -134,7 +145,7 @@ class BGTrainer(object):
         L = self.losses
         L.zero_()
         def real_pass():
-            cr = self.D.forward(self._pack('xd_real', inputs, targets), 'dr')
+            cr = self.D.forward(xd_real if xd_real is not None else self._pack('xd_real', inputs, targets), 'dr')
             nz = cr['z'].numel()
             dz_r = B.get('dz_r', cr['z'].shape)
             hip.call('ssc_bg_gan_loss', cr['z'], nz, 0, 1.0 / nz, L[0:1], dz_r, 1.0 / nz)
@@ -174,8 +185,9 @@ class BGTrainer(object):
         dz_g = B.get('dz_g', cf['z'].shape)
         hip.call('ssc_bg_gan_loss', cf['z'], nz, 0, 1.0 / nz, L[2:3], dz_g, self.w_gan / nz)
         dgan = self.D.backward(cfg, dz_g, False, True, accumulate=False)
-        count = B.get('l1_count', (1,))
-        hip.call('ssc_count_nonzero_i32', labels, M, count, ws, ws.numel() * 4)
+        if count is None:
+            count = B.get('l1_count', (1,))
+            hip.call('ssc_count_nonzero_i32', labels, M, count, ws, ws.numel() * 4)
         dpre = B.get('dpre', (N, H, W, 4))
         hip.call('ssc_bg_output_grad', image, targets, labels, count, 1.0, dgan, L[3:4], dpre, M)
         if self.w_l1 != 1.0:        # the kernel folds the weight into the gradient: run it with the real weight
@@ -231,11 +243,52 @@ class BGTrainer(object):
         st['targets'].copy_(targets)
         st['labels'].copy_(labels_gt)
         prep = text if isinstance(text, dict) else self.G.text.prepare(text, 'bg')
-        key = skey + (prep['S'],)
+        return self._step(skey + (prep['S'],), lambda: self.gradients(st['inputs'], st['targets'], prep, st['labels']))
+
+    def _stage_u8(self, st):
+        """The fused uint8 stage on the static tensors of a shape -> the keyword arguments of ``gradients``."""
+        xd = self.bufs.get('xd_real', tuple(st['fg'].shape[:3]) + (8,), zero_on_alloc=True)
+        count = self.bufs.get('l1_count', (1,))
+        hip.bg_stage_u8(st['fg'], st['bg'], st['labels'], st['inputs'], st['targets'], xd, count)
+        return {'xd_real': xd, 'count': count}
+
+    def train_step_u8(self, fg_u8, bg_u8, text, labels):
+        """``train_step`` fed with what the loader produces: fg_u8 / bg_u8 uint8 [N,H,W,3] (foreground = generator input,
+        background = target), labels int32 [N,H,W]; host (best: pinned) or device tensors, or NumPy arrays.  They are copied
+        into static tensors of the shape and one launch (hip.bg_stage_u8, inside the captured graph) makes the float images
+        u8/255*2-1, the discriminator's packed real pair and the masked-L1 pixel count from them."""
+        fg_u8, bg_u8, labels = [t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+                                for t in (fg_u8, bg_u8, labels)]
+        assert fg_u8.dtype == torch.uint8 and bg_u8.dtype == torch.uint8 and fg_u8.shape == bg_u8.shape
+        assert fg_u8.dim() == 4 and fg_u8.shape[3] == 3 and tuple(labels.shape) == tuple(fg_u8.shape[:3]), \
+            'labels %s for images %s' % (tuple(labels.shape), tuple(fg_u8.shape))
+        dev = self.losses.device
+        skey = ('u8',) + tuple(fg_u8.shape)
+        st = self._static.get(skey)
+        if st is None:
+            st = {'fg': torch.empty(tuple(fg_u8.shape), dtype=torch.uint8, device=dev), 'bg': torch.empty(tuple(fg_u8.shape), dtype=torch.uint8, device=dev),
+                  'labels': torch.empty(tuple(labels.shape), dtype=torch.int32, device=dev),
+                  'inputs': torch.empty(tuple(fg_u8.shape), dtype=torch.float32, device=dev),
+                  'targets': torch.empty(tuple(fg_u8.shape), dtype=torch.float32, device=dev)}
+            self._static[skey] = st
+        st['fg'].copy_(fg_u8, non_blocking=True)
+        st['bg'].copy_(bg_u8, non_blocking=True)
+        st['labels'].copy_(labels, non_blocking=True)
+        if not self.use_graphs or hip.PROFILE is not None:
+            gctx = self.gradients(st['inputs'], st['targets'], text, st['labels'], **self._stage_u8(st))
+            self.apply_gradients()
+            return gctx
+        prep = text if isinstance(text, dict) else self.G.text.prepare(text, 'bg')
+        return self._step(skey + (prep['S'],),
+                          lambda: self.gradients(st['inputs'], st['targets'], prep, st['labels'], **self._stage_u8(st)))
+
+    def _step(self, key, gradients):
+        """The optimizer step around ``gradients()`` (which reads static tensors only), eager the first time ``key`` is seen,
+        captured the second time, replayed from then on."""
         self._adam_prepare()
 
         def impl():
-            self._gctx = self.gradients(st['inputs'], st['targets'], prep, st['labels'])
+            self._gctx = gradients()
             self._adam_launch()
 
         g = self._graphs.get(key)

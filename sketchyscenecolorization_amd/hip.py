@@ -175,6 +175,8 @@ SIGNATURES = {
     'ssc_nhwc_to_nchw': [_P, _P, _I, _I, _I, _I, _I, _P],
     'ssc_sketch_preprocess_u8': [_P, _I, _I, _I, _I, _P, _P],
     'ssc_image_postprocess_u8': [_P, _I, _I, _L, _P, _P],
+    'ssc_bg_stage_u8': [_P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P],
+    'ssc_bg_finish_u8': [_P, _I, _P, _P, _L, _P, _P],
     'ssc_resample_u8': [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'ssc_decode_paired_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     'ssc_distance_map_u8': [_P, _I, _I, _P, _P, _L, _P],
@@ -1063,6 +1065,37 @@ def image_postprocess_u8(src_nhwc, coff=0, out=None):
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=src_nhwc.device)
     check(lib().ssc_image_postprocess_u8(ptr(src_nhwc), ldc, coff, n * h * w, ptr(out), stream_ptr()),
           'image_postprocess_u8')
+    return out
+
+
+def bg_stage_u8(fg_u8, bg_u8, labels, inputs, targets, xd_real, count):
+    """uint8 [N,H,W,3] foreground / background and int32 [N,H,W] labels (device) -> inputs, targets float [N,H,W,3] =
+    u8/255*2-1, xd_real float [N,H,W,8] = [inputs | targets | 0 0] and count[0] = #(labels != 0), in one launch."""
+    n, h, w, c = fg_u8.shape
+    assert c == 3 and fg_u8.dtype == torch.uint8 and bg_u8.dtype == torch.uint8 and labels.dtype == torch.int32
+    assert bg_u8.shape == fg_u8.shape and tuple(labels.shape) == (n, h, w)
+    assert tuple(inputs.shape) == (n, h, w, 3) and tuple(targets.shape) == (n, h, w, 3) and tuple(xd_real.shape) == (n, h, w, 8)
+    assert inputs.dtype == targets.dtype == xd_real.dtype == count.dtype == torch.float32 and count.numel() >= 1
+    for t in (fg_u8, bg_u8, labels, inputs, targets, xd_real):
+        assert t.is_contiguous()
+    ws = workspace()
+    check(lib().ssc_bg_stage_u8(ptr(fg_u8), ptr(bg_u8), ptr(labels), n * h * w, ptr(inputs), ptr(targets), ptr(xd_real),
+                                ptr(count), ptr(ws), ws.numel() * 4, stream_ptr()), 'bg_stage_u8')
+
+
+def bg_finish_u8(image, fg_u8=None, mask_u8=None, out=None):
+    """float [N,H,W,ldc] with the tanh image in channels 0..2 -> uint8 [N,H,W,3], rounded and saturated; where mask_u8
+    [N,H,W] is 0 the pixel of fg_u8 [N,H,W,3] is written instead."""
+    n, h, w, ldc = image.shape
+    assert image.dtype == torch.float32 and image.is_contiguous() and ldc >= 3
+    if mask_u8 is not None:
+        assert fg_u8 is not None and mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous() and mask_u8.numel() == n * h * w
+    if fg_u8 is not None:
+        assert fg_u8.dtype == torch.uint8 and fg_u8.is_contiguous() and tuple(fg_u8.shape) == (n, h, w, 3)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=image.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, h, w, 3)
+    check(lib().ssc_bg_finish_u8(ptr(image), ldc, ptr(fg_u8), ptr(mask_u8), n * h * w, ptr(out), stream_ptr()), 'bg_finish_u8')
     return out
 
 
