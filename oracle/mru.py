@@ -8,6 +8,7 @@ Follows models_collection.py:68-147 (image_encoder_mru), :251-377 (generate_mru)
 :353-461 (mru_conv_block_v3), :527-591 (mru_deconv_block_v2), :594-713 (mru_conv / mru_deconv), NUM_BLOCKS = 1.
 Tensors NCHW; conv weights HWIO; biases stored flat [C] (TF shape (1,C,1,1)); conditional-norm tables [n_labels, C].
 """
+import contextlib
 import math
 from collections import OrderedDict
 
@@ -190,9 +191,60 @@ def _lrelu(x):
     return torch.maximum(0.2 * x, x)
 
 
-def _minmax(x):
-    mn = x.amin(dim=(2, 3), keepdim=True)
-    mx = x.amax(dim=(2, 3), keepdim=True)
+# Optional selection for the min-max gates.  reduce_min / reduce_max send their gradient to the positions that attain the
+# extremum; where the runner-up of a plane lies within fp32 rounding of it, two evaluations in different arithmetic select
+# different positions and every upstream gradient moves with the choice.  ``gate_selection`` lets a caller fix, per gate,
+# WHICH positions count as the extremum (those another implementation chose), so that the remaining arithmetic can be compared.
+_GATE_CTX = None        # (selection, record) inside gate_selection(), else None: plain amin / amax
+_GATE_PASS = None       # which pass of build_single_graph is being evaluated: 'generator' | 'd_real' | 'd_fake'
+
+
+@contextlib.contextmanager
+def gate_selection(selection, record=None):
+    """Inside this context the gate identified by ``(pass, scope)`` -- pass = 'generator' | 'd_real' | 'd_fake' (None outside
+    build_single_graph), scope = the gate conv's variable scope, e.g. 'generator/mru_deconv_unit_t_0_layer_0/Conv_1' -- takes
+    its extrema from ``selection[(pass, scope)] = (sel_min, sel_max)``, boolean masks [N,C,H,W] with at least one position
+    per plane: mn = sum(x * sel_min) / sum(sel_min) over (H,W), likewise mx.  With an exact selection that IS the extremum;
+    with a near-tie selection the value moves by the gap to the extremum and the gradient goes, evenly divided, to the
+    selected positions.  Gates without an entry keep amin / amax.  ``record`` (a dict) receives every evaluated gate's
+    pre-normalisation tensor under its key, selected or not."""
+    global _GATE_CTX
+    old = _GATE_CTX
+    _GATE_CTX = (selection, record)
+    try:
+        yield
+    finally:
+        _GATE_CTX = old
+
+
+@contextlib.contextmanager
+def _gate_pass(name):
+    global _GATE_PASS
+    old = _GATE_PASS
+    _GATE_PASS = name
+    try:
+        yield
+    finally:
+        _GATE_PASS = old
+
+
+def _minmax(x, scope=None):
+    sel = None
+    if _GATE_CTX is not None and scope is not None:
+        selection, record = _GATE_CTX
+        key = (_GATE_PASS, scope)
+        if record is not None:
+            assert key not in record, key
+            record[key] = x.detach()
+        sel = selection.get(key)
+    if sel is None:
+        mn = x.amin(dim=(2, 3), keepdim=True)
+        mx = x.amax(dim=(2, 3), keepdim=True)
+    else:
+        sel_min, sel_max = (m.to(x.dtype) for m in sel)
+        assert sel_min.shape == x.shape and sel_max.shape == x.shape, (key, sel_min.shape, x.shape)
+        mn = (x * sel_min).sum(dim=(2, 3), keepdim=True) / sel_min.sum(dim=(2, 3), keepdim=True)
+        mx = (x * sel_max).sum(dim=(2, 3), keepdim=True) / sel_max.sum(dim=(2, 3), keepdim=True)
     return (x - mn) / (mx - mn)
 
 
@@ -202,7 +254,7 @@ def mru_conv_block_v3(p, pre, inp, ht, d, labels, stride):
     na = lambda t, scope: T.miu_relu(cond_batchnorm(p, pre + '/' + scope, t, labels))
     ht_orig = ht
     full_inp = torch.cat([na(ht, 'norm_activation_in'), inp], 1)
-    rg = _minmax(conv2d(p, pre + '/update_gate', full_inp, act=_lrelu))
+    rg = _minmax(conv2d(p, pre + '/update_gate', full_inp, act=_lrelu), pre + '/update_gate')
     img_new = conv2d(p, pre + '/Conv', inp)
     ht_new_in = na(ht + rg * img_new, 'norm_activation_merge_1')
     h_new = conv2d(p, pre + '/Conv_1', ht_new_in, labels=labels, norm=True, act=T.miu_relu)
@@ -219,8 +271,8 @@ def mru_deconv_block_v2(p, pre, inp, ht, d, labels, stride):
         ht = upsample(ht)
     ch = ht.shape[1]
     full_inp = torch.cat([ht, inp], 1)
-    rg = _minmax(conv2d(p, pre + '/Conv', full_inp, act=_lrelu))
-    zg = _minmax(conv2d(p, pre + '/Conv_1', full_inp, act=_lrelu))
+    rg = _minmax(conv2d(p, pre + '/Conv', full_inp, act=_lrelu), pre + '/Conv')
+    zg = _minmax(conv2d(p, pre + '/Conv_1', full_inp, act=_lrelu), pre + '/Conv_1')
     h_new = conv2d(p, pre + '/Conv_2', torch.cat([rg * ht, inp], 1), labels=labels, norm=True, act=T.miu_relu)
     h_new = conv2d(p, pre + '/Conv_3', h_new, labels=labels, norm=True, act=T.miu_relu)
     if ch != d:
@@ -290,7 +342,7 @@ def _d_conv_block(p, pre, inp, ht, d, us):
     """mru_conv_block_v3 with sn=True, activation prelu, no normaliser."""
     ch = ht.shape[1]
     full_inp = torch.cat([_prelu(p, pre + '/norm_activation_in', ht), inp], 1)
-    rg = _minmax(_sn_conv2d(p, pre + '/update_gate', full_inp, us, act=_lrelu))
+    rg = _minmax(_sn_conv2d(p, pre + '/update_gate', full_inp, us, act=_lrelu), pre + '/update_gate')
     img_new = _sn_conv2d(p, pre + '/Conv', inp, us)
     ht_new_in = _prelu(p, pre + '/norm_activation_merge_1', ht + rg * img_new)
     h_new = _sn_conv2d(p, pre + '/Conv_1', ht_new_in, us, act=lambda t: _prelu(p, pre + '/Conv_1', t))
@@ -339,9 +391,12 @@ def build_single_graph(p, images, sketches, images_d, class_id, class_id_d, text
     """One MRU tower (graph_single.py:221-314, block_type='MRU'): both losses and both gradient sets."""
     from .pix2pix import get_losses
     q = OrderedDict((k, v.detach().clone().requires_grad_(not k.endswith('/u'))) for k, v in p.items())
-    gen = generate_mru(q, sketches, text, class_id, noise_vec, lstm_hybrid)
-    real_disc, real_logit, us = discriminate_mru(q, sketches, images_d, return_u=True)
-    fake_disc, fake_logit = discriminate_mru(q, sketches, gen)
+    with _gate_pass('generator'):
+        gen = generate_mru(q, sketches, text, class_id, noise_vec, lstm_hybrid)
+    with _gate_pass('d_real'):
+        real_disc, real_logit, us = discriminate_mru(q, sketches, images_d, return_u=True)
+    with _gate_pass('d_fake'):
+        fake_disc, fake_logit = discriminate_mru(q, sketches, gen)
     loss_g, loss_d, parts = get_losses(q, images, gen, class_id, class_id_d, real_disc, fake_disc, real_logit,
                                        fake_logit, reg=regularization_loss)
     g_names = [k for k in q if k.startswith('generator/')]

@@ -181,15 +181,40 @@ def test_block_output_backward(two, act):
         close(dz, sc.grad, tol=5e-5)       # identity shortcut: its gradient is dz itself
 
 
-@pytest.mark.parametrize('n,h,ci,co', [(3, 48, 128, 128), (2, 96, 64, 64), (2, 12, 64, 128)])
-def test_gate_extrema_from_the_conv_epilogue(n, h, ci, co):
+def _tied_conv_case(n, h, ci, co):
+    """Integer-valued inputs (-2 .. 2), filter (-1 .. 1) and bias, the input a 24 x 24 tile repeated over the image: every fp32 (and
+    bf16-split) product and partial sum is an exact small integer whatever the order of the additions, so the conv output is
+    THE exact value, and every interior position repeats with the tile's period -- exact ties in every (sample, channel) plane."""
+    g = torch.Generator().manual_seed(44)
+    tile = torch.randint(-2, 3, (n, 24, 24, ci), generator=g).float()
+    x = tile.repeat(1, h // 24, h // 24, 1)
+    w = torch.randint(-1, 2, (3, 3, ci, co), generator=g).float()
+    b = torch.randint(-3, 4, (co,), generator=g).float()
+    y = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2).double(), w.permute(3, 2, 0, 1).double(), b.double(), padding=1)
+    y = y.permute(0, 2, 3, 1).float()            # |y| <= 2 * 9 * ci + 3 < 2^24: exact in fp32
+    return x, w, b, torch.maximum(0.2 * y, y)
+
+
+@pytest.mark.parametrize('n,h,ci,co,ties', [pytest.param(3, 48, 128, 128, False, id='3-48-128-128'),
+                                            pytest.param(2, 96, 64, 64, False, id='2-96-64-64'),
+                                            pytest.param(2, 12, 64, 128, False, id='2-12-64-128'),
+                                            pytest.param(2, 96, 64, 64, True, id='2-96-64-64-exact-ties')])
+def test_gate_extrema_from_the_conv_epilogue(n, h, ci, co, ties):
     """conv 3x3 SAME + bias + lrelu, then reduce_min / reduce_max over the positions of every sample and channel (mru.py:
     407-415): ssc_conv_forward_minmax (extrema out of the epilogue where a sample's positions are whole tiles; the 12 x 12 case
-    takes the separate pass) against torch, and the conv output against the plain launch bit for bit."""
+    takes the separate pass) against torch, and the conv output against the plain launch bit for bit.  The exact-ties input
+    (_tied_conv_case) has several positions attaining each extremum of every plane: the epilogue's extrema must equal
+    ssc_minmax_hw of the stored output bitwise and mark the same tied positions -- the set the gate backward divides over."""
     hip = _hip()
-    x = rnd(n, h, h, ci, seed=41).cuda()
-    w = rnd(3, 3, ci, co, seed=42, std=0.05).cuda()
-    b = (0.1 * rnd(co, seed=43)).cuda()
+    if ties:
+        x, w, b, want = _tied_conv_case(n, h, ci, co)
+        flat = want.view(n, h * h, co)
+        assert int((flat == flat.amin(1, keepdim=True)).sum(1).min()) >= 2 and int((flat == flat.amax(1, keepdim=True)).sum(1).min()) >= 2
+        x, w, b = x.cuda(), w.cuda(), b.cuda()
+    else:
+        x = rnd(n, h, h, ci, seed=41).cuda()
+        w = rnd(3, 3, ci, co, seed=42, std=0.05).cuda()
+        b = (0.1 * rnd(co, seed=43)).cuda()
     plain = torch.full((n, h, h, co), float('nan'), device='cuda')
     hip.conv_forward(hip.View(x), w, 1, 0, plain, bias=b, epi=2, same=True)
     out = torch.full((n, h, h, co), float('nan'), device='cuda')
@@ -198,6 +223,15 @@ def test_gate_extrema_from_the_conv_epilogue(n, h, ci, co):
     assert torch.equal(out, plain)
     flat = plain.view(n, h * h, co)
     assert torch.equal(mm[:, 0], flat.amin(1)) and torch.equal(mm[:, 1], flat.amax(1))
+    if ties:
+        assert torch.equal(out.cpu(), want), float((out.cpu() - want).abs().max())      # exact sums: the conv itself has one answer
+        mm2 = torch.full((n, 2, co), float('nan'), device='cuda')
+        hip.minmax_hw(out, mm2)
+        assert torch.equal(mm, mm2)
+        o = out.view(n, h * h, co)
+        for k in (0, 1):
+            a, c = o == mm[:, k][:, None, :], o == mm2[:, k][:, None, :]
+            assert torch.equal(a, c) and int(a.sum(1).min()) >= 2
 
 
 @pytest.mark.parametrize('m_hw,k,act,with_bn', [((3, 40, 48), 32, 2, True), ((4, 24, 24), 128, 1, True), ((5, 37, 21), 16, 0, False),
