@@ -266,6 +266,20 @@ int ssc_image_postprocess_u8(const float* src, int ldc, int coff, int64_t M, uin
  * 8-byte aligned (zeroed on the stream by this call).  fg / bg 4-byte, the other arrays 16-byte aligned. */
 int ssc_bg_stage_u8(const uint8_t* fg, const uint8_t* bg, const int32_t* labels, int64_t M, float* inputs, float* targets,
                     float* xd_real, float* count, void* workspace, int64_t workspace_bytes, void* stream);
+/* The same pass for a batch of N samples of P pixels gathered from device-resident caches: fg_cache uint8 [S_fg,P,3], bg_cache
+ * uint8 [S_bg,P,3], seg_cache uint8 [S_seg,P] = the red channel of the segment png; slot int32 [N,3] = the fg, bg and seg entry
+ * of each sample.  Writes what ssc_bg_stage_u8 writes and labels int32 [N,P] = 1 where seg == 128, 2 where seg == 255, else 0
+ * (data_processing/image_processing.py:14-25).  recolor uint8 [N,8] = {enable, sky r, g, b, ground r, g, b, 0} (may be NULL):
+ * where enable != 0 the background is seg == 128 ? sky : seg == 255 ? ground : bg, the augmented background of
+ * data_preparation/bg_data_generation.py:120-160 made from the base one.  A sample whose slot lies outside its cache reads
+ * nothing: its float outputs are NaN (the pair's two pad lanes stay 0), its labels 0, and count[0] is NaN.  N * P <= 2^24.
+ * workspace: 8 bytes, 8-byte aligned (zeroed on the stream by this call).  Caches and slot 4-byte, recolor 8-byte, the outputs
+ * 16-byte aligned; entries and float rows inside them need no alignment (P may be any number).
+ * Returns -1 for sizes out of range, -2 for the workspace, -3 for a misaligned pointer. */
+int ssc_bg_stage_cached_u8(const uint8_t* fg_cache, int64_t S_fg, const uint8_t* bg_cache, int64_t S_bg, const uint8_t* seg_cache,
+                           int64_t S_seg, const int32_t* slot, const uint8_t* recolor, int64_t N, int64_t P, float* inputs,
+                           float* targets, float* xd_real, int32_t* labels, float* count, void* workspace,
+                           int64_t workspace_bytes, void* stream);
 /* img float rows of ldc >= 3 floats (the generator's tanh image) -> out uint8 [M,3] = floor(clamp((x+1)/2, 0, 1)*255 + 0.5)
  * clamped to 0..255 (deprocess + convert_image_dtype(saturate=True), :36-39, 785-786); where mask uint8 [M] (may be NULL) is 0
  * the pixel of fg uint8 [M,3] is written instead (the paste-back of test mode, :861-871).  fg may be NULL without a mask. */

@@ -8,7 +8,9 @@ those TF names so a converted checkpoint loads with ``store.load_dict``.
 ``BGTrainer`` is ``create_model`` in train mode: generator with region branch, residual discriminator, the three loss terms,
 Adam(beta1 = 0.5) with the polynomial step size, one ``sess.run(model.train)`` per ``train_step``, replayed from a hipGraph.
 ``train_step`` takes float images; ``train_step_u8`` takes the loader's uint8 arrays and makes the float images, the
-discriminator's real pair and the masked-L1 pixel count from them in one launch inside the graph (csrc/bg_io.hip).  Both take
+discriminator's real pair and the masked-L1 pixel count from them in one launch inside the graph (csrc/bg_io.hip);
+``train_step_cached`` takes the entries of scenes that a ``scene_cache.SceneCache`` keeps on the device and gathers them in that
+launch, with the labels and an optional sky / ground recolouring.  All take
 any batch N: the reference's placeholders are fixed at 1 (:765-768), nothing else in its graph is, and at N > 1 the norms'
 statistics, the loss means and the masked-L1 count run over the whole batch -- what the float64 oracle computes
 (tests/test_gpu_residual.py holds the trainer to it at N = 2).  The command line (bg_colorization_main.py of this repository)
@@ -281,6 +283,67 @@ class BGTrainer(object):
         prep = text if isinstance(text, dict) else self.G.text.prepare(text, 'bg')
         return self._step(skey + (prep['S'],),
                           lambda: self.gradients(st['inputs'], st['targets'], prep, st['labels'], **self._stage_u8(st)))
+
+    def _stage_cached(self, cache, st):
+        """The cached stage on the static tensors of a batch shape -> the keyword arguments of ``gradients``."""
+        xd = self.bufs.get('xd_real', tuple(st['inputs'].shape[:3]) + (8,), zero_on_alloc=True)
+        count = self.bufs.get('l1_count', (1,))
+        hip.bg_stage_cached_u8(cache.fg, cache.bg, cache.seg, st['slot'], st['recolor'], st['inputs'], st['targets'], xd,
+                               st['labels'], count)
+        return {'xd_real': xd, 'count': count}
+
+    @staticmethod
+    def _small_upload(st, name, values, dtype):
+        """values (NumPy array or host tensor of the static tensor's shape) -> st[name], without a host wait: through one of
+        four pinned buffers used in turn, each written again only when the copy that last read it has happened."""
+        if torch.is_tensor(values) and (values.is_cuda or values.is_pinned()):
+            st[name].copy_(values, non_blocking=True)
+            return
+        ring = st.setdefault('ring_' + name, [])
+        turn = st['turn_' + name] = st.get('turn_' + name, -1) + 1
+        if turn < 4:
+            ring.append((torch.empty(tuple(st[name].shape), dtype=dtype).pin_memory(), torch.cuda.Event()))
+        buf, ev = ring[turn % 4]
+        ev.synchronize()        # (an event that was never recorded does not wait)
+        buf.copy_(values if torch.is_tensor(values) else torch.from_numpy(np.ascontiguousarray(values, dtype=buf.numpy().dtype)))
+        st[name].copy_(buf, non_blocking=True)
+        ev.record()
+
+    def train_step_cached(self, cache, slots, recolor, text):
+        """``train_step_u8`` on scenes that live on the device already: cache.fg / cache.bg uint8 [S,H,W,3] and cache.seg uint8
+        [S,H,W] (the segment png's red channel; a ``scene_cache.SceneCache``), allocated once -- their addresses are part of the
+        captured graph.  slots int [N,3] = the fg, bg and seg entry of each sample; recolor uint8 [N,8] = {enable, sky rgb,
+        ground rgb, 0} per sample or None (nothing recoloured).  Only these two small arrays are copied in a step; one launch
+        (hip.bg_stage_cached_u8, inside the graph) gathers the scenes and makes the float images, the labels, the packed real
+        pair and the masked-L1 pixel count."""
+        dev = self.losses.device
+        assert cache.fg.device == dev and cache.fg.dtype == torch.uint8 and cache.fg.dim() == 4
+        N, (H, W) = len(slots), cache.fg.shape[1:3]
+        assert tuple(slots.shape) == (N, 3) and (recolor is None or tuple(recolor.shape) == (N, 8))
+        skey = ('cached', N, H, W, cache.fg.data_ptr(), cache.bg.data_ptr(), cache.seg.data_ptr(),
+                cache.fg.shape[0], cache.bg.shape[0], cache.seg.shape[0])
+        st = self._static.get(skey)
+        if st is None:
+            st = {'slot': torch.zeros((N, 3), dtype=torch.int32, device=dev),
+                  'recolor': torch.zeros((N, 8), dtype=torch.uint8, device=dev), 'painted': False,
+                  'labels': torch.empty((N, H, W), dtype=torch.int32, device=dev),
+                  'inputs': torch.empty((N, H, W, 3), dtype=torch.float32, device=dev),
+                  'targets': torch.empty((N, H, W, 3), dtype=torch.float32, device=dev)}
+            self._static[skey] = st
+        self._small_upload(st, 'slot', slots, torch.int32)
+        if recolor is not None:
+            self._small_upload(st, 'recolor', recolor, torch.uint8)
+            st['painted'] = True
+        elif st['painted']:         # the static record still enables a colour pair of an earlier step
+            st['recolor'].zero_()
+            st['painted'] = False
+        if not self.use_graphs or hip.PROFILE is not None:
+            gctx = self.gradients(st['inputs'], st['targets'], text, st['labels'], **self._stage_cached(cache, st))
+            self.apply_gradients()
+            return gctx
+        prep = text if isinstance(text, dict) else self.G.text.prepare(text, 'bg')
+        return self._step(skey + (prep['S'],),
+                          lambda: self.gradients(st['inputs'], st['targets'], prep, st['labels'], **self._stage_cached(cache, st)))
 
     def _step(self, key, gradients):
         """The optimizer step around ``gradients()`` (which reads static tensors only), eager the first time ``key`` is seen,

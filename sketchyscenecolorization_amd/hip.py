@@ -176,6 +176,7 @@ SIGNATURES = {
     'ssc_sketch_preprocess_u8': [_P, _I, _I, _I, _I, _P, _P],
     'ssc_image_postprocess_u8': [_P, _I, _I, _L, _P, _P],
     'ssc_bg_stage_u8': [_P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P],
+    'ssc_bg_stage_cached_u8': [_P, _L, _P, _L, _P, _L, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P],
     'ssc_bg_finish_u8': [_P, _I, _P, _P, _L, _P, _P],
     'ssc_resample_u8': [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'ssc_decode_paired_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
@@ -1081,6 +1082,28 @@ def bg_stage_u8(fg_u8, bg_u8, labels, inputs, targets, xd_real, count):
     ws = workspace()
     check(lib().ssc_bg_stage_u8(ptr(fg_u8), ptr(bg_u8), ptr(labels), n * h * w, ptr(inputs), ptr(targets), ptr(xd_real),
                                 ptr(count), ptr(ws), ws.numel() * 4, stream_ptr()), 'bg_stage_u8')
+
+
+def bg_stage_cached_u8(fg_cache, bg_cache, seg_cache, slot, recolor, inputs, targets, xd_real, labels, count):
+    """bg_stage_u8 for N samples gathered from device caches: fg_cache / bg_cache uint8 [S,H,W,3], seg_cache uint8 [S,H,W] (the
+    segment png's red channel), slot int32 [N,3] = each sample's fg, bg and seg entry, recolor uint8 [N,8] = {enable, sky rgb,
+    ground rgb, 0} or None -> inputs, targets float [N,H,W,3], xd_real float [N,H,W,8], labels int32 [N,H,W] (128 -> 1,
+    255 -> 2, else 0) and count[0] = #(labels != 0), in one launch.  A slot outside its cache: NaN floats, labels 0, NaN count."""
+    n, h, w, c = inputs.shape
+    assert c == 3 and fg_cache.dtype == bg_cache.dtype == seg_cache.dtype == torch.uint8
+    assert slot.dtype == torch.int32 and tuple(slot.shape) == (n, 3) and labels.dtype == torch.int32
+    assert tuple(fg_cache.shape[1:]) == (h, w, 3) and tuple(bg_cache.shape[1:]) == (h, w, 3) and tuple(seg_cache.shape[1:]) == (h, w)
+    assert tuple(targets.shape) == (n, h, w, 3) and tuple(xd_real.shape) == (n, h, w, 8) and tuple(labels.shape) == (n, h, w)
+    assert inputs.dtype == targets.dtype == xd_real.dtype == count.dtype == torch.float32 and count.numel() >= 1
+    if recolor is not None:
+        assert recolor.dtype == torch.uint8 and tuple(recolor.shape) == (n, 8) and recolor.is_contiguous()
+    for t in (fg_cache, bg_cache, seg_cache, slot, inputs, targets, xd_real, labels):
+        assert t.is_contiguous()
+    ws = workspace()
+    check(lib().ssc_bg_stage_cached_u8(ptr(fg_cache), fg_cache.shape[0], ptr(bg_cache), bg_cache.shape[0], ptr(seg_cache),
+                                       seg_cache.shape[0], ptr(slot), ptr(recolor), n, h * w, ptr(inputs), ptr(targets),
+                                       ptr(xd_real), ptr(labels), ptr(count), ptr(ws), ws.numel() * 4, stream_ptr()),
+          'bg_stage_cached_u8')
 
 
 def bg_finish_u8(image, fg_u8=None, mask_u8=None, out=None):
