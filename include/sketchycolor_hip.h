@@ -302,6 +302,20 @@ int ssc_resample_u8(const uint8_t* src, int H, int W, int C, int chan, const int
  * that is not NULL (distance maps).  mnmx: [N,2] scratch (per-image min, max). */
 int ssc_decode_paired_u8(const uint8_t* img, const uint8_t* sk, const float* sk_f32, int N, int R, int size,
                          const float* noise, float* img_out, float* sk_out, float* mnmx, void* stream);
+/* The first half of ssc_decode_paired_u8 alone: mnmx [N,2] = the minimum and maximum of each image of img uint8 [N,R,R,3]
+ * resized to size x size (its pixels (f*y, f*x)).  Exact; the record cache computes it once per record.
+ * Returns -1 for sizes out of range (R % size != 0, N < 0); N == 0 returns 0. */
+int ssc_decode_minmax_u8(const uint8_t* img, int N, int R, int size, float* mnmx, void* stream);
+/* ssc_decode_paired_u8 for N samples gathered from a device-resident record cache, in one launch: img_cache / sk_cache uint8
+ * [S,R,R,3], skf_cache float [S,R,R,3] = the cached distance maps (when it is not NULL, sk_cache may be NULL), mnmx_cache float
+ * [S,2] from ssc_decode_minmax_u8 at the same size, idx int32 [N] (device memory, read by the kernel: the host does not wait).
+ * Output n is bit for bit what ssc_decode_paired_u8 writes for record idx[n] with noise [N,size,size,3] (may be NULL).
+ * sk_out == NULL: the sketch is neither read nor written.  An idx[n] outside [0,S) reads nothing and makes the outputs of
+ * sample n NaN.  No scratch.  Returns -1 for sizes out of range (R % size != 0, N < 0, S <= 0 or S >= 2^31), -2 for sk_out
+ * without a sketch cache; N == 0 returns 0. */
+int ssc_decode_paired_cached_u8(const uint8_t* img_cache, const uint8_t* sk_cache, const float* skf_cache,
+                                const float* mnmx_cache, int64_t S, const int32_t* idx, int N, int R, int size,
+                                const float* noise, float* img_out, float* sk_out, void* stream);
 /* --distance_map 1 (input_pipeline.py:86-96): sk uint8 [N,R,R,3] -> out float [N,R,R,3] = exact Euclidean distance of
  * every voxel to the nearest stroke voxel (sk < 250; scipy.ndimage.distance_transform_edt over [R,R,3]) / max * 255.
  * Pass it to ssc_decode_paired_u8 as sk_f32 (then sk may be NULL).  ws: (2*N*R*R*3 + N) int32 of scratch. */

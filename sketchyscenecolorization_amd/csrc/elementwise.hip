@@ -155,6 +155,96 @@ __global__ void decode_write_kernel(const unsigned char* __restrict__ img, const
     }
 }
 
+// The same decode for a batch gathered from a device-resident record cache (--record_cache device): sample n is record idx[n]
+// of img / sk uint8 [S,R,R,3] (or skf float [S,R,R,3], the cached distance maps), its minimum and maximum come from mnmx [S,2]
+// (decode_minmax_kernel, once per record when the cache is built), so one launch does what the two above do and needs no
+// scratch.  One thread per output pixel, x fastest: the six plane stores of a wave are contiguous, its loads cover one
+// contiguous stretch of 64 * 3f bytes of each source row.  F > 0: the factor at compile time, even, every record and row
+// 2-byte (floats: 8-byte) aligned -- a pixel's 3F bytes of a row are 3F/2 16-bit loads (3F/2 float2) instead of 3F byte
+// loads; F == 0: any factor, one element at a time.  The sums run in decode_write_kernel's order (rows, then columns).
+// A record number outside [0,S) is tested before any address is formed: nothing is read, the sample's outputs are NaN.
+template <int F>
+__global__ __launch_bounds__(256) void decode_cached_kernel(const unsigned char* __restrict__ img,
+                                                            const unsigned char* __restrict__ sk,
+                                                            const float* __restrict__ skf, const float* __restrict__ mnmx,
+                                                            long S, const int* __restrict__ idx, int N, int R, int f_any, int size,
+                                                            const float* __restrict__ noise, float* __restrict__ img_out,
+                                                            float* __restrict__ sk_out) {
+    const int f = F > 0 ? F : f_any;
+    const long plane = (long)size * size;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;             // over [N, size, size] pixels
+    if (i >= (long)N * plane) return;
+    const int n = (int)(i / plane);
+    const int p = (int)(i - (long)n * plane);
+    const int y = p / size, x = p - y * size;
+    float* oi = img_out + (long)n * 3 * plane + p;
+    float* os = sk_out != nullptr ? sk_out + (long)n * 3 * plane + p : nullptr;
+    const long s = idx[n];
+    if (s < 0 || s >= S) {
+        const float nan = __builtin_nanf("");
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            oi[c * plane] = nan;
+            if (os != nullptr) os[c * plane] = nan;
+        }
+        return;
+    }
+    const long src = ((long)s * R * R + (long)(y * f) * R + (long)x * f) * 3;       // the block's first element
+    float a[3];
+    if (F > 0) {
+        const unsigned w0 = *reinterpret_cast<const unsigned short*>(img + src);
+        const unsigned w1 = *reinterpret_cast<const unsigned short*>(img + src + 2);
+        a[0] = (float)(w0 & 0xffu); a[1] = (float)(w0 >> 8); a[2] = (float)(w1 & 0xffu);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a[c] = (float)img[src + c];
+    }
+    const float mn = mnmx[2 * s], mx = mnmx[2 * s + 1];
+    const float den = mx - mn + 1.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v = (a[c] - mn) / den;
+        if (noise != nullptr) v += noise[i * 3 + c];
+        oi[c * plane] = v * 2.f - 1.f;
+    }
+    if (os == nullptr) return;
+    float acc[3] = {0.f, 0.f, 0.f};
+    if (F > 0) {
+        constexpr int E = F > 0 ? 3 * F : 2;      // elements of a block's row
+#pragma unroll
+        for (int dy = 0; dy < F; ++dy) {
+            float v[E];
+            const long o = src + (long)dy * R * 3;
+            if (skf != nullptr) {
+#pragma unroll
+                for (int k = 0; k < E / 2; ++k) {
+                    const float2 w = *reinterpret_cast<const float2*>(skf + o + 2 * k);
+                    v[2 * k] = w.x; v[2 * k + 1] = w.y;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < E / 2; ++k) {
+                    const unsigned w = *reinterpret_cast<const unsigned short*>(sk + o + 2 * k);
+                    v[2 * k] = (float)(w & 0xffu); v[2 * k + 1] = (float)(w >> 8);
+                }
+            }
+#pragma unroll
+            for (int dx = 0; dx < F; ++dx)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] += v[3 * dx + c];
+        }
+    } else {
+        for (int dy = 0; dy < f; ++dy)
+            for (int dx = 0; dx < f; ++dx) {
+                const long o = src + ((long)dy * R + dx) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] += (skf != nullptr) ? skf[o + c] : (float)sk[o + c];
+            }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) os[c * plane] = acc[c] / (float)(f * f) / 255.f * 2.f - 1.f;
+}
+
 // ------------------------------------------------------------------ --distance_map 1 (input_pipeline.py:86-96)
 // sk -> 0 where sk < 250 else 255; scipy.ndimage.distance_transform_edt of the [R,R,3] array (the channel axis counts as
 // a third spatial axis, as in the reference); / max * 255.  Exact Euclidean distances: squared distances are integers,
@@ -264,6 +354,36 @@ extern "C" int ssc_decode_paired_u8(const uint8_t* img, const uint8_t* sk, const
     const long tot = (long)N * size * size;
     hipLaunchKernelGGL(decode_write_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, img, sk, sk_f32, N, R, f,
                        size, mnmx, noise, img_out, sk_out);
+    return CHECK_LAUNCH();
+}
+
+extern "C" int ssc_decode_minmax_u8(const uint8_t* img, int N, int R, int size, float* mnmx, void* stream) {
+    if (N < 0 || size <= 0 || R <= 0 || R % size != 0) return -1;
+    if (N == 0) return 0;
+    hipLaunchKernelGGL(decode_minmax_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, img, R, R / size, size, mnmx);
+    return CHECK_LAUNCH();
+}
+
+extern "C" int ssc_decode_paired_cached_u8(const uint8_t* img_cache, const uint8_t* sk_cache, const float* skf_cache,
+                                           const float* mnmx_cache, int64_t S, const int32_t* idx, int N, int R, int size,
+                                           const float* noise, float* img_out, float* sk_out, void* stream) {
+    if (N < 0 || S <= 0 || S > INT32_MAX || size <= 0 || R <= 0 || R % size != 0) return -1;
+    if (sk_out != nullptr && sk_cache == nullptr && skf_cache == nullptr) return -2;
+    if (N == 0) return 0;
+    const int f = R / size;
+    const long tot = (long)N * size * size;
+    if ((tot + 255) / 256 > INT32_MAX) return -1;
+    const dim3 grid((unsigned)((tot + 255) / 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    // an even factor makes R even: every record, row and block then starts on an even byte (an 8-byte boundary of the floats)
+    const bool wide = (((uintptr_t)img_cache | (uintptr_t)sk_cache) & 1) == 0 && ((uintptr_t)skf_cache & 7) == 0;
+#define SSC_DECODE_CACHED(F)                                                                                                  \
+    hipLaunchKernelGGL(decode_cached_kernel<F>, grid, block, 0, st, img_cache, sk_cache, skf_cache, mnmx_cache, (long)S, idx, \
+                       N, R, f, size, noise, img_out, sk_out)
+    if (wide && f == 2) SSC_DECODE_CACHED(2);
+    else if (wide && f == 6) SSC_DECODE_CACHED(6);
+    else SSC_DECODE_CACHED(0);
+#undef SSC_DECODE_CACHED
     return CHECK_LAUNCH();
 }
 

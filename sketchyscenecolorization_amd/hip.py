@@ -180,6 +180,8 @@ SIGNATURES = {
     'ssc_bg_finish_u8': [_P, _I, _P, _P, _L, _P, _P],
     'ssc_resample_u8': [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'ssc_decode_paired_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    'ssc_decode_minmax_u8': [_P, _I, _I, _I, _P, _P],
+    'ssc_decode_paired_cached_u8': [_P, _P, _P, _P, _L, _P, _I, _I, _I, _P, _P, _P, _P],
     'ssc_distance_map_u8': [_P, _I, _I, _P, _P, _L, _P],
     'ssc_fill': [_P, _F, _L, _P],
     'ssc_timestamp': [_P, _P],
@@ -1141,12 +1143,14 @@ def resample_u8(src_u8, new_h, new_w, coeffs_h, coeffs_v, chan=-1, out_hw=None, 
     return dst
 
 
-def distance_map_u8(sk_u8):
+def distance_map_u8(sk_u8, out=None):
     """--distance_map 1: uint8 sketches [N,R,R,3] (device) -> float [N,R,R,3], exact Euclidean distance to the nearest
     stroke voxel scaled to [0, 255] (input_pipeline.py:86-96)."""
     n, r, r2, c = sk_u8.shape
     assert r == r2 and c == 3 and sk_u8.dtype == torch.uint8 and sk_u8.is_contiguous()
-    out = torch.empty((n, r, r, 3), dtype=torch.float32, device=sk_u8.device)
+    if out is None:
+        out = torch.empty((n, r, r, 3), dtype=torch.float32, device=sk_u8.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, r, r, 3)
     ws = torch.empty(2 * out.numel() + n, dtype=torch.int32, device=sk_u8.device)
     check(lib().ssc_distance_map_u8(ptr(sk_u8), n, r, ptr(out), ptr(ws), ws.numel() * 4, stream_ptr()), 'distance_map_u8')
     return out
@@ -1167,6 +1171,48 @@ def decode_paired_u8(img_u8, sk_u8, size, noise=None, img_out=None, sk_out=None,
     skf = distance_map_u8(sk_u8) if distance_map else None
     check(lib().ssc_decode_paired_u8(ptr(img_u8), ptr(sk_u8), ptr(skf), n, r, size, ptr(noise), ptr(img_out),
                                      ptr(sk_out), ptr(mnmx), stream_ptr()), 'decode_paired_u8')
+    return img_out, sk_out
+
+
+def decode_minmax_u8(img_u8, size, out=None):
+    """Raw record images uint8 [N,R,R,3] (device) -> float [N,2] = the minimum and maximum of each image resized to
+    size x size, the normalisation constants of ``decode_paired_u8`` (exact: the record cache keeps them)."""
+    n, r, r2, c = img_u8.shape
+    assert r == r2 and c == 3 and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and r % size == 0
+    if out is None:
+        out = torch.empty((n, 2), dtype=torch.float32, device=img_u8.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 2)
+    check(lib().ssc_decode_minmax_u8(ptr(img_u8), n, r, size, ptr(out), stream_ptr()), 'decode_minmax_u8')
+    return out
+
+
+def decode_paired_cached_u8(cache, idx, size, noise=None, img_out=None, want_sketch=True, sk_out=None):
+    """``decode_paired_u8`` of the records idx int32 [N] (device) of a record cache, gathered and decoded by one launch.
+    cache: img, sk uint8 [S,R,R,3] (device), skf float [S,R,R,3] or None (the distance maps; sk may then be None), mnmx float
+    [S,2] for ``cache.size`` == size (``record_cache.RecordCache``).  -> (image, sketch) float NCHW [N,3,size,size];
+    want_sketch=False: the sketches are not read and (image, None) comes back.  A record number outside [0,S): NaN outputs."""
+    assert cache.size == size and cache.mnmx is not None, 'the cache was built for another image size'
+    s, r, r2, c = cache.img.shape
+    sk, skf = cache.sk, cache.skf
+    assert r == r2 and c == 3 and r % size == 0 and cache.img.dtype == torch.uint8 and cache.img.is_contiguous()
+    assert sk is None or (sk.dtype == torch.uint8 and sk.shape == cache.img.shape and sk.is_contiguous())
+    assert skf is None or (skf.dtype == torch.float32 and skf.shape == cache.img.shape and skf.is_contiguous())
+    assert cache.mnmx.dtype == torch.float32 and tuple(cache.mnmx.shape) == (s, 2) and cache.mnmx.is_contiguous()
+    assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()
+    n = idx.shape[0]
+    if noise is not None:
+        assert noise.dtype == torch.float32 and noise.is_contiguous() and tuple(noise.shape) == (n, size, size, 3)
+    if img_out is None:
+        img_out = torch.empty((n, 3, size, size), dtype=torch.float32, device=idx.device)
+    if not want_sketch:
+        sk_out = None
+    elif sk_out is None:
+        sk_out = torch.empty((n, 3, size, size), dtype=torch.float32, device=idx.device)
+    for t in (img_out, sk_out):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, 3, size, size))
+    assert not want_sketch or sk is not None or skf is not None
+    check(lib().ssc_decode_paired_cached_u8(ptr(cache.img), ptr(sk), ptr(skf), ptr(cache.mnmx), s, ptr(idx), n, r, size,
+                                            ptr(noise), ptr(img_out), ptr(sk_out), stream_ptr()), 'decode_paired_cached_u8')
     return img_out, sk_out
 
 

@@ -178,11 +178,17 @@ class PairedQueue(object):
     through a shuffle buffer of ``min_after_dequeue`` decoded examples (tf.train.maybe_shuffle_batch, :143-148)."""
 
     def __init__(self, mode, batch_size, data_format='NCHW', distance_map=False, small=False, min_after_dequeue=512,
-                 data_base_dir='data', seed=None, device_decode=None, prefetch=None):
+                 data_base_dir='data', seed=None, device_decode=None, prefetch=None, record_cache=None, want_sketch=True):
         """device_decode (default: on when a GPU is there and the layout is NCHW): the shuffle buffer keeps the raw
         uint8 records and a batch is resized / normalised by one kernel at dequeue (hip.decode_paired_u8, the arithmetic
         of decode_paired_example bit for bit); ``dequeue`` then returns device tensors.  The host decode costs ~3 ms per
-        example, ten times the GPU's step time at batch 32."""
+        example, ten times the GPU's step time at batch 32.
+
+        record_cache (a record_cache.RecordCache of the same files, --record_cache device): the shuffle buffer holds record
+        numbers; ``dequeue`` uploads the N numbers of a batch and one launch gathers and decodes them from the cache
+        (hip.decode_paired_cached_u8).  File order, shuffle and random numbers are those of the queue without a cache, no
+        thread and no image staging buffer exist.  want_sketch=False (with a cache only): the sketches are not decoded and
+        ``dequeue`` returns None in their place -- the discriminator's queue reads images and labels only."""
         from .. import tfrecord
         assert mode in ('train', 'val', 'test')
         data_dir = os.path.join(data_base_dir, 'tfrecord', mode)
@@ -200,12 +206,17 @@ class PairedQueue(object):
             import torch
             device_decode = torch.cuda.is_available() and data_format == 'NCHW'
         self.device_decode = bool(device_decode)
+        self.cache, self.want_sketch = record_cache, bool(want_sketch) or record_cache is None
+        if record_cache is not None:
+            assert list(record_cache.files) == self.files and record_cache.size == self.img_dim[0] and data_format == 'NCHW'
+            assert bool(record_cache.distance_map) == bool(distance_map)
+            self.device_decode = True
         self._gen, self._gen_seed = None, self.rng.randrange(2 ** 31)   # drawn in both modes: same example order
         self._it = self._examples()
         # Training from records: the host half of a batch (read, CRC, parse, stage: ~0.4 ms per 884 KB record, 64 records per
         # iteration of a 12 ms step) runs one batch ahead on a thread of its own.  SSC_RECORD_PREFETCH=0: in the caller.
         # (asked for by the training procedure, main_procedure.RecordQueue; a queue built directly stays synchronous)
-        self.prefetch = bool(prefetch) and self.device_decode and self.shuffle
+        self.prefetch = bool(prefetch) and self.device_decode and self.shuffle and record_cache is None
         self._ring, self._ring_i, self._q, self._thread, self._stop = None, 0, None, None, False
 
     def _examples(self):
@@ -214,6 +225,10 @@ class PairedQueue(object):
             if self.shuffle:
                 self.rng.shuffle(files)
             for path in files:
+                if self.cache is not None:      # record numbers: the bytes are on the device already
+                    for number in range(*self.cache.file_range[path]):
+                        yield number
+                    continue
                 if self.device_decode:
                     # records as views of the mapped file: CRC in place, the images copied once (into the staging buffer)
                     for rec in self.tf.read_records(path, views=True):
@@ -270,6 +285,43 @@ class PairedQueue(object):
             self._gen.manual_seed(self._gen_seed)
         noise = torch.rand((n, size, size, 3), device='cuda', generator=self._gen) * (1.0 / 256)   # dequantisation (:117)
         return hip.decode_paired_u8(dev[0], dev[1], size, noise=noise, distance_map=self.dm)
+
+    # ---- record cache: a batch is N record numbers ----
+    def next_indices(self):
+        """The record numbers of the next batch, in dequeue order (cached queue only)."""
+        assert self.cache is not None
+        ex = []
+        for _ in range(self.batch_size):
+            try:
+                ex.append(self._next())
+            except StopIteration:
+                break
+        if len(ex) < self.batch_size:
+            raise StopIteration
+        return ex
+
+    def _decode_from_cache(self, numbers):
+        """The numbers into a small pinned ring (a slot is reused once the copy out of it has happened), to the device without
+        waiting, the dequantisation noise from the generator of the uncached queue, one gather-decode launch."""
+        import torch
+        from .. import hip
+        n, size = len(numbers), self.img_dim[0]
+        if self._ring is None:
+            self._ring = [[torch.empty((n,), dtype=torch.int32).pin_memory(), None] for _ in range(self._RING)]
+            self._ring_i = 0
+        slot = self._ring[self._ring_i % self._RING]
+        self._ring_i += 1
+        if slot[1] is not None:
+            slot[1].synchronize()
+        slot[0].numpy()[:] = numbers
+        idx = slot[0].to(self.cache.device, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        if self._gen is None:
+            self._gen = torch.Generator(device='cuda')
+            self._gen.manual_seed(self._gen_seed)
+        noise = torch.rand((n, size, size, 3), device='cuda', generator=self._gen) * (1.0 / 256)   # dequantisation (:117)
+        return hip.decode_paired_cached_u8(self.cache, idx, size, noise=noise, want_sketch=self.want_sketch)
 
     # ---- prefetch: the host half of the NEXT batches on a thread of its own ----
     def _producer(self):
@@ -332,6 +384,11 @@ class PairedQueue(object):
     def dequeue(self, with_names=False):
         """One batch: (images [N,3,h,w], sketches, class ids int32 [N], caption indices int32 [N,15])
         [+ category names, image names].  Raises StopIteration when a val / test epoch is exhausted."""
+        if self.cache is not None:
+            c, ex = self.cache, self.next_indices()
+            images, sketches = self._decode_from_cache(ex)
+            out = (images, sketches, c.class_id[ex], c.text[ex])
+            return out + ([c.category[e] for e in ex], [c.name[e] for e in ex]) if with_names else out
         if self.prefetch:
             if self._thread is None:
                 self._start_prefetch()

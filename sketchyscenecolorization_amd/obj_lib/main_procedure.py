@@ -126,12 +126,14 @@ class RecordQueue(object):
     """The same interface over the reference's TFRecords: queue 1 feeds (images, sketches, class_id, text), an
     independently shuffled queue 2 the discriminator's real images and labels (main_procedure.py:109-122)."""
 
-    def __init__(self, batch_size, small, which, data_base_dir='data', seed=None):
+    def __init__(self, batch_size, small, which, data_base_dir='data', seed=None, record_cache=None):
+        """record_cache (--record_cache device): both queues gather from one device cache; queue 2 decodes no sketches."""
         from .input_pipeline import PairedQueue
         # prefetch: the host half of the next batch (read, CRC, parse, pinned staging) on a thread of its own, in dequeue order
         self.q = PairedQueue('train', batch_size, Config.data_format, Config.distance_map != 0, small,
                              data_base_dir=data_base_dir, seed=seed,
-                             prefetch=os.environ.get('SSC_RECORD_PREFETCH', '1') == '1')
+                             prefetch=os.environ.get('SSC_RECORD_PREFETCH', '1') == '1', record_cache=record_cache,
+                             want_sketch=(which == 1))
         self.which = which
         self.cur = None
         self.img = SIZE[bool(small)][0]
@@ -212,10 +214,22 @@ def train(**kwargs):
     # Every process is one tower and owns its queues: it dequeues batch_size examples per step (its share of the
     # reference's batch_size * num_gpu dequeue, input_pipeline.py:143-148 + split_inputs), from its own shuffle.
     if os.path.isdir(os.path.join('data', 'tfrecord', 'train')):     # the reference's dataset location (:109-122)
-        q1 = RecordQueue(batch_size, small, 1, seed=(None if num_gpu == 1 else 7919 * rank + 1))
-        q2 = RecordQueue(batch_size, small, 2, seed=(None if num_gpu == 1 else 7919 * rank + 2))
+        cache = None
+        if getattr(Config, 'record_cache', 'off') == 'device':
+            # every record on the device once, a step uploads record numbers only (record_cache.py).  Found again, not rebuilt,
+            # when a NaN restart calls train() a second time.  Every rank shuffles the whole set itself: each holds all of it.
+            from ..record_cache import get_record_cache
+            cache = get_record_cache(os.path.join('data', 'tfrecord', 'train'), img, distance_map,
+                                     device='cuda:%d' % torch.cuda.current_device())
+            print('record cache: %d records, %d bytes (%.1f MB%s) on %s, built in %.1f s%s'
+                  % (len(cache), cache.nbytes, cache.nbytes / 1e6, ', distance maps included' if distance_map else '',
+                     cache.device, cache.build_seconds,
+                     '; rank %d of %d: every rank holds the full set' % (rank, num_gpu) if num_gpu > 1 else ''))
+        q1 = RecordQueue(batch_size, small, 1, seed=(None if num_gpu == 1 else 7919 * rank + 1), record_cache=cache)
+        q2 = RecordQueue(batch_size, small, 2, seed=(None if num_gpu == 1 else 7919 * rank + 2), record_cache=cache)
     else:
-        print('data/tfrecord/train not found: training on seeded synthetic batches')
+        print('data/tfrecord/train not found: training on seeded synthetic batches'
+              + (' (--record_cache device has nothing to cache)' if getattr(Config, 'record_cache', 'off') == 'device' else ''))
         q1 = SyntheticQueue(batch_size, img, Config.vocab_size, seed=1234 + 1000 * rank)
         q2 = SyntheticQueue(batch_size, img, Config.vocab_size, seed=998244 + 1000 * rank)
     opt_g, opt_d, loss_g, loss_d, merged_all = build_multi_tower_graph(

@@ -81,6 +81,22 @@ def read_records(path, verify=True, views=False):
             yield data
 
 
+def count_records(path):
+    """The number of records of a .tfrecord file, from the length fields alone (nothing else is read or checked)."""
+    n, pos, size = 0, 0, os.path.getsize(path)
+    with open(path, 'rb') as f:
+        while pos < size:
+            f.seek(pos)
+            head = f.read(8)
+            if len(head) != 8:
+                raise IOError('%s: truncated record header' % path)
+            pos += 16 + struct.unpack('<Q', head)[0]
+            n += 1
+    if pos != size:
+        raise IOError('%s: truncated record' % path)
+    return n
+
+
 def write_records(path, payloads):
     with open(path, 'wb') as f:
         for data in payloads:
