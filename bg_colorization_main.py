@@ -17,6 +17,10 @@ with a freshly drawn colour pair, caption to match (class CachedScenes).  Both a
 --batch_size N trains on N scenes per step (the reference's placeholders are fixed at 1, :765-768; nothing else in its graph
 is): the norms' statistics, the loss means and the masked-L1 pixel count then run over the whole batch.  Test mode stays at
 one image per forward pass, because those batch statistics would make every output depend on its batch mates.
+
+--metrics 1 (test mode) scores every ``outputs`` image against its ``targets`` image on the device -- mean absolute error, PSNR
+and SSIM (hip.image_metrics_u8) -- and writes ``results/metrics.json``.  Where the scene has a segment file its red channel is
+the mask: the foreground pixels that were pasted back over the generation are not counted.
 """
 import argparse
 import json
@@ -54,6 +58,8 @@ FLAGS = [
                                                    'on the device as uint8; a step then gathers its scenes by index'),
     ('recolor', int, 0, [0, 1], '1 (needs --scene_cache device): train on the base records only and paint the sky and the ground '
                                 'of every sample with a freshly drawn colour pair on the device, caption to match'),
+    ('metrics', int, 0, [0, 1], '1 (--mode test): score every output against its target on the GPU (MAE, PSNR, SSIM; the '
+                                'pasted-back foreground is not counted) and write results/metrics.json'),
 ]
 
 
@@ -212,6 +218,7 @@ def bg_colorization(**p):
         x = torch.empty((1, size, size, 3), dtype=torch.float32, device='cuda')
         y, xd, cnt = torch.empty_like(x), torch.empty((1, size, size, 8), dtype=torch.float32, device='cuda'), torch.empty(1, device='cuda')
         lab0 = torch.zeros((1, size, size), dtype=torch.int32, device='cuda')
+        names, rows = [], []
         # one image per forward pass whatever --batch_size says: the norms are batch statistics
         for i in range(len(scenes)):
             print('Processing', i, '/', len(scenes))
@@ -225,9 +232,20 @@ def bg_colorization(**p):
             inner = None
             if os.path.exists(seg_path):        # paste the foreground (segment value 0) back over the generation
                 inner = torch.from_numpy(np.ascontiguousarray(np.array(Image.open(seg_path).convert('RGB'), np.uint8)[:, :, 0])).cuda()
-            out = hip.bg_finish_u8(gctx['image'], fg_d, inner).cpu().numpy()
+            out_d = hip.bg_finish_u8(gctx['image'], fg_d, inner)
+            out = out_d.cpu().numpy()
+            if p.get('metrics', 0):     # out_d holds the bytes that are written below; the mask is the paste-back's
+                rows.append(hip.image_metrics_u8(out_d, torch.from_numpy(bg).cuda(),
+                                                 None if inner is None else inner.reshape(1, size, size)).cpu().numpy())
+                names.append(bg_name[:-4])
             for kind, arr in (('inputs', fg), ('outputs', out), ('targets', bg)):
                 Image.fromarray(arr[0], 'RGB').save(os.path.join(res_dir, bg_name[:-4] + '_' + kind + '.png'), 'PNG')
+        if p.get('metrics', 0):
+            from sketchyscenecolorization_amd import metrics as M
+            summary = M.summarise(names, ['all'] * len(names), np.concatenate(rows, 0))
+            with open(os.path.join(res_dir, 'metrics.json'), 'w') as fp:
+                fp.write(M.dumps(summary))
+            print(M.all_line(summary))
         return
 
     log_dir = os.path.join(out_dir, 'log')
@@ -324,6 +342,8 @@ def main(argv=None):
         raise ValueError('--batch_size %d: at least one scene per step' % args.batch_size)
     if args.recolor and args.scene_cache != 'device':
         raise ValueError('--recolor 1 paints the cached scenes on the device: it needs --scene_cache device')
+    if args.metrics and args.mode != 'test':
+        raise ValueError('--metrics 1 scores the images of --mode test: training writes none')
     bg_colorization(**{name: getattr(args, name) for name, _t, _d, _c, _h in FLAGS})
 
 

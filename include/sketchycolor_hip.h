@@ -285,6 +285,24 @@ int ssc_bg_stage_cached_u8(const uint8_t* fg_cache, int64_t S_fg, const uint8_t*
  * the pixel of fg uint8 [M,3] is written instead (the paste-back of test mode, :861-871).  fg may be NULL without a mask. */
 int ssc_bg_finish_u8(const float* img, int ldc, const uint8_t* fg, const uint8_t* mask, int64_t M, uint8_t* out,
                      void* stream);
+/* --- full-reference image scores of the evaluation modes (metrics.hip) ---
+ * a, b uint8 [N,H,W,3] (the arrays --mode val / --mode test write as PNG), mask uint8 [N,H,W] or NULL: a pixel is counted when
+ * mask is NULL or its mask byte is not 0.  out double [N,5], per image:
+ *   0  sum |a-b| over the counted pixels and the 3 channels        1  sum (a-b)^2 over the same
+ *   2  the number of counted pixels
+ *   3  the SSIM sum over the counted windows and the 3 channels    4  the number of counted windows, per channel
+ * 0, 1, 2 and 4 are integers and exact.  SSIM (Wang et al. 2004) per channel on the byte values: 11x11 separable window,
+ * "valid" positions only ((H-10)*(W-10) windows; none, and no error, when H < 11 or W < 11), weights win11 double [11]
+ * (device; exp(-(i-5)^2 / (2*1.5^2)) normalised to sum 1, made once by the host in float64), mu = sum w*x, var = sum w*x^2 -
+ * mu^2 (biased), cov likewise, C1 = (0.01*255)^2, C2 = (0.03*255)^2, ssim = (2 mu_a mu_b + C1)(2 cov + C2) / ((mu_a^2 + mu_b^2
+ * + C1)(var_a + var_b + C2)).  With a mask a window is counted when its centre pixel is; it still reads all 121 pixels.
+ * The moments and the SSIM sum are formed in double: the variance is a difference of terms near 65025 set against C2 = 58.5.
+ * One workgroup per 24x32 tile writes its five partial sums to ws, a second launch adds an image's tiles in a fixed order: no
+ * floating-point atomics, the same bits from run to run.  ws: N * ceil(H/24) * ceil(W/32) * 5 doubles, 8-byte aligned.
+ * Returns -1 for sizes out of range, -2 for a workspace that is too small or misaligned, -3 for a misaligned win11 / out;
+ * nothing is launched and out is not written then. */
+int ssc_image_metrics_u8(const uint8_t* a, const uint8_t* b, const uint8_t* mask, int N, int H, int W, const double* win11,
+                         double* out, void* ws, int64_t ws_bytes, void* stream);
 /* PIL.Image.resize of an 8-bit image on the device (resize_and_padding_mask_image, input_pipeline.py:199-239: ANTIALIAS =
  * LANCZOS; reverse_resize_image, Pipeline_utils/fg_color_utils.py:137-160: scipy.misc.imresize = PIL bilinear): Pillow's
  * two-pass 8-bit resampler, horizontal then vertical, bit for bit.  src uint8 [H,W,C]; chan >= 0: only that channel,

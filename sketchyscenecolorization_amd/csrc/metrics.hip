@@ -1,0 +1,211 @@
+// metrics.hip -- full-reference scores of the evaluation modes: sum |a-b|, sum (a-b)^2 and the SSIM sum (Wang et al. 2004) of
+// two uint8 [N,H,W,3] batches, per image, optionally under a pixel mask (definitions: include/sketchycolor_hip.h).
+//
+// A workgroup owns a TH x TW tile of one image's pixels: their absolute and squared differences, and the windows whose CENTRE
+// lies in the tile.  It loads the tile with a 5-pixel halo of both images into LDS as bytes, de-interleaved into three planes,
+// then per channel runs the horizontal 11-tap pass of the five moments (a, b, a^2, b^2, ab) into LDS and the vertical pass into
+// registers, all in double.  Its five sums go to ws; a second launch adds the tiles of an image in a fixed order.  Integers are
+// carried as doubles (every one far below 2^53: exact in any order); the SSIM sum is ordered by construction, never by arrival.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "sketchycolor_hip.h"
+
+#define CHECK_LAUNCH() ((int)hipGetLastError())
+
+namespace {
+
+constexpr int TH = 24, TW = 32;             // the tile, in pixels (256 threads = 8 rows x 32 columns, TH / 8 rows each)
+constexpr int R = 5;                        // window radius
+constexpr int LR = TH + 2 * R;              // rows with the halo
+constexpr int LC = TW + 2 * R;              // columns with the halo
+constexpr int LCP = 48;                     // row pitch of a byte plane
+constexpr int LANES_PER_ROW = 8;            // lanes that load one row: one 16-byte piece each
+static_assert(LC <= LCP && (LC * 3 + 15) / 16 <= LANES_PER_ROW, "a row of the tile is at most LANES_PER_ROW 16-byte pieces");
+static_assert(TW == 32 && TH % 8 == 0, "thread (tid >> 5, tid & 31) owns rows tid >> 5 + 8 * i");
+static_assert((3 * LR * LCP) % 16 == 0, "the planes are cleared with 16-byte stores");
+
+typedef unsigned char plane_t[LR][LCP];
+
+// One row of the tile (nbytes interleaved bytes at g, the first of them byte p0 of the tile's row) into the three planes.
+// The 16-byte aligned middle goes one 16-byte load per lane, what lies in front of it and behind it byte by byte.
+__device__ __forceinline__ void load_row(const unsigned char* __restrict__ g, int nbytes, plane_t* s, int r, int p0, int lane) {
+    int head = (int)((16u - (unsigned)((uintptr_t)g & 15u)) & 15u);
+    if (head > nbytes) head = nbytes;
+    const int pieces = (nbytes - head) >> 4;
+    const int tail = head + (pieces << 4);
+    if (lane < pieces) {
+        const int o = head + (lane << 4);
+        const uint4 v = *reinterpret_cast<const uint4*>(g + o);
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int p = p0 + o + i;
+            s[p % 3][r][p / 3] = (unsigned char)((w[i >> 2] >> ((i & 3) * 8)) & 0xffu);
+        }
+    }
+    for (int i = lane; i < head; i += LANES_PER_ROW) {
+        const int p = p0 + i;
+        s[p % 3][r][p / 3] = g[i];
+    }
+    for (int i = tail + lane; i < nbytes; i += LANES_PER_ROW) {
+        const int p = p0 + i;
+        s[p % 3][r][p / 3] = g[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void image_metrics_u8_kernel(const unsigned char* __restrict__ a,
+                                                                const unsigned char* __restrict__ b,
+                                                                const unsigned char* __restrict__ mask, int H, int W,
+                                                                int tiles_x, int tiles_y, const double* __restrict__ win,
+                                                                double* __restrict__ partial) {
+    __shared__ __attribute__((aligned(16))) unsigned char sa[3][LR][LCP];
+    __shared__ __attribute__((aligned(16))) unsigned char sb[3][LR][LCP];
+    __shared__ double hb[5][LR][TW];        // the horizontal pass of one channel
+    __shared__ double sw[2 * R + 1];
+    __shared__ double red[4][5];
+    const int tid = threadIdx.x;
+    const unsigned blk = blockIdx.x;
+    const int tx_i = (int)(blk % (unsigned)tiles_x);
+    const int ty_i = (int)((blk / (unsigned)tiles_x) % (unsigned)tiles_y);
+    const long n = (long)(blk / ((unsigned)tiles_x * (unsigned)tiles_y));
+    const int y0 = ty_i * TH, x0 = tx_i * TW;
+
+    // what lies outside the image reads 0: only windows that are not counted reach it
+    for (int i = tid; i < 3 * LR * LCP / 16; i += 256) {
+        reinterpret_cast<uint4*>(&sa[0][0][0])[i] = make_uint4(0, 0, 0, 0);
+        reinterpret_cast<uint4*>(&sb[0][0][0])[i] = make_uint4(0, 0, 0, 0);
+    }
+    if (tid < 2 * R + 1) sw[tid] = win[tid];
+    __syncthreads();
+    {
+        const int gx0 = x0 - R < 0 ? 0 : x0 - R;
+        const int gx1 = x0 + TW + R > W ? W : x0 + TW + R;
+        const int nbytes = (gx1 - gx0) * 3;
+        const int p0 = (gx0 - (x0 - R)) * 3;
+        for (int r = tid / LANES_PER_ROW; r < LR; r += 256 / LANES_PER_ROW) {
+            const int gy = y0 - R + r;
+            if (gy < 0 || gy >= H) continue;
+            const long off = ((n * H + gy) * W + gx0) * 3;
+            load_row(a + off, nbytes, sa, r, p0, tid % LANES_PER_ROW);
+            load_row(b + off, nbytes, sb, r, p0, tid % LANES_PER_ROW);
+        }
+    }
+    __syncthreads();
+
+    const int tx = tid & 31, tr = tid >> 5;
+    unsigned sad = 0, sse = 0, cnt = 0, wcnt = 0;
+    bool window[TH / 8];
+#pragma unroll
+    for (int i = 0; i < TH / 8; ++i) {
+        const int ty = tr + 8 * i;
+        const int cy = y0 + ty, cx = x0 + tx;
+        bool counted = cy < H && cx < W;
+        if (counted && mask != nullptr) counted = mask[(n * H + cy) * W + cx] != 0;
+        if (counted) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int d = (int)sa[c][ty + R][tx + R] - (int)sb[c][ty + R][tx + R];
+                sad += (unsigned)(d < 0 ? -d : d);
+                sse += (unsigned)(d * d);
+            }
+            ++cnt;
+        }
+        window[i] = counted && cy >= R && cy < H - R && cx >= R && cx < W - R;
+        wcnt += window[i];
+    }
+
+    const double C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
+    double ssum = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        for (int it = tid; it < LR * TW; it += 256) {
+            const int r = it >> 5, x = it & 31;
+            double ma = 0.0, mb = 0.0, maa = 0.0, mbb = 0.0, mab = 0.0;
+#pragma unroll
+            for (int k = 0; k < 2 * R + 1; ++k) {
+                const int ia = sa[c][r][x + k], ib = sb[c][r][x + k];
+                const double w = sw[k];
+                ma += w * (double)ia;
+                mb += w * (double)ib;
+                maa += w * (double)(ia * ia);       // the products are integers: exact
+                mbb += w * (double)(ib * ib);
+                mab += w * (double)(ia * ib);
+            }
+            hb[0][r][x] = ma; hb[1][r][x] = mb; hb[2][r][x] = maa; hb[3][r][x] = mbb; hb[4][r][x] = mab;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < TH / 8; ++i) {
+            if (!window[i]) continue;
+            const int ty = tr + 8 * i;
+            double ma = 0.0, mb = 0.0, maa = 0.0, mbb = 0.0, mab = 0.0;
+#pragma unroll
+            for (int k = 0; k < 2 * R + 1; ++k) {
+                const double w = sw[k];
+                ma += w * hb[0][ty + k][tx];
+                mb += w * hb[1][ty + k][tx];
+                maa += w * hb[2][ty + k][tx];
+                mbb += w * hb[3][ty + k][tx];
+                mab += w * hb[4][ty + k][tx];
+            }
+            const double va = maa - ma * ma, vb = mbb - mb * mb, cov = mab - ma * mb;
+            ssum += ((2.0 * ma * mb + C1) * (2.0 * cov + C2)) / ((ma * ma + mb * mb + C1) * (va + vb + C2));
+        }
+        __syncthreads();
+    }
+
+    double v[5] = {(double)sad, (double)sse, (double)cnt, ssum, (double)wcnt};
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) red[tid >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (tid < 5) partial[(long)blk * 5 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// out[n][k] = the sum of image n's tile partials: thread t adds tiles t, t + 256, ... in turn, then the 256 threads are added
+// by the same tree every time.
+__global__ __launch_bounds__(256) void image_metrics_sum_kernel(const double* __restrict__ partial, int tiles,
+                                                                 double* __restrict__ out) {
+    __shared__ double red[4][5];
+    const int tid = threadIdx.x;
+    const double* p = partial + (long)blockIdx.x * tiles * 5;
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int t = tid; t < tiles; t += 256) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) v[k] += p[(long)t * 5 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) red[tid >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (tid < 5) out[(long)blockIdx.x * 5 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+}  // namespace
+
+extern "C" int ssc_image_metrics_u8(const uint8_t* a, const uint8_t* b, const uint8_t* mask, int N, int H, int W,
+                                    const double* win11, double* out, void* ws, int64_t ws_bytes, void* stream) {
+    if (N < 1 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return -1;
+    const int64_t tiles_y = (H + TH - 1) / TH, tiles_x = (W + TW - 1) / TW;
+    const int64_t tiles = tiles_x * tiles_y;
+    if (tiles > INT32_MAX || tiles * N > INT32_MAX) return -1;
+    if (a == nullptr || b == nullptr || win11 == nullptr || out == nullptr) return -1;
+    if (ws == nullptr || ((uintptr_t)ws & 7) || ws_bytes < tiles * N * 5 * (int64_t)sizeof(double)) return -2;
+    if (((uintptr_t)win11 & 7) || ((uintptr_t)out & 7)) return -3;
+    hipLaunchKernelGGL(image_metrics_u8_kernel, dim3((unsigned)(tiles * N)), dim3(256), 0, (hipStream_t)stream, a, b, mask, H, W,
+                       (int)tiles_x, (int)tiles_y, win11, (double*)ws);
+    const int rc = CHECK_LAUNCH();
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(image_metrics_sum_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
+                       (int)tiles, out);
+    return CHECK_LAUNCH();
+}

@@ -178,6 +178,7 @@ SIGNATURES = {
     'ssc_bg_stage_u8': [_P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P],
     'ssc_bg_stage_cached_u8': [_P, _L, _P, _L, _P, _L, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P],
     'ssc_bg_finish_u8': [_P, _I, _P, _P, _L, _P, _P],
+    'ssc_image_metrics_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_resample_u8': [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'ssc_decode_paired_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     'ssc_decode_minmax_u8': [_P, _I, _I, _I, _P, _P],
@@ -1121,6 +1122,40 @@ def bg_finish_u8(image, fg_u8=None, mask_u8=None, out=None):
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=image.device)
     assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, h, w, 3)
     check(lib().ssc_bg_finish_u8(ptr(image), ldc, ptr(fg_u8), ptr(mask_u8), n * h * w, ptr(out), stream_ptr()), 'bg_finish_u8')
+    return out
+
+
+METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 owns (csrc/metrics.hip)
+_ssim_win = {}
+
+
+def image_metrics_workspace_bytes(n, h, w):
+    """What ssc_image_metrics_u8 needs: five doubles per tile and image."""
+    th, tw = METRICS_TILE
+    return n * ((h + th - 1) // th) * ((w + tw - 1) // tw) * 5 * 8
+
+
+def image_metrics_u8(a_u8, b_u8, mask_u8=None, out=None):
+    """Two uint8 [N,H,W,3] batches (device), mask_u8 uint8 [N,H,W] or None (a pixel counts where its mask byte is not 0) ->
+    float64 [N,5] on the device, per image: sum |a-b|, sum (a-b)^2, counted pixels, the SSIM sum over the counted 11x11 windows
+    and the 3 channels, counted windows per channel (metrics.scores turns a row into MAE, PSNR and SSIM).  The same bits from
+    run to run; the window weights (metrics.ssim_window, float64) are uploaded once per device."""
+    n, h, w, c = a_u8.shape
+    assert c == 3 and a_u8.dtype == torch.uint8 and b_u8.dtype == torch.uint8 and a_u8.is_cuda and b_u8.device == a_u8.device
+    assert tuple(b_u8.shape) == tuple(a_u8.shape) and a_u8.is_contiguous() and b_u8.is_contiguous()
+    if mask_u8 is not None:
+        assert mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (n, h, w) and mask_u8.is_contiguous()
+        assert mask_u8.device == a_u8.device
+    if out is None:
+        out = torch.empty((n, 5), dtype=torch.float64, device=a_u8.device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (n, 5) and out.is_contiguous() and out.device == a_u8.device
+    win = _ssim_win.get(a_u8.device)
+    if win is None:
+        from .metrics import ssim_window
+        win = _ssim_win[a_u8.device] = torch.from_numpy(ssim_window()).to(a_u8.device)
+    ws = workspace(max(image_metrics_workspace_bytes(n, h, w), 256 << 20))
+    check(lib().ssc_image_metrics_u8(ptr(a_u8), ptr(b_u8), ptr(mask_u8), n, h, w, ptr(win), ptr(out), ptr(ws), ws.numel() * 4,
+                                     stream_ptr()), 'image_metrics_u8')
     return out
 
 

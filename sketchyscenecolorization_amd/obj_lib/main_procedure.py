@@ -437,7 +437,10 @@ def test():
 def validation(**kwargs):
     """The reference validates from the data/tfrecord/val queue (main_procedure.py:245-358): here the
     restored generator runs over data/tfrecord/val when that directory exists, otherwise over one seeded synthetic
-    batch, and writes validation_results/with_text/<category>_<name>_{output,target,input}.png."""
+    batch, and writes validation_results/with_text/<category>_<name>_{output,target,input}.png.
+
+    --metrics 1 scores every _output against its _target on the device (hip.image_metrics_u8 on the very uint8 arrays that are
+    written as PNG) and writes metrics.json beside them: the images by stem, grouped by category."""
     small = Config.small_img != 0
     img = SIZE[small][0]
     from ..synthetic import synthetic_batch
@@ -446,17 +449,36 @@ def validation(**kwargs):
     restore_checkpoint(store, latest_checkpoint(Config.ckpt_dir))
     out_dir = os.path.join(Config.results_dir, 'with_text' if Config.LSTM_hybrid != 0 else 'without_text')
     os.makedirs(out_dir, exist_ok=True)
+    metrics = getattr(Config, 'metrics', 0) != 0
+    scored = {'names': [], 'groups': [], 'rows': []}
 
-    def run(images_, sketches_, class_id_, text_, stems):
+    def run(images_, sketches_, class_id_, text_, stems, cats):
         gen, images, sketches = build_single_graph(images_, sketches_, None, class_id_, None, text_,
                                                    batch_size=Config.batch_size, training=False,
                                                    LSTM_hybrid=Config.LSTM_hybrid != 0, vocab_size=Config.vocab_size,
                                                    data_format=Config.data_format, distance_map=False,
                                                    block_type=Config.block_type)
+        out_u8, target_u8, input_u8 = _postprocess(gen), _postprocess(images), _postprocess(sketches)
         for i, stem in enumerate(stems):
-            _write_png(os.path.join(out_dir, stem + '_output.png'), _postprocess(gen)[i])
-            _write_png(os.path.join(out_dir, stem + '_target.png'), _postprocess(images)[i])
-            _write_png(os.path.join(out_dir, stem + '_input.png'), _postprocess(sketches)[i])
+            _write_png(os.path.join(out_dir, stem + '_output.png'), out_u8[i])
+            _write_png(os.path.join(out_dir, stem + '_target.png'), target_u8[i])
+            _write_png(os.path.join(out_dir, stem + '_input.png'), input_u8[i])
+        if metrics:
+            from .. import hip
+            k = len(stems)
+            dev = lambda u8: torch.from_numpy(np.ascontiguousarray(u8[:k])).cuda()      # noqa: E731
+            scored['rows'].append(hip.image_metrics_u8(dev(out_u8), dev(target_u8)).cpu().numpy())
+            scored['names'] += list(stems)
+            scored['groups'] += list(cats)
+
+    def finish():
+        if not metrics:
+            return
+        from .. import metrics as M
+        summary = M.summarise(scored['names'], scored['groups'], np.concatenate(scored['rows'], 0))
+        with open(os.path.join(out_dir, 'metrics.json'), 'w') as fp:
+            fp.write(M.dumps(summary))
+        print(M.all_line(summary))
 
     if os.path.isdir(os.path.join('data', 'tfrecord', 'val')):      # the reference's validation set (:262-272)
         from .input_pipeline import build_input_queue_paired_test
@@ -468,9 +490,10 @@ def validation(**kwargs):
                 break
             dev = lambda a: a if torch.is_tensor(a) else torch.from_numpy(a).cuda()
             run(dev(images), dev(sketches), dev(cls), text,
-                ['%s_%s' % (c, n[:-4] if n.endswith('.png') else n) for c, n in zip(cats, names)])
-        return
+                ['%s_%s' % (c, n[:-4] if n.endswith('.png') else n) for c, n in zip(cats, names)], cats)
+        return finish()
     b = synthetic_batch(Config.batch_size, 4321, img, Config.vocab_size)
     cls = b['class_id'].cpu().numpy()
-    run(b['images'], b['sketches'], b['class_id'], b['text'],
-        ['%s_%04d' % (CATEGORIES[int(cls[i])], i) for i in range(Config.batch_size)])
+    cats = [CATEGORIES[int(cls[i])] for i in range(Config.batch_size)]
+    run(b['images'], b['sketches'], b['class_id'], b['text'], ['%s_%04d' % (cats[i], i) for i in range(Config.batch_size)], cats)
+    finish()
