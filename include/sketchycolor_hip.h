@@ -246,6 +246,13 @@ int ssc_conv_wgrad_kernel_name(const ssc_wgrad_desc* d, char* buf, int len);
 /* the launch plan for a descriptor (host only; tuning and tests): out5 = {tile configuration, split-K slabs, whole
  * tiles, K slices per remaining tile (combined inside the launch), modelled kilo-cycles} */
 int ssc_conv_forward_plan(const ssc_conv_desc* d, int64_t ws_bytes, int* out5);
+/* the launch plan of a filter gradient that reaches the general kernel (conv_wgrad_kernel of igemm.hip; host only, launches
+ * nothing): out4 = {tile configuration (0 128x128, 1 64x128, 2 128x64, 3 64x64, 4 128x32; -1: the patch head, the 128 x 128 or
+ * the 16-column kernel takes the launch), split-K slabs, view form (gathered side plain, dense side plain, dense tile by LDS-DMA:
+ * 0 TTT, 1 FTT, 2 TTF, 3 FTF, 4 FFF), the kernel that sums the slabs (0 none, 1 reduce4, 2 reduce<1>, 3 reduce<4>, 4 reduce<16>)}.
+ * ws_bytes <= 0 stands for a NULL workspace; any other workspace is taken to be 16-byte aligned.  Computed by the functions
+ * that make the launch. */
+int ssc_conv_wgrad_plan(const ssc_wgrad_desc* d, int64_t ws_bytes, int* out4);
 
 /* --- layout (elementwise.hip) --- */
 /* dst[n,hw,coff+c] = src[n,c,hw]; tf.transpose NCHW->NHWC (models_collection.py:381) */

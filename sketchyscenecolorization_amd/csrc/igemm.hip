@@ -30,6 +30,7 @@ int ssc_conv_wgrad128_bf_selected(const ssc_wgrad_desc* dp);
 // wgn16.hip
 extern "C" int ssc_conv_wgn16_supported(const ssc_wgrad_desc* dp);
 int ssc_conv_wgn16(const ssc_wgrad_desc* dp, float* ws, int64_t ws_bytes, void* stream);
+int ssc_conv_wgn16_fits(const ssc_wgrad_desc* dp, int64_t ws_bytes);
 // narrow.hip
 int ssc_conv_narrow_forward_ws(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, void* stream, int* csplit_out);
 // fewchan.hip
@@ -1300,6 +1301,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const float4* __rest
     out[i] = v;
 }
 
+// which kernel sums the slabs: 1 wgrad_reduce4_kernel, 2 wgrad_reduce_kernel<1>, 3 <4>, 4 <16>
+static int wgrad_reduce_form(const float* ws, long count, int splitk, const float* out) {
+    if (count >= 262144 || splitk < 8)
+        return ((count % 4) == 0 && (((uintptr_t)ws | (uintptr_t)out) & 15) == 0) ? 1 : 2;
+    return (count >= 65536 || splitk < 32) ? 3 : 4;
+}
+
 static void launch_wgrad_reduce(const float* ws, long count, int splitk, float* out, int accumulate, hipStream_t st) {
     static int skip = -1;       // SSC_DIAG_SKIP_WGRAD_REDUCE=1: timing diagnostic only (wrong gradients): what do the slab sums cost
     if (skip < 0) {
@@ -1307,19 +1315,25 @@ static void launch_wgrad_reduce(const float* ws, long count, int splitk, float* 
         skip = (e != nullptr && e[0] == '1') ? 1 : 0;
     }
     if (skip) return;
-    if ((count >= 262144 || splitk < 8) && (count % 4) == 0 && (((uintptr_t)ws | (uintptr_t)out) & 15) == 0) {
-        const long c4 = count / 4;
-        hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)((c4 + 255) / 256)), dim3(256), 0, st, (const float4*)ws, c4,
-                           splitk, (float4*)out, c4, accumulate);
-    } else if (count >= 262144 || splitk < 8) {
-        hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, count,
-                           splitk, out, count, accumulate);
-    } else if (count >= 65536 || splitk < 32) {
-        hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, st, ws, count, splitk,
-                           out, count, accumulate);
-    } else {
-        hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)((count + 15) / 16)), dim3(256), 0, st, ws, count, splitk,
-                           out, count, accumulate);
+    switch (wgrad_reduce_form(ws, count, splitk, out)) {
+        case 1: {
+            const long c4 = count / 4;
+            hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)((c4 + 255) / 256)), dim3(256), 0, st, (const float4*)ws, c4,
+                               splitk, (float4*)out, c4, accumulate);
+            break;
+        }
+        case 2:
+            hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, count,
+                               splitk, out, count, accumulate);
+            break;
+        case 3:
+            hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, st, ws, count, splitk,
+                               out, count, accumulate);
+            break;
+        default:
+            hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)((count + 15) / 16)), dim3(256), 0, st, ws, count, splitk,
+                               out, count, accumulate);
+            break;
     }
 }
 
@@ -2104,8 +2118,8 @@ static int launch_wgrad_v(const ssc_wgrad_desc& d, int splitk, float* ws, hipStr
     return (int)hipGetLastError();
 }
 
-template <int WM, int WN, int SM, int SN>
-static int launch_wgrad(const ssc_wgrad_desc& d, int splitk, float* ws, hipStream_t st) {
+// the view form (GPLAIN, DPLAIN, DDMA) of a launch: 0 TTT, 1 FTT, 2 TTF, 3 FTF, 4 FFF
+static int wgrad_view_form(const ssc_wgrad_desc& d) {
     const bool gp = gview_plain(d.g), dp = gview_plain(d.d);
     static int ddma_on = -1;       // SSC_WGRAD_DMA=0: dense tiles through registers (A/B)
     if (ddma_on < 0) {
@@ -2114,11 +2128,20 @@ static int launch_wgrad(const ssc_wgrad_desc& d, int splitk, float* ws, hipStrea
     }
     // LDS-DMA of the dense tile: one plain tensor whose byte offsets fit 32 bits
     const bool ddma = SSC_BDMA && ddma_on && dp && d.d.C1 == 0 && (long)d.NB * d.PH * d.PW * d.d.C0 < 0x1fffffffL;
-    if (dp && ddma) return gp ? launch_wgrad_v<WM, WN, SM, SN, true, true, true>(d, splitk, ws, st)
-                              : launch_wgrad_v<WM, WN, SM, SN, false, true, true>(d, splitk, ws, st);
-    if (dp) return gp ? launch_wgrad_v<WM, WN, SM, SN, true, true, false>(d, splitk, ws, st)
-                      : launch_wgrad_v<WM, WN, SM, SN, false, true, false>(d, splitk, ws, st);
-    return launch_wgrad_v<WM, WN, SM, SN, false, false, false>(d, splitk, ws, st);   // the full transform covers a plain side
+    if (dp && ddma) return gp ? 0 : 1;
+    if (dp) return gp ? 2 : 3;
+    return 4;       // the full transform covers a plain side
+}
+
+template <int WM, int WN, int SM, int SN>
+static int launch_wgrad(const ssc_wgrad_desc& d, int splitk, float* ws, hipStream_t st) {
+    switch (wgrad_view_form(d)) {
+        case 0: return launch_wgrad_v<WM, WN, SM, SN, true, true, true>(d, splitk, ws, st);
+        case 1: return launch_wgrad_v<WM, WN, SM, SN, false, true, true>(d, splitk, ws, st);
+        case 2: return launch_wgrad_v<WM, WN, SM, SN, true, true, false>(d, splitk, ws, st);
+        case 3: return launch_wgrad_v<WM, WN, SM, SN, false, true, false>(d, splitk, ws, st);
+        default: return launch_wgrad_v<WM, WN, SM, SN, false, false, false>(d, splitk, ws, st);
+    }
 }
 
 // split over the pixel (K) dimension: many more choices than the forward form, so search a wider range
@@ -2183,6 +2206,31 @@ extern "C" int ssc_conv_wgrad_kernel_name(const ssc_wgrad_desc* dp, char* buf, i
     return 0;
 }
 
+// which kernel takes a filter-gradient launch: 0 conv_wgrad_kernel, 1 head1, 2 wgrad128, 3 wgn16
+static int wgrad_route(const ssc_wgrad_desc* dp, bool have_ws, int64_t ws_bytes) {
+    if (have_ws && ws_bytes >= (int64_t)16 * 512 * 4 && ssc_head1_wgrad_supported(dp)) return 1;     // the one-output patch head
+    if (ssc_conv_wgrad128_supported(dp)) return 2;                                                  // the large layers
+    // 16 output channels, 3x3 x 16 or 4x4 x 64 gathered: 16-column MFMA, when the workspace can hold a slab
+    if (have_ws && ssc_conv_wgn16_supported(dp) && ssc_conv_wgn16_fits(dp, ws_bytes)) return 3;
+    return 0;
+}
+
+extern "C" int ssc_conv_wgrad_plan(const ssc_wgrad_desc* dp, int64_t ws_bytes, int* out4) {
+    // host only: {tile configuration, split-K slabs, view form, reduce form}; ws_bytes <= 0 stands for a NULL workspace, any
+    // other workspace is taken to be 16-byte aligned
+    const ssc_wgrad_desc& d = *dp;
+    const bool have_ws = ws_bytes > 0;
+    out4[0] = -1; out4[1] = 1; out4[2] = 0; out4[3] = 0;
+    if (wgrad_route(dp, have_ws, ws_bytes) != 0) return 0;
+    const Plan p = plan_wgrad(d, ws_bytes, have_ws);
+    out4[0] = p.cfg;
+    out4[1] = p.splitk;
+    out4[2] = wgrad_view_form(d);
+    if (p.splitk > 1)
+        out4[3] = wgrad_reduce_form(nullptr, (long)d.TH * d.TW * d.Cg_real * d.ldc, p.splitk, d.out);
+    return 0;
+}
+
 extern "C" int ssc_conv_wgrad(const ssc_wgrad_desc* dp, float* ws, int64_t ws_bytes, void* stream) {
     const ssc_wgrad_desc& d = *dp;
     hipStream_t st = (hipStream_t)stream;
@@ -2191,12 +2239,11 @@ extern "C" int ssc_conv_wgrad(const ssc_wgrad_desc* dp, float* ws, int64_t ws_by
     // the filter-gradient slab is dense [TH*TW*Cg_real][ldc]; rows/cols skipped by the kernel
     // (padding channels) do not exist in it, so every slab entry is written when ldc == Nn.
     if (d.ldc != d.Nn) return -3;
-    if (ws != nullptr && ws_bytes >= (int64_t)16 * 512 * 4 && ssc_head1_wgrad_supported(dp))     // the one-output patch head
-        return ssc_head1_wgrad(dp, ws, ws_bytes, stream);
-    if (ssc_conv_wgrad128_supported(dp)) return ssc_conv_wgrad128(dp, ws, ws_bytes, stream);     // the large layers
-    if (ws != nullptr && ssc_conv_wgn16_supported(dp)) {      // 16 output channels, 3x3 x 16 or 4x4 x 64 gathered: 16-column MFMA
-        const int rc = ssc_conv_wgn16(dp, ws, ws_bytes, stream);
-        if (rc != -2) return rc;        // -2: the workspace cannot hold a slab
+    switch (wgrad_route(dp, ws != nullptr, ws_bytes)) {
+        case 1: return ssc_head1_wgrad(dp, ws, ws_bytes, stream);
+        case 2: return ssc_conv_wgrad128(dp, ws, ws_bytes, stream);
+        case 3: return ssc_conv_wgn16(dp, ws, ws_bytes, stream);
+        default: break;
     }
     const Plan p = plan_wgrad(d, ws_bytes, ws != nullptr);
     switch (p.cfg) {

@@ -254,6 +254,25 @@ static int wg16_form(const ssc_wgrad_desc& d) {
 
 extern "C" int ssc_conv_wgn16_supported(const ssc_wgrad_desc* dp) { return wg16_form(*dp) != 0 ? 1 : 0; }
 
+// workgroups of a launch (each writes per_wg slabs of rows x 16 floats): as many as the workspace holds, 0 when it cannot hold one
+static long wg16_groups(const ssc_wgrad_desc& d, int form, int64_t ws_bytes) {
+    const int tc = form == 3 ? 32 : 16;
+    const int tiles_x = (d.PW + tc - 1) / tc, tiles_y = (d.PH + 3) / 4;
+    const long tiles = (long)d.NB * tiles_y * tiles_x;
+    const int rows = form == 3 ? 144 : 1024;
+    const int per_wg = form == 3 ? 4 : 1;               // slabs per workgroup
+    long G = (long)ssc_num_cu() * 3;
+    if (G > tiles) G = tiles;
+    while (G > 1 && (int64_t)G * per_wg * rows * 16 * 4 > ws_bytes) G /= 2;
+    return (int64_t)G * per_wg * rows * 16 * 4 > ws_bytes ? 0 : G;
+}
+
+// host only: the workspace can hold a slab of this launch (ssc_conv_wgrad takes the general kernel otherwise)
+int ssc_conv_wgn16_fits(const ssc_wgrad_desc* dp, int64_t ws_bytes) {
+    const int form = wg16_form(*dp);
+    return form != 0 && wg16_groups(*dp, form, ws_bytes) > 0 ? 1 : 0;
+}
+
 int ssc_conv_wgn16(const ssc_wgrad_desc* dp, float* ws, int64_t ws_bytes, void* stream) {
     const ssc_wgrad_desc& d = *dp;
     const int form = wg16_form(d);
@@ -264,10 +283,8 @@ int ssc_conv_wgn16(const ssc_wgrad_desc* dp, float* ws, int64_t ws_bytes, void* 
     const long tiles = (long)d.NB * tiles_y * tiles_x;
     const int rows = form == 3 ? 144 : 1024;
     const int per_wg = form == 3 ? 4 : 1;               // slabs per workgroup
-    long G = (long)ssc_num_cu() * 3;
-    if (G > tiles) G = tiles;
-    while (G > 1 && (int64_t)G * per_wg * rows * 16 * 4 > ws_bytes) G /= 2;
-    if ((int64_t)G * per_wg * rows * 16 * 4 > ws_bytes) return -2;
+    const long G = wg16_groups(d, form, ws_bytes);
+    if (G == 0) return -2;
     if (form == 3)
         hipLaunchKernelGGL(wgn16_k3_kernel, dim3((unsigned)G), dim3(256), 0, st, d, (int)tiles, tiles_x, tiles_y, ws);
     else

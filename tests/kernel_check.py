@@ -4,8 +4,10 @@ device outputs, the raw return code of an entry point, and the two comparison ru
   check      |device - float64 oracle| <= tol * max(1, max|oracle|)            (the close() convention of test_gpu_igemm.py)
   check_fp32 per element max(that floor, 4 x |float32 oracle - float64 oracle|): for formulas that lose digits in float32 by
              construction, the same way in the reference (the factor 4 allows for expf / logf / tanhf a few ulp off libm)
+  check_dot  per element |device - float64 oracle| <= (K + 8) * 2^-24 * S for sums of K fp32 products, S the float64 sum of the
+             absolute products: the any-order dot-product bound, nothing measured in it (tests/test_gpu_wgrad_forms.py)
 
-Both print the measured distance before they assert and log it with conftest.parity_log (variant='kernel', never forward=True:
+All print the measured distance before they assert and log it with conftest.parity_log (variant='kernel', never forward=True:
 these are not network outputs)."""
 import torch
 
@@ -91,3 +93,30 @@ def check_fp32(test, config, got, ref64, ref32, tol=1e-5, what=''):
     print('%s %s %s: err %.3e (bound there %.3e, max err %.3e), fp32 oracle vs f64 %.3e' % (test, what, config, e, b, float(err.max()), c))
     parity_log(test, dict(config, what=what), e, b, variant='kernel', cpu_fp32_vs_f64=c, max_err_anywhere=float(err.max()))
     assert bool((err <= bound).all()), (test, what, config, e, b)
+
+
+U_FP32 = 2.0 ** -24        # unit roundoff of fp32
+
+
+def check_dot(test, config, got, ref64, S, K, plan=None, what=''):
+    """An fp32 sum of K products, added up in any order: per element |got - ref64| <= (K + 8) * 2^-24 * S, where S is the float64
+    sum of the absolute products of that element.  gamma_K = K*u / (1 - K*u) bounds the rounding of the products and of the K - 1
+    additions in whatever order (Higham, Accuracy and Stability of Numerical Algorithms, section 3.1); the 8 more roundings per
+    term allow for the folded norm (one fma), the activation's slope product and the float32 slope constant on either factor, and
+    the additions of split-K slabs and of an accumulate base, which the caller counts as one more term of S.  (K + 8) * u stands
+    for gamma_(K+8): the quotient 1 - (K+8)*u is within 1e-3 of 1 for every K the tests use, K <= 8192.)
+    plan: what ssc_conv_wgrad_plan reported for the launch, logged with the worst err / bound ratio."""
+    got, ref64, S = _f64(got), _f64(ref64), _f64(S)
+    assert got.shape == ref64.shape == S.shape, (test, what, got.shape, ref64.shape, S.shape)
+    assert K + 8 <= 16384, K
+    assert bool(torch.isfinite(got).all()), (test, what, config, 'non-finite output')
+    bound = (K + 8) * U_FP32 * S
+    err = (got - ref64).abs()
+    ratio = torch.where(err > 0, err / torch.clamp(bound, min=1e-300), torch.zeros_like(err))
+    k = int(torch.argmax(ratio))
+    r, e, b = float(ratio.reshape(-1)[k]), float(err.reshape(-1)[k]), float(bound.reshape(-1)[k])
+    print('%s %s %s plan %s: worst err/bound %.3e (err %.3e, bound there %.3e), max err %.3e' %
+          (test, what, config, plan, r, e, b, float(err.max())))
+    parity_log(test, dict(config, what=what), e, b, variant='kernel', ratio=r, K=int(K), plan=list(plan) if plan is not None else None)
+    assert bool((err <= bound).all()), (test, what, config, 'err/bound', r, 'at', k)
+    return r

@@ -1,0 +1,69 @@
+"""The float64 reference of the filter-gradient tests (tests/wgrad_oracle.py) against itself, and the comparison rule
+(kernel_check.check_dot) against results that miss one term.  No GPU."""
+import pytest
+import torch
+
+import wgrad_oracle as O
+from kernel_check import check_dot
+
+
+@pytest.mark.parametrize('name', [c['name'] for c in O.CASES])
+def test_autograd_reference_equals_tap_loop_reference(name):
+    """(a) autograd through oracle/tf_ops.py == (b) shifted slices + einsum, to 1e-12 of the largest value."""
+    c = O.BY_NAME[name]
+    inp = O.make_inputs(c)
+    a = O.ref_autograd(c, inp)
+    b, S = O.ref_taps(c, inp)
+    assert a.shape == b.shape == S.shape and a.dtype == b.dtype == torch.float64
+    scale = float(b.abs().max())
+    assert scale > 0 and bool((S >= b.abs() * (1 - 1e-12)).all())
+    assert float((a - b).abs().max()) <= 1e-12 * scale, (float((a - b).abs().max()), scale)
+
+
+def test_padding_lanes_hold_1e3_and_do_not_reach_the_reference():
+    c = O.BY_NAME['t4_nn3_dy4_deconv']
+    inp = O.make_inputs(c)
+    assert float(inp['g0'][..., 3].min()) == O.PAD_LANE and float(inp['d0'][..., 3].min()) == O.PAD_LANE
+    assert float(O.ref_taps(c, inp)[1].max()) < 1e3
+
+
+def _border_tap(c):
+    """A pixel and a tap that lies inside the gathered image while another tap of the same pixel lies outside."""
+    geo = O.geometry(c)
+    for py in (0, geo['PH'] - 1):       # SAME over an even size pads after only: the border is the bottom row
+        pixel = (geo['NB'] - 1, py, geo['PW'] // 2)
+        inside = [(ty, tx) for ty in range(geo['TH']) for tx in range(geo['TW'])
+                  if 0 <= py * geo['stride'] + geo['oy'] + ty < geo['GH']]
+        if 0 < len(inside) < geo['TH'] * geo['TW']:
+            break
+    else:
+        raise AssertionError('no pixel at a border')
+    return pixel, inside[0]
+
+
+@pytest.mark.parametrize('name', ['t4_first_layer_4x4s2', 't2_3x3same_s2_even', 't0_3x3_two_gathered'])
+def test_rule_rejects_a_result_that_misses_one_term(name):
+    """check_dot accepts what a CPU computes in float32 and rejects the float64 reference with the last pixel removed, with one
+    border tap of one pixel removed, and with one padding-lane value (1.0e3) taken into channel 0."""
+    c = O.BY_NAME[name]
+    inp = O.make_inputs(c)
+    geo = O.geometry(c)
+    K = O.pixels(c)
+    ref, S = O.ref_taps(c, inp)
+    cfg = dict(case=name)
+    check_dot('wgrad_rule', cfg, O.ref_taps(c, inp, torch.float32)[0], ref, S, K, what='float32 CPU')
+    last = (geo['NB'] - 1, geo['PH'] - 1, geo['PW'] - 1)
+    no_last = ref.clone()
+    for ty in range(geo['TH']):
+        for tx in range(geo['TW']):
+            no_last[ty, tx] -= O.term(c, inp, last, (ty, tx))
+    pixel, tap = _border_tap(c)
+    no_tap = ref.clone()
+    no_tap[tap] -= O.term(c, inp, pixel, tap)
+    assert float((no_tap - ref).abs().max()) > 0
+    leaked = ref.clone()
+    D = O.transformed(c, inp, 'd')[..., :c['d'][2]]
+    leaked[tap[0], tap[1], 0] += O.PAD_LANE * D[pixel]
+    for what, damaged in (('last pixel removed', no_last), ('border tap removed', no_tap), ('padding lane leaked', leaked)):
+        with pytest.raises(AssertionError):
+            check_dot('wgrad_rule', cfg, damaged.float(), ref, S, K, what=what)
