@@ -310,6 +310,20 @@ int ssc_bg_finish_u8(const float* img, int ldc, const uint8_t* fg, const uint8_t
  * nothing is launched and out is not written then. */
 int ssc_image_metrics_u8(const uint8_t* a, const uint8_t* b, const uint8_t* mask, int N, int H, int W, const double* win11,
                          double* out, void* ws, int64_t ws_bytes, void* stream);
+/* The same five sums for two FLOAT images whose uint8 forms are never written: scoring a held-out set during training, in place
+ * of the checkpoint scoring the reference meant to have (graph_single.py:557-559: its Inception call, commented out).
+ * a float NHWC, rows of lda floats, the image in channels [coff_a, coff_a + 3) (the generator's output buffer: lda 4 or 8);
+ * b the same form (ldb, coff_b) or, with b_planar != 0, planar NCHW [N,3,H,W] (what ssc_decode_paired_cached_u8 writes; ldb and
+ * coff_b are then not read).  No mask.  Every value is quantised while the tile is loaded, with the arithmetic of
+ * ssc_image_postprocess_u8: (x+1)/2*255, each operation rounded to fp32, fmaxf(v, 0) then fminf(.., 255) (NaN becomes 0),
+ * truncating cast; from there on it is ssc_image_metrics_u8's code.  out is therefore bit-identical to ssc_image_metrics_u8 of
+ * the two postprocessed images, and the same bits from run to run.  16-byte loads where the layout allows (NHWC with ld 4 or 8
+ * on a 16-byte aligned base; four consecutive pixels of a plane), single floats elsewhere; padding channels are never part of
+ * a result and nothing outside [N,H,W] is read.  ws as for ssc_image_metrics_u8.
+ * Returns -1 for sizes out of range (N < 1, coff + 3 > ld, ...), -2 for a workspace that is too small or misaligned, -3 for a
+ * misaligned pointer (a, b: 4 bytes; win11, out: 8); nothing is launched and out is not written then. */
+int ssc_image_metrics_f32(const float* a, int lda, int coff_a, const float* b, int ldb, int coff_b, int b_planar, int N, int H,
+                          int W, const double* win11, double* out, void* ws, int64_t ws_bytes, void* stream);
 /* PIL.Image.resize of an 8-bit image on the device (resize_and_padding_mask_image, input_pipeline.py:199-239: ANTIALIAS =
  * LANCZOS; reverse_resize_image, Pipeline_utils/fg_color_utils.py:137-160: scipy.misc.imresize = PIL bilinear): Pillow's
  * two-pass 8-bit resampler, horizontal then vertical, bit for bit.  src uint8 [H,W,C]; chan >= 0: only that channel,

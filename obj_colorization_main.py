@@ -10,6 +10,7 @@ inference_results}``, ``log/param_<first iteration>.json`` and the restart-after
     python obj_colorization_main.py --mode train -bt Pix2Pix -bs 32 -rc device   # data/tfrecord/train cached on the GPU
     python -m torch.distributed.run --nproc-per-node 8 obj_colorization_main.py --mode train -bt Pix2Pix -gpu 8   # same
     python obj_colorization_main.py --mode val -rf <timestamp> -bt Pix2Pix -mt 1   # validation PNGs and their metrics.json
+    python obj_colorization_main.py --mode train -bt Pix2Pix -bs 32 -rc device -vf 1000   # data/tfrecord/val scored every 1000
     python obj_colorization_main.py --mode inference -rf <timestamp> --infer_name car.png \
         --instruction 'the car is yellow with blue window'
 """
@@ -51,6 +52,10 @@ FLAGS = [
      'device = train from data/tfrecord/train held on the GPU as uint8 (0.88 MB per record, 2.2 MB with --distance_map 1)'),
     ('metrics', 'mt', int, 0, [0, 1], 'metrics',
      '1 (--mode val): score every output against its target on the GPU (MAE, PSNR, SSIM) and write metrics.json beside the PNGs'),
+    ('val_freq', 'vf', int, 0, None, 'val_freq',
+     'iterations between held-out passes during training: data/tfrecord/val scored on the GPU (MAE, PSNR, SSIM), one line per '
+     'pass in log/validation.jsonl; 0 = never'),
+    ('val_records', 'vn', int, 0, None, 'val_records', 'held-out records a pass takes, the first N in file order; 0 = all'),
 ]
 RESULT_DIRS = {'val': 'validation_results', 'test': 'test_results', 'inference': 'inference_results'}
 

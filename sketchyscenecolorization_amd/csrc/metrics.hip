@@ -6,6 +6,10 @@
 // then per channel runs the horizontal 11-tap pass of the five moments (a, b, a^2, b^2, ab) into LDS and the vertical pass into
 // registers, all in double.  Its five sums go to ws; a second launch adds the tiles of an image in a fixed order.  Integers are
 // carried as doubles (every one far below 2^53: exact in any order); the SSIM sum is ordered by construction, never by arrival.
+//
+// Two loaders fill the byte planes, one body reads them.  U8Loader takes the uint8 images of the evaluation modes; F32Loader takes
+// float images (the generator's NHWC output buffer, the decode kernel's planar target) and quantises every value on its way into
+// the planes with the arithmetic of image_postprocess_u8_kernel (elementwise.hip), so that the uint8 forms never exist in memory.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sketchycolor_hip.h"
@@ -53,11 +57,119 @@ __device__ __forceinline__ void load_row(const unsigned char* __restrict__ g, in
     }
 }
 
-__global__ __launch_bounds__(256) void image_metrics_u8_kernel(const unsigned char* __restrict__ a,
-                                                                const unsigned char* __restrict__ b,
-                                                                const unsigned char* __restrict__ mask, int H, int W,
-                                                                int tiles_x, int tiles_y, const double* __restrict__ win,
-                                                                double* __restrict__ partial) {
+struct U8Loader {
+    const unsigned char* a;
+    const unsigned char* b;
+    // the tile at (y0, x0) of image n with its halo, clipped to the image, into the planes (cleared by the caller)
+    __device__ __forceinline__ void operator()(plane_t* sa, plane_t* sb, long n, int y0, int x0, int H, int W, int tid) const {
+        const int gx0 = x0 - R < 0 ? 0 : x0 - R;
+        const int gx1 = x0 + TW + R > W ? W : x0 + TW + R;
+        const int nbytes = (gx1 - gx0) * 3;
+        const int p0 = (gx0 - (x0 - R)) * 3;
+        for (int r = tid / LANES_PER_ROW; r < LR; r += 256 / LANES_PER_ROW) {
+            const int gy = y0 - R + r;
+            if (gy < 0 || gy >= H) continue;
+            const long off = ((n * H + gy) * W + gx0) * 3;
+            load_row(a + off, nbytes, sa, r, p0, tid % LANES_PER_ROW);
+            load_row(b + off, nbytes, sb, r, p0, tid % LANES_PER_ROW);
+        }
+    }
+};
+
+// image_postprocess_u8_kernel's value (elementwise.hip): (x + 1) / 2 * 255, each operation rounded to fp32, NaN and what lies
+// below 0 to 0, what lies above 255 to 255, then the truncating cast
+__device__ __forceinline__ unsigned char quantise(float x) {
+    float v = (x + 1.f) / 2.f * 255.f;
+    v = fminf(fmaxf(v, 0.f), 255.f);
+    return (unsigned char)(int)v;
+}
+
+constexpr int F32_ROW_LANES = 16;           // lanes per row of a plane: <= 10 float4 pieces + <= 3 floats in front + <= 3 behind
+static_assert((LC + 3) / 4 - 1 + 3 + 3 <= F32_ROW_LANES, "a plane's row is loaded in one pass");
+
+struct F32Loader {
+    const float* a;
+    int lda, coff_a;
+    const float* b;
+    int ldb, coff_b;        // (not read when b is planar)
+    int b_planar;
+
+    // NHWC rows of ld floats, the image in channels [coff, coff + 3).  ld 4 or 8 on a 16-byte aligned base: the pixel's one
+    // or two float4 (which hold the padding channels as well: loaded, never selected); else three floats.
+    static __device__ __forceinline__ void nhwc(const float* __restrict__ g, int ld, int coff, plane_t* s, long n, int y0, int x0,
+                                                 int H, int W, int tid) {
+        const bool wide = (ld == 4 || ld == 8) && ((uintptr_t)g & 15u) == 0;
+        for (int it = tid; it < LR * LC; it += 256) {
+            const int r = it / LC, x = it - r * LC;
+            const int gy = y0 - R + r, gx = x0 - R + x;
+            if (gy < 0 || gy >= H || gx < 0 || gx >= W) continue;
+            const float* p = g + ((n * H + gy) * W + gx) * ld;
+            float v0, v1, v2;
+            if (wide) {
+                const int first = coff >> 2, last = (coff + 2) >> 2;        // the float4s that hold the image's channels
+                const float4 lo = *reinterpret_cast<const float4*>(p + (first << 2));
+                float4 hi = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (last != first) hi = *reinterpret_cast<const float4*>(p + (last << 2));
+                const int o = coff & 3;     // (selects, not an indexed array: the values stay in registers)
+                v0 = o == 0 ? lo.x : o == 1 ? lo.y : o == 2 ? lo.z : lo.w;
+                v1 = o == 0 ? lo.y : o == 1 ? lo.z : o == 2 ? lo.w : hi.x;
+                v2 = o == 0 ? lo.z : o == 1 ? lo.w : o == 2 ? hi.x : hi.y;
+            } else {
+                v0 = p[coff]; v1 = p[coff + 1]; v2 = p[coff + 2];
+            }
+            s[0][r][x] = quantise(v0);
+            s[1][r][x] = quantise(v1);
+            s[2][r][x] = quantise(v2);
+        }
+    }
+
+    // planar [N,3,H,W]: a row of a plane is count consecutive floats.  Its 16-byte aligned middle goes four pixels per lane,
+    // what lies in front of it and behind it float by float.
+    static __device__ __forceinline__ void planar(const float* __restrict__ g, plane_t* s, long n, int y0, int x0, int H, int W,
+                                                   int tid) {
+        const int gx0 = x0 - R < 0 ? 0 : x0 - R;
+        const int gx1 = x0 + TW + R > W ? W : x0 + TW + R;
+        const int count = gx1 - gx0;
+        const int c0 = gx0 - (x0 - R);              // column of the plane the first float goes to
+        const int lane = tid % F32_ROW_LANES;
+        for (int row = tid / F32_ROW_LANES; row < 3 * LR; row += 256 / F32_ROW_LANES) {
+            const int c = row / LR, r = row - c * LR;
+            const int gy = y0 - R + r;
+            if (gy < 0 || gy >= H) continue;
+            const float* p = g + (((n * 3 + c) * H + gy) * W + gx0);
+            int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);      // (p is 4-byte aligned)
+            if (head > count) head = count;
+            const int pieces = (count - head) >> 2;
+            const int tail = head + (pieces << 2);
+            if (lane < pieces) {
+                const int o = head + (lane << 2);
+                const float4 v = *reinterpret_cast<const float4*>(p + o);
+                s[c][r][c0 + o] = quantise(v.x);
+                s[c][r][c0 + o + 1] = quantise(v.y);
+                s[c][r][c0 + o + 2] = quantise(v.z);
+                s[c][r][c0 + o + 3] = quantise(v.w);
+            } else if (lane < pieces + head) {
+                const int o = lane - pieces;
+                s[c][r][c0 + o] = quantise(p[o]);
+            } else if (lane < pieces + head + (count - tail)) {
+                const int o = tail + (lane - pieces - head);
+                s[c][r][c0 + o] = quantise(p[o]);
+            }
+        }
+    }
+
+    __device__ __forceinline__ void operator()(plane_t* sa, plane_t* sb, long n, int y0, int x0, int H, int W, int tid) const {
+        nhwc(a, lda, coff_a, sa, n, y0, x0, H, W, tid);
+        if (b_planar) planar(b, sb, n, y0, x0, H, W, tid);
+        else nhwc(b, ldb, coff_b, sb, n, y0, x0, H, W, tid);
+    }
+};
+
+// The body both kernels share: the loader fills the planes, everything behind it reads bytes.
+template <class Loader>
+__device__ __forceinline__ void image_metrics_tile(const Loader& load, const unsigned char* __restrict__ mask, int H, int W,
+                                                   int tiles_x, int tiles_y, const double* __restrict__ win,
+                                                   double* __restrict__ partial) {
     __shared__ __attribute__((aligned(16))) unsigned char sa[3][LR][LCP];
     __shared__ __attribute__((aligned(16))) unsigned char sb[3][LR][LCP];
     __shared__ double hb[5][LR][TW];        // the horizontal pass of one channel
@@ -77,19 +189,7 @@ __global__ __launch_bounds__(256) void image_metrics_u8_kernel(const unsigned ch
     }
     if (tid < 2 * R + 1) sw[tid] = win[tid];
     __syncthreads();
-    {
-        const int gx0 = x0 - R < 0 ? 0 : x0 - R;
-        const int gx1 = x0 + TW + R > W ? W : x0 + TW + R;
-        const int nbytes = (gx1 - gx0) * 3;
-        const int p0 = (gx0 - (x0 - R)) * 3;
-        for (int r = tid / LANES_PER_ROW; r < LR; r += 256 / LANES_PER_ROW) {
-            const int gy = y0 - R + r;
-            if (gy < 0 || gy >= H) continue;
-            const long off = ((n * H + gy) * W + gx0) * 3;
-            load_row(a + off, nbytes, sa, r, p0, tid % LANES_PER_ROW);
-            load_row(b + off, nbytes, sb, r, p0, tid % LANES_PER_ROW);
-        }
-    }
+    load(sa, sb, n, y0, x0, H, W, tid);
     __syncthreads();
 
     const int tx = tid & 31, tr = tid >> 5;
@@ -166,6 +266,19 @@ __global__ __launch_bounds__(256) void image_metrics_u8_kernel(const unsigned ch
     if (tid < 5) partial[(long)blk * 5 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
+__global__ __launch_bounds__(256) void image_metrics_u8_kernel(const unsigned char* __restrict__ a,
+                                                                const unsigned char* __restrict__ b,
+                                                                const unsigned char* __restrict__ mask, int H, int W,
+                                                                int tiles_x, int tiles_y, const double* __restrict__ win,
+                                                                double* __restrict__ partial) {
+    image_metrics_tile(U8Loader{a, b}, mask, H, W, tiles_x, tiles_y, win, partial);
+}
+
+__global__ __launch_bounds__(256) void image_metrics_f32_kernel(F32Loader load, int H, int W, int tiles_x, int tiles_y,
+                                                                 const double* __restrict__ win, double* __restrict__ partial) {
+    image_metrics_tile(load, nullptr, H, W, tiles_x, tiles_y, win, partial);
+}
+
 // out[n][k] = the sum of image n's tile partials: thread t adds tiles t, t + 256, ... in turn, then the 256 threads are added
 // by the same tree every time.
 __global__ __launch_bounds__(256) void image_metrics_sum_kernel(const double* __restrict__ partial, int tiles,
@@ -202,6 +315,28 @@ extern "C" int ssc_image_metrics_u8(const uint8_t* a, const uint8_t* b, const ui
     if (ws == nullptr || ((uintptr_t)ws & 7) || ws_bytes < tiles * N * 5 * (int64_t)sizeof(double)) return -2;
     if (((uintptr_t)win11 & 7) || ((uintptr_t)out & 7)) return -3;
     hipLaunchKernelGGL(image_metrics_u8_kernel, dim3((unsigned)(tiles * N)), dim3(256), 0, (hipStream_t)stream, a, b, mask, H, W,
+                       (int)tiles_x, (int)tiles_y, win11, (double*)ws);
+    const int rc = CHECK_LAUNCH();
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(image_metrics_sum_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
+                       (int)tiles, out);
+    return CHECK_LAUNCH();
+}
+
+extern "C" int ssc_image_metrics_f32(const float* a, int lda, int coff_a, const float* b, int ldb, int coff_b, int b_planar,
+                                     int N, int H, int W, const double* win11, double* out, void* ws, int64_t ws_bytes,
+                                     void* stream) {
+    if (N < 1 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return -1;
+    if (coff_a < 0 || lda < 3 || coff_a + 3 > lda) return -1;
+    if (!b_planar && (coff_b < 0 || ldb < 3 || coff_b + 3 > ldb)) return -1;
+    const int64_t tiles_y = (H + TH - 1) / TH, tiles_x = (W + TW - 1) / TW;
+    const int64_t tiles = tiles_x * tiles_y;
+    if (tiles > INT32_MAX || tiles * N > INT32_MAX) return -1;
+    if (a == nullptr || b == nullptr || win11 == nullptr || out == nullptr) return -1;
+    if (ws == nullptr || ((uintptr_t)ws & 7) || ws_bytes < tiles * N * 5 * (int64_t)sizeof(double)) return -2;
+    if (((uintptr_t)win11 & 7) || ((uintptr_t)out & 7) || ((uintptr_t)a & 3) || ((uintptr_t)b & 3)) return -3;
+    const F32Loader load{a, lda, coff_a, b, b_planar ? 0 : ldb, b_planar ? 0 : coff_b, b_planar ? 1 : 0};
+    hipLaunchKernelGGL(image_metrics_f32_kernel, dim3((unsigned)(tiles * N)), dim3(256), 0, (hipStream_t)stream, load, H, W,
                        (int)tiles_x, (int)tiles_y, win11, (double*)ws);
     const int rc = CHECK_LAUNCH();
     if (rc != 0) return rc;

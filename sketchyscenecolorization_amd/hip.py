@@ -180,6 +180,7 @@ SIGNATURES = {
     'ssc_bg_stage_cached_u8': [_P, _L, _P, _L, _P, _L, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P],
     'ssc_bg_finish_u8': [_P, _I, _P, _P, _L, _P, _P],
     'ssc_image_metrics_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
+    'ssc_image_metrics_f32': [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_resample_u8': [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'ssc_decode_paired_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     'ssc_decode_minmax_u8': [_P, _I, _I, _I, _P, _P],
@@ -1126,12 +1127,12 @@ def bg_finish_u8(image, fg_u8=None, mask_u8=None, out=None):
     return out
 
 
-METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 owns (csrc/metrics.hip)
+METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 / _f32 owns (csrc/metrics.hip)
 _ssim_win = {}
 
 
 def image_metrics_workspace_bytes(n, h, w):
-    """What ssc_image_metrics_u8 needs: five doubles per tile and image."""
+    """What ssc_image_metrics_u8 and ssc_image_metrics_f32 need: five doubles per tile and image."""
     th, tw = METRICS_TILE
     return n * ((h + th - 1) // th) * ((w + tw - 1) // tw) * 5 * 8
 
@@ -1157,6 +1158,34 @@ def image_metrics_u8(a_u8, b_u8, mask_u8=None, out=None):
     ws = workspace(max(image_metrics_workspace_bytes(n, h, w), 256 << 20))
     check(lib().ssc_image_metrics_u8(ptr(a_u8), ptr(b_u8), ptr(mask_u8), n, h, w, ptr(win), ptr(out), ptr(ws), ws.numel() * 4,
                                      stream_ptr()), 'image_metrics_u8')
+    return out
+
+
+def image_metrics_f32(a, coff_a, b, coff_b=None, out=None):
+    """``image_metrics_u8(image_postprocess_u8(a), image_postprocess_u8(b))`` bit for bit, without the uint8 images: a float
+    NHWC [N,H,W,lda] with the image in channels [coff_a, coff_a + 3) (a generator context's ``out`` / ``out_coff``); b the same
+    form with its own ``coff_b``, or -- ``b.dim() == 4 and coff_b is None`` -- planar NCHW [N,3,H,W] (a decoded target).
+    -> float64 [N,5] on the device, the rows of ``image_metrics_u8``; no mask."""
+    n, h, w, lda = a.shape
+    planar = b.dim() == 4 and coff_b is None
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_cuda and b.device == a.device
+    assert a.is_contiguous() and b.is_contiguous() and 0 <= coff_a and coff_a + 3 <= lda
+    if planar:
+        assert tuple(b.shape) == (n, 3, h, w)
+        ldb, coff_b = 0, 0
+    else:
+        assert b.dim() == 4 and tuple(b.shape[:3]) == (n, h, w) and 0 <= coff_b and coff_b + 3 <= b.shape[3]
+        ldb = b.shape[3]
+    if out is None:
+        out = torch.empty((n, 5), dtype=torch.float64, device=a.device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (n, 5) and out.is_contiguous() and out.device == a.device
+    win = _ssim_win.get(a.device)
+    if win is None:
+        from .metrics import ssim_window
+        win = _ssim_win[a.device] = torch.from_numpy(ssim_window()).to(a.device)
+    ws = workspace(max(image_metrics_workspace_bytes(n, h, w), 256 << 20))
+    check(lib().ssc_image_metrics_f32(ptr(a), lda, coff_a, ptr(b), ldb, coff_b, int(planar), n, h, w, ptr(win), ptr(out), ptr(ws),
+                                      ws.numel() * 4, stream_ptr()), 'image_metrics_f32')
     return out
 
 

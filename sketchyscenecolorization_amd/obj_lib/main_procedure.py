@@ -232,6 +232,26 @@ def train(**kwargs):
               + (' (--record_cache device has nothing to cache)' if getattr(Config, 'record_cache', 'off') == 'device' else ''))
         q1 = SyntheticQueue(batch_size, img, Config.vocab_size, seed=1234 + 1000 * rank)
         q2 = SyntheticQueue(batch_size, img, Config.vocab_size, seed=998244 + 1000 * rank)
+    # --val_freq F: a held-out pass every F iterations (train_validation.py).  The records of data/tfrecord/val live in a second
+    # device cache beside the training one -- whether or not training itself reads from a cache -- built with the run's image size
+    # and --distance_map flag, and found again by a NaN restart.  Every rank knows WHETHER passes happen (their iterations do not
+    # prefetch); rank 0 alone holds the cache and runs them.
+    val_freq = int(getattr(Config, 'val_freq', 0) or 0)
+    validate, evaluator = False, None
+    if val_freq > 0:
+        val_dir = os.path.join('data', 'tfrecord', 'val')
+        validate = os.path.isdir(val_dir)
+        if not validate:
+            print('data/tfrecord/val not found: --val_freq %d is ignored, nothing is scored during training' % val_freq)
+        elif rank == 0:
+            from ..record_cache import get_record_cache
+            from ..train_validation import HeldOutEvaluator
+            val_cache = get_record_cache(val_dir, img, distance_map, device='cuda:%d' % torch.cuda.current_device(),
+                                         max_records=(int(getattr(Config, 'val_records', 0) or 0) or None))
+            evaluator = HeldOutEvaluator(val_cache, batch_size)
+            print('held-out cache: %d records, %d bytes (%.1f MB%s) on %s, built in %.1f s; a pass of %d batches every %d iterations'
+                  % (len(val_cache), val_cache.nbytes, val_cache.nbytes / 1e6, ', distance maps included' if distance_map else '',
+                     val_cache.device, val_cache.build_seconds, len(evaluator.plan), val_freq))
     opt_g, opt_d, loss_g, loss_d, merged_all = build_multi_tower_graph(
         q1.field('images', advance=True), q1.field('sketches'), q2.field('images_d', advance=True),
         q1.field('class_id'), q2.field('class_id_d'), q1.field('text'),
@@ -250,6 +270,7 @@ def train(**kwargs):
     print_parameter_count(store)
     counter.assign(iter_from)
     log_f = open(os.path.join(log_dir, 'scalars.jsonl'), 'a') if rank == 0 else None
+    val_f = open(os.path.join(log_dir, 'validation.jsonl'), 'a') if evaluator is not None else None
     prev_time = float("-inf")
     fetch_counter, fetch_add = type(opt_g)(tower, 'counter'), type(opt_g)(tower, 'counter_add')
 
@@ -289,11 +310,16 @@ def train(**kwargs):
         # batch), but a snapshot written after this step would see the queue one batch ahead of the reference, so iterations
         # that write a snapshot do not prefetch (the scalar summary reads no queue).
         snapshot_iter = i % save_model_freq == save_model_freq - 1
+        # A held-out pass sits behind this G-step, where a snapshot would: the generator forward that ran ahead inside the last
+        # D-step has been consumed, and without a prefetched real pass nothing of the next iteration is in flight -- the pass
+        # shares the generator's activation buffers and bf16 planes with both.  So such an iteration does not prefetch either.
+        eval_iter = validate and (i % val_freq == val_freq - 1 or i + 1 == max_iter_step)
         _, loss_g_out, counter_out, _ = sess.run([opt_g, loss_g, fetch_counter, fetch_add],
-                                                 d_follows=(Diters >= 1 and i + 1 < max_iter_step and not snapshot_iter),
+                                                 d_follows=(Diters >= 1 and i + 1 < max_iter_step and not snapshot_iter
+                                                            and not eval_iter),
                                                  lazy=lazy)
         pending.append(('G', loss_g_out))
-        writes = (log_f is not None and i % summary_write_freq == 0) or snapshot_iter or i + 1 == max_iter_step
+        writes = (log_f is not None and i % summary_write_freq == 0) or snapshot_iter or i + 1 == max_iter_step or eval_iter
         if not lazy or writes or num_gpu > 1:       # (many towers: one read per iteration, behind the G-step's launch)
             if _settle_first(pending, len(pending)) == -1:
                 return -1
@@ -307,6 +333,18 @@ def train(**kwargs):
                 save_checkpoint(store, ckpt_dir, 'model_{}.ckpt'.format(i), global_step=i)
                 print('Save model_{}.ckpt'.format(i))
             if num_gpu > 1:     # a restart on any rank must find the snapshot rank 0 has just written
+                import torch.distributed as dist
+                dist.barrier()
+        if eval_iter:
+            if evaluator is not None:       # (every loss up to here has been read: a NaN iteration never gets a line)
+                from .. import metrics as M
+                from ..train_validation import validation_line
+                rows, seconds = evaluator.run(tower.tr)
+                line, summary = validation_line(i, evaluator.names, evaluator.groups, rows, seconds)
+                val_f.write(json.dumps(line, sort_keys=True) + '\n')
+                val_f.flush()
+                print('held-out pass at iteration %d (%.2f s): %s' % (i, seconds, M.all_line(summary)))
+            if num_gpu > 1:     # the other ranks wait for rank 0's pass, as they do for its snapshot
                 import torch.distributed as dist
                 dist.barrier()
     return status
@@ -438,6 +476,9 @@ def validation(**kwargs):
     """The reference validates from the data/tfrecord/val queue (main_procedure.py:245-358): here the
     restored generator runs over data/tfrecord/val when that directory exists, otherwise over one seeded synthetic
     batch, and writes validation_results/with_text/<category>_<name>_{output,target,input}.png.
+
+    (--distance_map is not passed to that queue yet -- the reference passes it, main_procedure.py:277-280; the held-out pass of
+    --val_freq does)
 
     --metrics 1 scores every _output against its _target on the device (hip.image_metrics_u8 on the very uint8 arrays that are
     written as PNG) and writes metrics.json beside them: the images by stem, grouped by category."""

@@ -7,6 +7,9 @@ step then uploads record numbers only and one launch gathers and decodes the bat
 obj_lib.input_pipeline.PairedQueue(record_cache=...)): no image crosses the host-device link after start-up.
 
 0.88 MB per record; 2.2 MB with the distance maps (float, instead of the uint8 sketch).
+
+--val_freq keeps a second cache, over data/tfrecord/val, beside the training one (train_validation.py): ``get_record_cache``
+keeps one cache per directory, and a cache built while others are held counts their bytes against the same half of the device.
 """
 import os
 import time
@@ -36,9 +39,11 @@ class RecordCache(object):
     ``text`` int32 [S,15], ``category`` and ``name`` (lists) on the host; ``file_range[path]`` = (first, end) record number of a
     file.  On a GPU also ``mnmx`` float [S,2], the minimum and maximum of each image resized to ``size`` (exact, so computed
     once), and with ``distance_map`` ``skf`` float [S,384,384,3] from hip.distance_map_u8 -- ``sk`` is then not kept.
-    ``device='cpu'`` holds everything but ``mnmx`` and ``skf`` (the host logic without a GPU)."""
+    ``device='cpu'`` holds everything but ``mnmx`` and ``skf`` (the host logic without a GPU).
+    ``max_records``: the first that many records only, in the same order (--val_records).  ``reserved``: bytes of the caches
+    already held on the device -- the limit of half the free memory applies to all of them together."""
 
-    def __init__(self, files, size, distance_map=False, device='cuda'):
+    def __init__(self, files, size, distance_map=False, device='cuda', max_records=None, reserved=0):
         t0 = time.time()
         self.device = torch.device(device)
         self.files, self.size, self.distance_map = list(files), int(size), bool(distance_map)
@@ -46,6 +51,11 @@ class RecordCache(object):
         R = RECORD_HW
         assert R % self.size == 0
         counts = [tfrecord.count_records(p) for p in self.files]
+        if max_records is not None:     # the first max_records records: whole files, then the head of one, then nothing
+            left = int(max_records)
+            for i, c in enumerate(counts):
+                counts[i] = min(c, left)
+                left -= counts[i]
         S = int(sum(counts))
         if S == 0:
             raise ValueError('no records in %s' % (self.files,))
@@ -55,10 +65,13 @@ class RecordCache(object):
         self.nbytes = S * per_record
         if on_gpu:
             free = torch.cuda.mem_get_info(self.device)[0]
-            if self.nbytes > free // 2:
+            if self.nbytes + reserved > (free + reserved) // 2:
                 raise RuntimeError('the record cache needs %d bytes (%d records of %d bytes%s), more than half of the %d bytes free '
-                                   'on the device: run with --record_cache off'
-                                   % (self.nbytes, S, per_record, ' with their distance maps' if self.distance_map else '', free))
+                                   'on the device%s: run with --record_cache off%s'
+                                   % (self.nbytes, S, per_record, ' with their distance maps' if self.distance_map else '', free,
+                                      ' once the %d bytes of the caches already held are counted with it' % reserved if reserved else '',
+                                      ' or hold fewer held-out records with --val_records' if (reserved or max_records is not None)
+                                      else ''))
         keep_sk = not (self.distance_map and on_gpu)
         self.img = torch.empty((S, R, R, 3), dtype=torch.uint8, device=self.device)
         self.sk = torch.empty((S, R, R, 3), dtype=torch.uint8, device=self.device) if keep_sk else None
@@ -73,6 +86,8 @@ class RecordCache(object):
         raw, self._first, k = stage.numpy(), 0, 0
         for path in self.files:
             for rec in tfrecord.read_records(path, views=True):
+                if self._first + k == self.file_range[path][1]:     # (max_records: the rest of this file is not held)
+                    break
                 feat = tfrecord.parse_example(rec, views=True)
                 raw[0, k] = np.frombuffer(feat['cartoon_data'][0], dtype=np.uint8).reshape(R, R, 3)
                 raw[1, k] = np.frombuffer(feat['sketch_data'][0], dtype=np.uint8).reshape(R, R, 3)
@@ -116,19 +131,25 @@ class RecordCache(object):
         return int(self.img.shape[0])
 
 
-_MEMO = {}              # the last cache built, by key: a restart after a NaN loss calls train() again in the same process
+_MEMO = {}              # key -> cache, one per directory: a restart after a NaN loss calls train() again in the same process
 BUILDS = 0              # caches built by get_record_cache in this process
 
 
-def get_record_cache(data_dir, size, distance_map=False, device='cuda'):
+def get_record_cache(data_dir, size, distance_map=False, device='cuda', max_records=None):
     """The cache of ``data_dir`` for this image size, built on the first call and found again by later ones as long as the
-    files (names, sizes, modification times), the size, the distance-map flag and the device are the same.  One cache is
-    kept: another key frees the earlier one first."""
+    files (names, sizes, modification times), the size, the distance-map flag, the device and the record limit are the same.
+    One cache is kept per directory (the training set and the held-out set live side by side): another key for the same
+    directory frees that directory's earlier cache first.  A cache is built with the bytes of the others on its device
+    counted against the same limit (``RecordCache(reserved=...)``)."""
     global BUILDS
     files = list_record_files(data_dir)
-    key = (files_key(files), int(size), bool(distance_map), str(torch.device(device)))
+    where = os.path.abspath(data_dir)
+    key = (where, files_key(files), int(size), bool(distance_map), str(torch.device(device)),
+           None if max_records is None else int(max_records))
     if key not in _MEMO:
-        _MEMO.clear()
-        _MEMO[key] = RecordCache(files, size, distance_map, device)
+        for k in [k for k in _MEMO if k[0] == where]:
+            del _MEMO[k]
+        reserved = sum(c.nbytes for c in _MEMO.values() if c.device == torch.device(device) and c.device.type == 'cuda')
+        _MEMO[key] = RecordCache(files, size, distance_map, device, max_records=max_records, reserved=reserved)
         BUILDS += 1
     return _MEMO[key]

@@ -158,6 +158,7 @@ class GanTrainer(object):
         self._real_pending, self._real_key = False, None
         self.loss_real = torch.zeros(1, dtype=torch.float64, device=device)      # its loss terms
         self.use_graphs_infer = os.environ.get('SSC_INFER_GRAPHS', '1') == '1'   # hipGraph replay of generate / generate_u8
+        self.infer_nhwc = None          # (buffer, channel offset) of the last inference pass's image (_infer)
         self.G.text_stream = self._text_stream          # forward half: every generator
         if block_type == 'Pix2Pix':
             self.G.text_stream_bwd = None if self.segment_graphs else self._text_stream
@@ -856,19 +857,25 @@ class GanTrainer(object):
         shape is seen, is captured into a hipGraph the second time and replayed afterwards (a batch-16 forward is ~150
         launches of 5-100 us: launch-bound when issued one by one); inputs are copied into the graph's static tensors
         (unless they ARE those tensors: ``infer_buffers``) and the result is returned as a fresh tensor (clone=False: the
-        graph's own output tensor, valid until the next call)."""
+        graph's own output tensor, valid until the next call).  ``self.infer_nhwc`` = (the generator's NHWC output buffer, the
+        channel its image starts at) of the pass just run, valid as long: what hip.image_metrics_f32 reads."""
         if self.block_type == 'MRU' and labels is None:
             raise ValueError('the MRU generator is class-conditional: pass the class ids (image_data_class_id)')
         labels = None if self.block_type != 'MRU' else labels.to(device='cuda', dtype=torch.int32).contiguous()
 
+        made = {}       # the generator's own output buffer of this pass: see infer_nhwc
+
         def body(sk, tx, nv, lb):
             xs = hip.sketch_preprocess_u8(sk, thicken) if kind == 'u8' else sk
             ctx = self.G.forward(xs, tx, lb, nv, 'g') if self.block_type == 'MRU' else self.G.forward(xs, tx, nv, 'g')
+            made['nhwc'] = (ctx['out'], ctx['out_coff'])
             return hip.image_postprocess_u8(ctx['out'], ctx['out_coff']) if kind == 'u8' else self.G.output_nchw(ctx)
 
         sketches, noise_vec = sketches.contiguous(), noise_vec.contiguous()
         if not self.use_graphs_infer or hip.PROFILE is not None:
-            return body(sketches, text, noise_vec, labels)
+            res = body(sketches, text, noise_vec, labels)
+            self.infer_nhwc = made['nhwc']
+            return res
         prep = text if isinstance(text, dict) or not self.G.lstm_hybrid else self.G.text.prepare(text, 'gi')
         S = prep['S'] if isinstance(prep, dict) else -1
         key = ('infer', kind, bool(thicken), bool(self.G.lstm_hybrid), tuple(sketches.shape), S)
@@ -880,7 +887,9 @@ class GanTrainer(object):
         if g is None:
             if key not in self._seen:
                 self._seen.add(key)
-                return body(st['sk'], prep, st['nv'], st['lb'])
+                res = body(st['sk'], prep, st['nv'], st['lb'])
+                self.infer_nhwc = made['nhwc']
+                return res
             try:
                 g = hip.new_graph()
                 with torch.cuda.graph(g, capture_error_mode='thread_local'):
@@ -889,10 +898,14 @@ class GanTrainer(object):
                 print('hipGraph capture of the inference pass failed (%r): continuing with eager launches' % (e,))
                 self.use_graphs_infer = False
                 torch.cuda.synchronize()
-                return body(sketches, text, noise_vec, labels)
+                res = body(sketches, text, noise_vec, labels)
+                self.infer_nhwc = made['nhwc']
+                return res
             self._graphs[key] = g
+            self._static[key + ('nhwc',)] = made['nhwc']
         hip.resplit_stale()         # weights replaced through torch (load_dict, a restore) since the planes were made
         g.replay()
+        self.infer_nhwc = self._static[key + ('nhwc',)]
         return self._static[key].clone() if clone else self._static[key]
 
     def generate_u8(self, sketch_u8, text, noise_vec, labels=None, thicken=False, clone=True):
