@@ -21,6 +21,12 @@ one image per forward pass, because those batch statistics would make every outp
 --metrics 1 (test mode) scores every ``outputs`` image against its ``targets`` image on the device -- mean absolute error, PSNR
 and SSIM (hip.image_metrics_u8) -- and writes ``results/metrics.json``.  Where the scene has a segment file its red channel is
 the mask: the foreground pixels that were pasted back over the generation are not counted.
+
+--val_freq F (train mode) scores a held-out set with the weights of the moment every F steps and on the last one: the scenes of
+``foreground/val``, ``background/val``, ``segment/val`` and ``captions/val.json`` (the first --val_records of them), one per
+forward pass, on the device.  A line per pass goes to ``log/validation.jsonl``: MAE / PSNR / SSIM as --metrics 1 defines them and
+the region branch's pixel accuracy and IoU (sketchyscenecolorization_amd/bg_validation.py).  Training itself is the run of
+--val_freq 0, bit for bit.  Without captions/val.json one line says so and the run trains on.
 """
 import argparse
 import json
@@ -60,6 +66,10 @@ FLAGS = [
                                 'of every sample with a freshly drawn colour pair on the device, caption to match'),
     ('metrics', int, 0, [0, 1], '1 (--mode test): score every output against its target on the GPU (MAE, PSNR, SSIM; the '
                                 'pasted-back foreground is not counted) and write results/metrics.json'),
+    ('val_freq', int, 0, None, 'steps between held-out passes in train mode (0 = never): the scenes of {foreground,background,'
+                               'segment}/val and captions/val.json are coloured one per pass with the current weights and scored '
+                               'on the GPU (MAE, PSNR, SSIM; region accuracy and IoU) into log/validation.jsonl'),
+    ('val_records', int, 0, None, 'held-out records a pass takes, the first ones in caption-file order (0 = all)'),
 ]
 
 
@@ -261,6 +271,10 @@ def bg_colorization(**p):
     nb = p['batch_size']
     cache = CachedScenes(p, scenes, tr.losses.device) if p.get('scene_cache', 'off') == 'device' else None
     n_scenes = len(cache) if cache is not None else len(scenes)
+    held = None
+    if p.get('val_freq', 0):        # the held-out set on the device, whatever --scene_cache says; both caches share one limit
+        from sketchyscenecolorization_amd import bg_validation
+        held = bg_validation.open_held_out(p, Scenes, tr, cache.cache.nbytes if cache is not None else 0)
     depth = int(os.environ.get('SSC_BG_PREFETCH', '4'))
     pool = ThreadPoolExecutor(max_workers=max(depth, 1) * min(nb, 4)) if depth > 0 and cache is None else None
     ahead, drawn = collections.deque(), [iter_from]
@@ -323,6 +337,8 @@ def bg_colorization(**p):
                       % (tr.global_step, rate, left // 86400, left % 86400 // 3600, left % 3600 // 60))
                 for n, v in zip(names, ema):
                     print(n, v)
+        if held is not None and should(p['val_freq']):
+            bg_validation.run_pass(held, tr, log_dir)       # (reads the pending losses first, as a snapshot step settles them)
         if should(p['save_freq']):
             print('saving model to', snap_dir)
             name = 'snapshot-%d' % tr.global_step
@@ -344,6 +360,11 @@ def main(argv=None):
         raise ValueError('--recolor 1 paints the cached scenes on the device: it needs --scene_cache device')
     if args.metrics and args.mode != 'test':
         raise ValueError('--metrics 1 scores the images of --mode test: training writes none')
+    if args.val_freq < 0 or args.val_records < 0:
+        raise ValueError('--val_freq %d --val_records %d: neither can be negative' % (args.val_freq, args.val_records))
+    if args.val_freq and args.mode != 'train':
+        raise ValueError('--val_freq %d scores a held-out set during --mode train: test mode scores its own images with --metrics 1'
+                         % args.val_freq)
     bg_colorization(**{name: getattr(args, name) for name, _t, _d, _c, _h in FLAGS})
 
 

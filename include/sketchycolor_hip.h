@@ -324,6 +324,28 @@ int ssc_image_metrics_u8(const uint8_t* a, const uint8_t* b, const uint8_t* mask
  * misaligned pointer (a, b: 4 bytes; win11, out: 8); nothing is launched and out is not written then. */
 int ssc_image_metrics_f32(const float* a, int lda, int coff_a, const float* b, int ldb, int coff_b, int b_planar, int N, int H,
                           int W, const double* win11, double* out, void* ws, int64_t ws_bytes, void* stream);
+/* The same five sums for the Background generator's FLOAT image against a uint8 target: scoring a held-out set during Background
+ * training.  img float rows of ldc >= 3 floats, the tanh image in channels 0..2; fg, target uint8 [N,H,W,3]; mask uint8 [N,H,W] or
+ * NULL (fg may then be NULL too).  While the tile is loaded, image a of a pixel becomes the fg byte where the mask byte is 0 and
+ * otherwise the img value quantised with the arithmetic of ssc_bg_finish_u8: floor(clamp((x+1)/2, 0, 1)*255 + 0.5) clamped to
+ * 0..255, each operation rounded to fp32, NaN to 0.  Image b is the target, and the mask counts pixels as in
+ * ssc_image_metrics_u8.  out is therefore bit-identical to ssc_image_metrics_u8(ssc_bg_finish_u8(img, fg, mask), target, mask),
+ * and the same bits from run to run; the uint8 image is never written.  16-byte loads where ldc is 4 on a 16-byte aligned base,
+ * single floats elsewhere; nothing outside [N,H,W] is read.  ws as for ssc_image_metrics_u8.
+ * Returns -1 for sizes out of range (N < 1, ldc < 3, a mask without fg, ...), -2 for a workspace that is too small or misaligned,
+ * -3 for a misaligned pointer (img: 4 bytes; win11, out: 8); nothing is launched and out is not written then. */
+int ssc_image_metrics_bg_f32(const float* img, int ldc, const uint8_t* fg, const uint8_t* target, const uint8_t* mask, int N, int H,
+                             int W, const double* win11, double* out, void* ws, int64_t ws_bytes, void* stream);
+/* Confusion counts of the region branch (metrics.hip): logits float rows of ld >= K floats, 1 <= K <= 4 (ssc_seg_ce_loss's limit),
+ * labels int32 [N,P] -> out int64 [N][K*K+1]: out[n][t*K+p] = the pixels of sample n with label t and prediction p; the last slot
+ * = the pixels whose label lies outside [0, K), which are in no other cell.  The prediction is the lowest index among the largest
+ * logits, found with strict > from index 0 against -inf: a NaN never wins and a row of NaN predicts 0.  Integer counts: one
+ * workgroup per run of pixels writes its counts to ws, a second launch adds a sample's workgroups in order; no atomics.
+ * ws: N * min(max(ceil(P/1024), 1), 256) * (K*K+1) int64, 8-byte aligned.  N <= 65535, P < 2^31.
+ * Returns -1 for sizes out of range, -2 for a workspace that is too small or misaligned, -3 for a misaligned pointer (logits,
+ * labels: 4 bytes; out: 8); nothing is launched and out is not written then. */
+int ssc_seg_confusion(const float* logits, int ld, int K, const int32_t* labels, int64_t N, int64_t P, int64_t* out, void* ws,
+                      int64_t ws_bytes, void* stream);
 /* PIL.Image.resize of an 8-bit image on the device (resize_and_padding_mask_image, input_pipeline.py:199-239: ANTIALIAS =
  * LANCZOS; reverse_resize_image, Pipeline_utils/fg_color_utils.py:137-160: scipy.misc.imresize = PIL bilinear): Pillow's
  * two-pass 8-bit resampler, horizontal then vertical, bit for bit.  src uint8 [H,W,C]; chan >= 0: only that channel,

@@ -7,9 +7,13 @@
 // registers, all in double.  Its five sums go to ws; a second launch adds the tiles of an image in a fixed order.  Integers are
 // carried as doubles (every one far below 2^53: exact in any order); the SSIM sum is ordered by construction, never by arrival.
 //
-// Two loaders fill the byte planes, one body reads them.  U8Loader takes the uint8 images of the evaluation modes; F32Loader takes
+// Three loaders fill the byte planes, one body reads them.  U8Loader takes the uint8 images of the evaluation modes; F32Loader takes
 // float images (the generator's NHWC output buffer, the decode kernel's planar target) and quantises every value on its way into
 // the planes with the arithmetic of image_postprocess_u8_kernel (elementwise.hip), so that the uint8 forms never exist in memory.
+// BgLoader is the Background module's: the generator's float image, rounded as bg_finish_u8_kernel (bg_io.hip) rounds it, with the
+// foreground bytes pasted where the mask is 0, against a uint8 target.
+//
+// ssc_seg_confusion (the region branch's score) is at the end of the file: integer counts, per-workgroup partials, a fixed fold.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sketchycolor_hip.h"
@@ -165,7 +169,65 @@ struct F32Loader {
     }
 };
 
-// The body both kernels share: the loader fills the planes, everything behind it reads bytes.
+// bg_finish_u8_kernel's value (bg_io.hip: unit_to_u8): floor(clamp((x + 1) / 2, 0, 1) * 255 + 0.5) clamped to 0..255, every
+// operation rounded to fp32 on its own (no fused y * 255 + 0.5); fminf / fmaxf drop a NaN operand, so a NaN comes out as 0
+__device__ __forceinline__ unsigned char quantise_round(float x) {
+#pragma clang fp contract(off)
+    const float h = (x + 1.f) / 2.f;
+    const float y = fminf(fmaxf(h, 0.f), 1.f) * 255.f;
+    const float r = y + 0.5f;
+    return (unsigned char)(int)fminf(fmaxf(floorf(r), 0.f), 255.f);
+}
+
+// Plane a = bg_finish_u8 of (img, fg, mask), made while it is loaded: the fg pixel where the mask byte is 0, else the rounded
+// img pixel (img: rows of ldc floats, the image in channels 0..2; ldc 4 on a 16-byte aligned base: one float4 per pixel).
+// Plane b = the uint8 target, row by row as U8Loader loads it.
+struct BgLoader {
+    const float* img;
+    int ldc;
+    const unsigned char* fg;
+    const unsigned char* target;
+    const unsigned char* mask;      // may be null: nothing is pasted, fg is not read
+
+    __device__ __forceinline__ void operator()(plane_t* sa, plane_t* sb, long n, int y0, int x0, int H, int W, int tid) const {
+        const int gx0 = x0 - R < 0 ? 0 : x0 - R;
+        const int gx1 = x0 + TW + R > W ? W : x0 + TW + R;
+        const int nbytes = (gx1 - gx0) * 3;
+        const int p0 = (gx0 - (x0 - R)) * 3;
+        for (int r = tid / LANES_PER_ROW; r < LR; r += 256 / LANES_PER_ROW) {
+            const int gy = y0 - R + r;
+            if (gy < 0 || gy >= H) continue;
+            load_row(target + ((n * H + gy) * W + gx0) * 3, nbytes, sb, r, p0, tid % LANES_PER_ROW);
+        }
+        const bool wide = ldc == 4 && ((uintptr_t)img & 15u) == 0;
+        for (int it = tid; it < LR * LC; it += 256) {
+            const int r = it / LC, x = it - r * LC;
+            const int gy = y0 - R + r, gx = x0 - R + x;
+            if (gy < 0 || gy >= H || gx < 0 || gx >= W) continue;
+            const long pix = (n * H + gy) * W + gx;
+            if (mask != nullptr && mask[pix] == 0) {
+                const unsigned char* f = fg + pix * 3;
+                sa[0][r][x] = f[0];
+                sa[1][r][x] = f[1];
+                sa[2][r][x] = f[2];
+                continue;
+            }
+            const float* p = img + pix * ldc;
+            float v0, v1, v2;
+            if (wide) {
+                const float4 v = *reinterpret_cast<const float4*>(p);
+                v0 = v.x; v1 = v.y; v2 = v.z;
+            } else {
+                v0 = p[0]; v1 = p[1]; v2 = p[2];
+            }
+            sa[0][r][x] = quantise_round(v0);
+            sa[1][r][x] = quantise_round(v1);
+            sa[2][r][x] = quantise_round(v2);
+        }
+    }
+};
+
+// The body all three kernels share: the loader fills the planes, everything behind it reads bytes.
 template <class Loader>
 __device__ __forceinline__ void image_metrics_tile(const Loader& load, const unsigned char* __restrict__ mask, int H, int W,
                                                    int tiles_x, int tiles_y, const double* __restrict__ win,
@@ -279,6 +341,11 @@ __global__ __launch_bounds__(256) void image_metrics_f32_kernel(F32Loader load, 
     image_metrics_tile(load, nullptr, H, W, tiles_x, tiles_y, win, partial);
 }
 
+__global__ __launch_bounds__(256) void image_metrics_bg_f32_kernel(BgLoader load, int H, int W, int tiles_x, int tiles_y,
+                                                                    const double* __restrict__ win, double* __restrict__ partial) {
+    image_metrics_tile(load, load.mask, H, W, tiles_x, tiles_y, win, partial);
+}
+
 // out[n][k] = the sum of image n's tile partials: thread t adds tiles t, t + 256, ... in turn, then the 256 threads are added
 // by the same tree every time.
 __global__ __launch_bounds__(256) void image_metrics_sum_kernel(const double* __restrict__ partial, int tiles,
@@ -301,6 +368,82 @@ __global__ __launch_bounds__(256) void image_metrics_sum_kernel(const double* __
     }
     __syncthreads();
     if (tid < 5) out[(long)blockIdx.x * 5 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Confusion counts of the region branch.  A workgroup takes every gridDim.x-th run of 256 pixels of one sample; a thread keeps
+// the K * K + 1 counts of its pixels in registers (the cell of a pixel is compared against every cell number: no indexed
+// array), the 64 lanes of a wave and then the 4 waves are added, and the workgroup's counts go to ws.  A second launch adds a
+// sample's workgroups in order.  Integers throughout: any order gives the same counts.
+constexpr int CONF_MAX_K = 4;
+constexpr int CONF_CELLS = CONF_MAX_K * CONF_MAX_K + 1;
+constexpr int CONF_MAX_BLOCKS = 256;        // workgroups per sample
+constexpr int CONF_PIXELS = 1024;           // pixels a workgroup takes before a sample gets another one
+
+__host__ __device__ inline long conf_blocks(long P) {
+    const long b = (P + CONF_PIXELS - 1) / CONF_PIXELS;
+    return b < 1 ? 1 : (b > CONF_MAX_BLOCKS ? CONF_MAX_BLOCKS : b);
+}
+
+__global__ __launch_bounds__(256) void seg_confusion_kernel(const float* __restrict__ logits, int ld, int K,
+                                                             const int* __restrict__ labels, long P,
+                                                             long long* __restrict__ partial) {
+    __shared__ unsigned red[4][CONF_CELLS];
+    const int tid = threadIdx.x;
+    const long n = blockIdx.y;
+    const int cells = K * K + 1;
+    const bool wide = ld == 4 && ((uintptr_t)logits & 15u) == 0;
+    unsigned cnt[CONF_CELLS];
+#pragma unroll
+    for (int c = 0; c < CONF_CELLS; ++c) cnt[c] = 0;
+    for (long i = (long)blockIdx.x * 256 + tid; i < P; i += (long)gridDim.x * 256) {
+        const long r = n * P + i;
+        const float* z = logits + r * ld;
+        float z0, z1 = 0.f, z2 = 0.f, z3 = 0.f;
+        if (wide) {
+            const float4 v = *reinterpret_cast<const float4*>(z);
+            z0 = v.x; z1 = v.y; z2 = v.z; z3 = v.w;
+        } else {
+            z0 = z[0];
+            if (K > 1) z1 = z[1];
+            if (K > 2) z2 = z[2];
+            if (K > 3) z3 = z[3];
+        }
+        // the lowest index among the largest logits; strict > from index 0 against -inf: a NaN never wins
+        float best = -INFINITY;
+        int pred = 0;
+        if (z0 > best) { best = z0; pred = 0; }
+        if (K > 1 && z1 > best) { best = z1; pred = 1; }
+        if (K > 2 && z2 > best) { best = z2; pred = 2; }
+        if (K > 3 && z3 > best) { best = z3; pred = 3; }
+        const int t = labels[r];
+        const int cell = (unsigned)t < (unsigned)K ? t * K + pred : K * K;
+#pragma unroll
+        for (int c = 0; c < CONF_CELLS; ++c) cnt[c] += (unsigned)(cell == c);
+    }
+#pragma unroll
+    for (int c = 0; c < CONF_CELLS; ++c)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt[c] += __shfl_down(cnt[c], o, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < CONF_CELLS; ++c) red[tid >> 6][c] = cnt[c];
+    }
+    __syncthreads();
+    if (tid < cells)
+        partial[(n * gridDim.x + blockIdx.x) * cells + tid] =
+            (long long)red[0][tid] + (long long)red[1][tid] + (long long)red[2][tid] + (long long)red[3][tid];
+}
+
+// out[n][c] = the sum of sample n's workgroup counts (thread c adds them in order)
+__global__ __launch_bounds__(64) void seg_confusion_sum_kernel(const long long* __restrict__ partial, int blocks, int cells,
+                                                                long long* __restrict__ out) {
+    const int c = threadIdx.x;
+    if (c >= cells) return;
+    const long long* p = partial + (long)blockIdx.x * blocks * cells;
+    long long s = 0;
+    for (int b = 0; b < blocks; ++b) s += p[(long)b * cells + c];
+    out[(long)blockIdx.x * cells + c] = s;
 }
 
 }  // namespace
@@ -342,5 +485,44 @@ extern "C" int ssc_image_metrics_f32(const float* a, int lda, int coff_a, const 
     if (rc != 0) return rc;
     hipLaunchKernelGGL(image_metrics_sum_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
                        (int)tiles, out);
+    return CHECK_LAUNCH();
+}
+
+extern "C" int ssc_image_metrics_bg_f32(const float* img, int ldc, const uint8_t* fg, const uint8_t* target, const uint8_t* mask,
+                                        int N, int H, int W, const double* win11, double* out, void* ws, int64_t ws_bytes,
+                                        void* stream) {
+    if (N < 1 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return -1;
+    if (ldc < 3) return -1;
+    const int64_t tiles_y = (H + TH - 1) / TH, tiles_x = (W + TW - 1) / TW;
+    const int64_t tiles = tiles_x * tiles_y;
+    if (tiles > INT32_MAX || tiles * N > INT32_MAX) return -1;
+    if (img == nullptr || target == nullptr || win11 == nullptr || out == nullptr) return -1;
+    if (mask != nullptr && fg == nullptr) return -1;
+    if (ws == nullptr || ((uintptr_t)ws & 7) || ws_bytes < tiles * N * 5 * (int64_t)sizeof(double)) return -2;
+    if (((uintptr_t)win11 & 7) || ((uintptr_t)out & 7) || ((uintptr_t)img & 3)) return -3;
+    const BgLoader load{img, ldc, fg, target, mask};
+    hipLaunchKernelGGL(image_metrics_bg_f32_kernel, dim3((unsigned)(tiles * N)), dim3(256), 0, (hipStream_t)stream, load, H, W,
+                       (int)tiles_x, (int)tiles_y, win11, (double*)ws);
+    const int rc = CHECK_LAUNCH();
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(image_metrics_sum_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
+                       (int)tiles, out);
+    return CHECK_LAUNCH();
+}
+
+extern "C" int ssc_seg_confusion(const float* logits, int ld, int K, const int32_t* labels, int64_t N, int64_t P, int64_t* out,
+                                 void* ws, int64_t ws_bytes, void* stream) {
+    if (K < 1 || K > CONF_MAX_K || ld < K) return -1;
+    if (N < 1 || P < 1 || N > 65535 || P > INT32_MAX) return -1;
+    if (logits == nullptr || labels == nullptr || out == nullptr) return -1;
+    const int64_t blocks = conf_blocks((long)P), cells = (int64_t)K * K + 1;
+    if (ws == nullptr || ((uintptr_t)ws & 7) || ws_bytes < N * blocks * cells * (int64_t)sizeof(int64_t)) return -2;
+    if (((uintptr_t)logits & 3) || ((uintptr_t)labels & 3) || ((uintptr_t)out & 7)) return -3;
+    hipLaunchKernelGGL(seg_confusion_kernel, dim3((unsigned)blocks, (unsigned)N), dim3(256), 0, (hipStream_t)stream, logits, ld,
+                       K, labels, (long)P, (long long*)ws);
+    const int rc = CHECK_LAUNCH();
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(seg_confusion_sum_kernel, dim3((unsigned)N), dim3(64), 0, (hipStream_t)stream, (const long long*)ws,
+                       (int)blocks, (int)cells, (long long*)out);
     return CHECK_LAUNCH();
 }

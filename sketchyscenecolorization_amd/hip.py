@@ -181,6 +181,8 @@ SIGNATURES = {
     'ssc_bg_finish_u8': [_P, _I, _P, _P, _L, _P, _P],
     'ssc_image_metrics_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_image_metrics_f32': [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    'ssc_image_metrics_bg_f32': [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
+    'ssc_seg_confusion': [_P, _I, _I, _P, _L, _L, _P, _P, _L, _P],
     'ssc_resample_u8': [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'ssc_decode_paired_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     'ssc_decode_minmax_u8': [_P, _I, _I, _I, _P, _P],
@@ -279,7 +281,7 @@ def stream_ptr():
 def ptr(t):
     if t is None:
         return None
-    assert t.is_cuda and t.dtype in (torch.float32, torch.int32, torch.float64, torch.uint8), (t.device, t.dtype)
+    assert t.is_cuda and t.dtype in (torch.float32, torch.int32, torch.float64, torch.uint8, torch.int64), (t.device, t.dtype)
     return C.c_void_p(t.data_ptr())
 
 
@@ -1127,7 +1129,7 @@ def bg_finish_u8(image, fg_u8=None, mask_u8=None, out=None):
     return out
 
 
-METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 / _f32 owns (csrc/metrics.hip)
+METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 / _f32 / _bg_f32 owns (csrc/metrics.hip)
 _ssim_win = {}
 
 
@@ -1186,6 +1188,58 @@ def image_metrics_f32(a, coff_a, b, coff_b=None, out=None):
     ws = workspace(max(image_metrics_workspace_bytes(n, h, w), 256 << 20))
     check(lib().ssc_image_metrics_f32(ptr(a), lda, coff_a, ptr(b), ldb, coff_b, int(planar), n, h, w, ptr(win), ptr(out), ptr(ws),
                                       ws.numel() * 4, stream_ptr()), 'image_metrics_f32')
+    return out
+
+
+def image_metrics_bg_f32(image, fg_u8, target_u8, mask_u8=None, out=None):
+    """``image_metrics_u8(bg_finish_u8(image, fg_u8, mask_u8), target_u8, mask_u8)`` bit for bit, without the uint8 image: image
+    float [N,H,W,ldc] with the Background generator's tanh image in channels 0..2, fg_u8 / target_u8 uint8 [N,H,W,3], mask_u8
+    uint8 [N,H,W] or None (fg_u8 may then be None too) -> float64 [N,5] on the device, the rows of ``image_metrics_u8``."""
+    n, h, w, ldc = image.shape
+    assert image.dtype == torch.float32 and image.is_cuda and image.is_contiguous() and ldc >= 3
+    assert target_u8.dtype == torch.uint8 and tuple(target_u8.shape) == (n, h, w, 3) and target_u8.is_contiguous()
+    assert target_u8.device == image.device
+    if mask_u8 is not None:
+        assert fg_u8 is not None and mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (n, h, w)
+        assert mask_u8.is_contiguous() and mask_u8.device == image.device
+    if fg_u8 is not None:
+        assert fg_u8.dtype == torch.uint8 and tuple(fg_u8.shape) == (n, h, w, 3) and fg_u8.is_contiguous()
+        assert fg_u8.device == image.device
+    if out is None:
+        out = torch.empty((n, 5), dtype=torch.float64, device=image.device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (n, 5) and out.is_contiguous() and out.device == image.device
+    win = _ssim_win.get(image.device)
+    if win is None:
+        from .metrics import ssim_window
+        win = _ssim_win[image.device] = torch.from_numpy(ssim_window()).to(image.device)
+    ws = workspace(max(image_metrics_workspace_bytes(n, h, w), 256 << 20))
+    check(lib().ssc_image_metrics_bg_f32(ptr(image), ldc, ptr(fg_u8), ptr(target_u8), ptr(mask_u8), n, h, w, ptr(win), ptr(out),
+                                         ptr(ws), ws.numel() * 4, stream_ptr()), 'image_metrics_bg_f32')
+    return out
+
+
+def seg_confusion_workspace_bytes(n, p, k):
+    """What ssc_seg_confusion needs: K * K + 1 int64 per workgroup, one workgroup per 1024 pixels of a sample, at most 256."""
+    return n * min(max((p + 1023) // 1024, 1), 256) * (k * k + 1) * 8
+
+
+def seg_confusion(logits, labels, classes=None, out=None):
+    """Region logits float [N,...,ld] (a row per pixel, the classes in its first ``classes`` floats; default: all ld) and labels
+    int32 [N,...] with one entry per row -> int64 [N, K*K+1] on the device: [n, t*K+p] = the pixels of sample n with label t and
+    prediction p (the lowest index among the largest logits; a NaN never wins), the last slot the pixels whose label lies
+    outside [0, K)."""
+    n, ld = logits.shape[0], logits.shape[-1]
+    k = ld if classes is None else int(classes)
+    p = logits.numel() // (n * ld)
+    assert logits.dtype == torch.float32 and logits.is_cuda and logits.is_contiguous() and 1 <= k <= min(ld, 4)
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.device == logits.device
+    assert labels.shape[0] == n and labels.numel() == n * p, (tuple(labels.shape), tuple(logits.shape))
+    if out is None:
+        out = torch.empty((n, k * k + 1), dtype=torch.int64, device=logits.device)
+    assert out.dtype == torch.int64 and tuple(out.shape) == (n, k * k + 1) and out.is_contiguous() and out.device == logits.device
+    ws = workspace(max(seg_confusion_workspace_bytes(n, p, k), 256 << 20))
+    check(lib().ssc_seg_confusion(ptr(logits), ld, k, ptr(labels), n, p, ptr(out), ptr(ws), ws.numel() * 4, stream_ptr()),
+          'seg_confusion')
     return out
 
 

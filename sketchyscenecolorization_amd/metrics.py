@@ -1,6 +1,7 @@
 """Full-reference image scores of the evaluation modes, the host side: the SSIM window, and the step from the five sums per
 image that hip.image_metrics_u8 returns (sum |a-b|, sum (a-b)^2, counted pixels, SSIM sum, counted windows per channel) to MAE,
-PSNR and SSIM per image, per group and over everything.  NumPy only: nothing here needs a GPU."""
+PSNR and SSIM per image, per group and over everything; and the step from the confusion counts of hip.seg_confusion to the region
+branch's pixel accuracy and IoU.  NumPy only: nothing here needs a GPU."""
 import json
 import math
 
@@ -67,3 +68,23 @@ def all_line(summary):
     fmt = lambda v, f: 'n/a' if v is None else f % v      # noqa: E731
     return 'metrics: n %d  mae %s  psnr %s dB (%d infinite)  ssim %s' % (
         a['n'], fmt(a['mae'], '%.4f'), fmt(a['psnr'], '%.3f'), a['psnr_infinite'], fmt(a['ssim'], '%.6f'))
+
+
+def region_scores(conf):
+    """Confusion counts [K*K+1] or [S, K*K+1] (hip.seg_confusion: cell t*K+p = pixels with label t and prediction p, the last
+    slot = pixels whose label lies outside [0, K); samples are added) -> {'accuracy': trace / counted pixels, 'iou': [TP / (TP +
+    FP + FN) per class, None for a class with TP + FP + FN == 0], 'miou': the mean over the classes that have a value,
+    'ignored': the last slot}.  accuracy and miou are None when nothing is counted."""
+    c = np.asarray(conf, dtype=np.int64)
+    c = c.reshape(-1, c.shape[-1]).sum(0)
+    k = int(round(math.sqrt(c.size - 1)))
+    assert k >= 1 and k * k + 1 == c.size, c.size
+    m = [[int(v) for v in row] for row in c[:k * k].reshape(k, k)]
+    counted = sum(sum(row) for row in m)
+    iou = []
+    for j in range(k):
+        tp = m[j][j]
+        union = sum(m[j]) + sum(m[t][j] for t in range(k)) - tp        # TP + FN + FP
+        iou.append(tp / union if union > 0 else None)
+    return {'accuracy': sum(m[j][j] for j in range(k)) / counted if counted > 0 else None, 'iou': iou, 'miou': _mean(iou),
+            'ignored': int(c[-1])}

@@ -33,9 +33,11 @@ class SceneCache(object):
 
     ``scenes``: the command line's ``Scenes`` (records, dirs, vocab, size, T, get).  ``keep``: the indices of the records to
     cache, in the order they are numbered here (default: all).  Without records (the synthetic scenes) every scene is cached
-    as one entry of each kind, its labels stored as the segment values they stand for."""
+    as one entry of each kind, its labels stored as the segment values they stand for.  ``beside``: the bytes of the caches that
+    live on the device already and count against the same limit (the training cache, when this one is the held-out set's);
+    ``remedy``: what the refusal tells the user to do."""
 
-    def __init__(self, scenes, device='cuda', keep=None):
+    def __init__(self, scenes, device='cuda', keep=None, beside=0, remedy='run with --scene_cache off'):
         t0 = time.time()
         self.device = torch.device(device)
         size = scenes.size
@@ -66,11 +68,14 @@ class SceneCache(object):
         P = size * size
         self.nbytes = (len(keys[0]) + len(keys[1])) * P * 3 + len(keys[2]) * P
         if self.device.type == 'cuda':
-            free = torch.cuda.mem_get_info(self.device)[0]
-            if self.nbytes > free // 2:
-                raise RuntimeError('the scene cache needs %d bytes (%d foregrounds, %d backgrounds, %d segment maps at %d x %d), '
-                                   'more than half of the %d bytes free on the device: run with --scene_cache off'
-                                   % (self.nbytes, len(keys[0]), len(keys[1]), len(keys[2]), size, size, free))
+            # the caches together may take half of what was free before the first of them was built
+            free = torch.cuda.mem_get_info(self.device)[0] + int(beside)
+            if self.nbytes + int(beside) > free // 2:
+                raise RuntimeError('the scene cache needs %d bytes (%d foregrounds, %d backgrounds, %d segment maps at %d x %d)%s, '
+                                   'more than half of the %d bytes free on the device: %s'
+                                   % (self.nbytes, len(keys[0]), len(keys[1]), len(keys[2]), size, size,
+                                      ' beside the %d bytes of the cache that is there already' % beside if beside else '',
+                                      free, remedy))
         shapes = [(len(keys[0]), size, size, 3), (len(keys[1]), size, size, 3), (len(keys[2]), size, size)]
         self.fg, self.bg, self.seg = [torch.empty(s, dtype=torch.uint8, device=self.device) for s in shapes]
         # each distinct file is decoded once, a few at a time; the decoded array goes straight into its entry
