@@ -27,6 +27,14 @@ the mask: the foreground pixels that were pasted back over the generation are no
 forward pass, on the device.  A line per pass goes to ``log/validation.jsonl``: MAE / PSNR / SSIM as --metrics 1 defines them and
 the region branch's pixel accuracy and IoU (sketchyscenecolorization_amd/bg_validation.py).  Training itself is the run of
 --val_freq 0, bit for bit.  Without captions/val.json one line says so and the run trains on.
+
+--mode scene --resume_from <stamp> --image_id <id> --instruction 'the sky is ...' colours the background of one user scene as the
+reference's scene pipeline does (Pipeline_utils/bg_utils.py::build_background_colorization): ``<scene_dir>/sketches/<id>.png``,
+``inner_masks/<id>.mat`` and ``seg_data/<id>_datas.npz`` are read, the instruction is spliced into --previous_text, the instances
+of --previous_image (default: the sketch) go through one forward pass, and the device finishes the image -- instances and sketch
+strokes pasted over the generation and, with --color_gradient 1, the sky gradient (sketchyscenecolorization_amd/bg_scene.py).
+``outputs/<stamp>/scene_results/<id>/`` receives ``<id>_bg.png``, ``<id>_fg.png`` and ``scene.json``.  The caller keeps the
+records: the next instruction names this result as --previous_image and the processed text as --previous_text.
 """
 import argparse
 import json
@@ -40,7 +48,7 @@ import numpy as np
 import torch
 
 FLAGS = [
-    ('mode', str, 'train', ['train', 'test'], 'train or test'),
+    ('mode', str, 'train', ['train', 'test', 'scene'], 'train, test, or scene: colour the background of one user scene'),
     ('resume_from', str, '', None, 'stamp of an earlier run under outputs/'),
     ('data_base_dir', str, 'data', None, 'dataset root'),
     ('image_size', int, 768, None, 'square image size'),
@@ -70,7 +78,15 @@ FLAGS = [
                                'segment}/val and captions/val.json are coloured one per pass with the current weights and scored '
                                'on the GPU (MAE, PSNR, SSIM; region accuracy and IoU) into log/validation.jsonl'),
     ('val_records', int, 0, None, 'held-out records a pass takes, the first ones in caption-file order (0 = all)'),
+    ('scene_dir', str, 'examples', None, '--mode scene: directory with sketches/, inner_masks/ and seg_data/'),
+    ('image_id', str, None, None, '--mode scene: the scene, <id> of sketches/<id>.png'),
+    ('instruction', str, None, None, "--mode scene: what to paint, e.g. 'the sky is pink'"),
+    ('previous_image', str, '', None, '--mode scene: the result of the last instruction, a png of the image size (default: the sketch)'),
+    ('previous_text', str, '', None, "--mode scene: the processed text of the last instruction (default: 'the sky is blue and the "
+                                     "ground is green')"),
+    ('color_gradient', int, 1, [0, 1], '--mode scene: 1 = lighten the sky towards the top (add_color_gradient)'),
 ]
+SCENE_FLAGS = ('scene_dir', 'image_id', 'instruction', 'previous_image', 'previous_text', 'color_gradient')
 
 
 def build_parser():
@@ -185,8 +201,68 @@ def to_u8(x):
     return (y + 0.5).floor().clamp(0, 255).to(torch.uint8).cpu().numpy()
 
 
-def bg_colorization(**p):
+def load_checkpoint(tr, snap_dir):
+    """Load the snapshot that ``snap_dir/checkpoint`` names -- a tf.train.Saver bundle or a snapshot of this command line --
+    into the trainer -> the global step it was taken at."""
+    idx = os.path.join(snap_dir, 'checkpoint')
+    with open(idx) as fp:
+        name = fp.readline().split('"')[1]
+    print('loading model from checkpoint', os.path.join(snap_dir, name))
+    from sketchyscenecolorization_amd import tf_checkpoint
+    if tf_checkpoint.is_tf_checkpoint(os.path.join(snap_dir, name)):    # a tf.train.Saver checkpoint (released model)
+        tr.store.load_dict(tf_checkpoint.read_checkpoint(os.path.join(snap_dir, name)))
+    else:
+        sd = torch.load(os.path.join(snap_dir, name), map_location='cpu')
+        tr.store.load_state_dict(sd)
+        for sc in (tr.store.generator, tr.store.discriminator):
+            if '__adam_m__/' + sc.name in sd:
+                sc.adam_m.copy_(sd['__adam_m__/' + sc.name])
+    tr.global_step = int(name.split('-')[1])
+    return tr.global_step
+
+
+def new_trainer(p):
     from sketchyscenecolorization_amd.bg_colorization import BGTrainer
+    tr = BGTrainer(image_size=p['image_size'], vocab_size=p['vocab_size'], ngf=p['ngf'], ndf=p['ndf'],
+                   seg_classes=p['seg_classes'], lr=p['lr'], max_steps=p['max_steps'], gan_weight=p['gan_weight'],
+                   l1_weight=p['l1_weight'], seg_weight=p['seg_weight'], seed=random.randint(0, 2 ** 31 - 1))
+    print('parameter_count =', tr.store.parameter_count('generator') + tr.store.parameter_count('discriminator'))
+    return tr
+
+
+def color_scene(p):
+    """--mode scene: one instruction on one scene -> the directory the three files went to."""
+    from PIL import Image
+    from sketchyscenecolorization_amd import bg_scene
+    from sketchyscenecolorization_amd.data_processing.text_processing import load_vocab_dict_from_file
+    out_dir = os.path.join('outputs', p['resume_from'])
+    scene = bg_scene.load_scene(p['scene_dir'], p['image_id'], p['image_size'])
+    previous = None
+    if p['previous_image'] != '':
+        previous = np.array(Image.open(p['previous_image']).convert('RGB'), dtype=np.uint8)
+        if previous.shape[:2] != (p['image_size'], p['image_size']):
+            raise ValueError('--previous_image %s is %d x %d, --image_size is %d'
+                             % (p['previous_image'], previous.shape[0], previous.shape[1], p['image_size']))
+    vocab = load_vocab_dict_from_file(p['vocab_file'])
+    tr = new_trainer(p)
+    print('iter_from', load_checkpoint(tr, os.path.join(out_dir, 'snapshot')))
+    facts = {}
+    bg, fg, text = bg_scene.colorize_background(tr, scene, p['instruction'], previous, p['previous_text'], bool(p['color_gradient']),
+                                                vocab=vocab, text_len=p['text_len'], info=facts)
+    print('proc_input_text:', text)
+    res_dir = os.path.join(out_dir, 'scene_results', scene['image_id'])
+    os.makedirs(res_dir, exist_ok=True)
+    Image.fromarray(bg, 'RGB').save(os.path.join(res_dir, scene['image_id'] + '_bg.png'), 'PNG')
+    Image.fromarray(fg, 'RGB').save(os.path.join(res_dir, scene['image_id'] + '_fg.png'), 'PNG')
+    with open(os.path.join(res_dir, 'scene.json'), 'w') as fp:
+        json.dump(dict(facts, text=text, color_gradient=int(bool(p['color_gradient']))), fp, sort_keys=True)
+        fp.write('\n')
+    return res_dir
+
+
+def bg_colorization(**p):
+    if p['mode'] == 'scene':
+        return color_scene(p)
     mode, stamp = p['mode'], p['resume_from']
     if stamp == '':
         if mode == 'test':
@@ -196,27 +272,8 @@ def bg_colorization(**p):
     snap_dir = os.path.join(out_dir, 'snapshot')
     os.makedirs(snap_dir, exist_ok=True)
     scenes = Scenes(p)
-    tr = BGTrainer(image_size=p['image_size'], vocab_size=p['vocab_size'], ngf=p['ngf'], ndf=p['ndf'],
-                   seg_classes=p['seg_classes'], lr=p['lr'], max_steps=p['max_steps'], gan_weight=p['gan_weight'],
-                   l1_weight=p['l1_weight'], seg_weight=p['seg_weight'], seed=random.randint(0, 2 ** 31 - 1))
-    print('parameter_count =', tr.store.parameter_count('generator') + tr.store.parameter_count('discriminator'))
-    iter_from = 0
-    if p['resume_from'] != '':
-        idx = os.path.join(snap_dir, 'checkpoint')
-        with open(idx) as fp:
-            name = fp.readline().split('"')[1]
-        print('loading model from checkpoint', os.path.join(snap_dir, name))
-        from sketchyscenecolorization_amd import tf_checkpoint
-        if tf_checkpoint.is_tf_checkpoint(os.path.join(snap_dir, name)):    # a tf.train.Saver checkpoint (released model)
-            tr.store.load_dict(tf_checkpoint.read_checkpoint(os.path.join(snap_dir, name)))
-        else:
-            sd = torch.load(os.path.join(snap_dir, name), map_location='cpu')
-            tr.store.load_state_dict(sd)
-            for sc in (tr.store.generator, tr.store.discriminator):
-                if '__adam_m__/' + sc.name in sd:
-                    sc.adam_m.copy_(sd['__adam_m__/' + sc.name])
-        iter_from = int(name.split('-')[1])
-        tr.global_step = iter_from
+    tr = new_trainer(p)
+    iter_from = load_checkpoint(tr, snap_dir) if p['resume_from'] != '' else 0
     print('iter_from', iter_from)
 
     if mode == 'test':
@@ -365,6 +422,19 @@ def main(argv=None):
     if args.val_freq and args.mode != 'train':
         raise ValueError('--val_freq %d scores a held-out set during --mode train: test mode scores its own images with --metrics 1'
                          % args.val_freq)
+    defaults = {name: default for name, _t, default, _c, _h in FLAGS}
+    if args.mode == 'scene':
+        if args.resume_from == '':
+            raise ValueError('--mode scene needs --resume_from <stamp>: the run whose snapshot colours the scene')
+        if args.image_id is None or args.instruction is None:
+            raise ValueError("--mode scene needs --image_id <id> and --instruction '<text>'")
+        if args.image_size < 16:
+            raise ValueError('--image_size %d: a scene is at least 16 x 16 (the sky colour is sought in rows 5 and 6 of the upper half)'
+                             % args.image_size)
+    else:
+        given = [name for name in SCENE_FLAGS if getattr(args, name) != defaults[name]]
+        if given:
+            raise ValueError('--%s belongs to --mode scene, this is --mode %s' % (', --'.join(given), args.mode))
     bg_colorization(**{name: getattr(args, name) for name, _t, _d, _c, _h in FLAGS})
 
 

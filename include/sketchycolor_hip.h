@@ -346,6 +346,34 @@ int ssc_image_metrics_bg_f32(const float* img, int ldc, const uint8_t* fg, const
  * labels: 4 bytes; out: 8); nothing is launched and out is not written then. */
 int ssc_seg_confusion(const float* logits, int ld, int K, const int32_t* labels, int64_t N, int64_t P, int64_t* out, void* ws,
                       int64_t ws_bytes, void* stream);
+/* --- the background of a user scene (bg_scene.hip; Pipeline_utils/bg_utils.py::build_background_colorization) ---
+ * All images uint8 [H,W,3]; inner uint8 [H,W] = 0 for background, k + 1 for instance k.  Nothing returns to the host between
+ * the launches of a scene.  Returns -1 for sizes out of range or a missing array, -2 for the workspace, -3 for a misaligned
+ * pointer (every uint8 array but sketch and grass: 4 bytes; img: 4 bytes); nothing is launched then.
+ * Crop (:222-224): fg_out uint8 [M,3] = prev where inner != 0, white elsewhere.  M <= 2^24. */
+int ssc_bg_scene_crop_u8(const uint8_t* prev, const uint8_t* inner, int64_t M, uint8_t* fg_out, void* stream);
+/* Compose (:290-314).  (1) out = img under the cast of ssc_bg_finish_u8 (img float rows of ldc >= 3 floats); (2) where inner != 0,
+ * out = fg; (3) with moved[i][j] = sketch[i-1][j-1] for i, j >= 1 and sketch[i][j] in row 0 and column 0: where moved's red byte
+ * is 0 and grass[inner] == 0, out and fg_marked take moved's pixel; elsewhere fg_marked = fg.  grass uint8 [256]: grass[v] = 1
+ * when instance v - 1 is grass (class 27), grass[0] = 0.  overlay_only != 0 (:319, behind the gradient): step 3 alone on the
+ * image already in out; img, fg and fg_marked are not touched and may be NULL.  H * W <= 2^24. */
+int ssc_bg_scene_compose_u8(const float* img, int ldc, const uint8_t* fg, const uint8_t* inner, const uint8_t* grass,
+                            const uint8_t* sketch, int H, int W, uint8_t* out, uint8_t* fg_marked, int overlay_only,
+                            void* stream);
+/* add_color_gradient (:96-166) in three launches.  img_bg = white where inner != 0, else color.  The sky colour is the most
+ * frequent RGB triple among the pixels with inner == 0 of rows search_from .. search_from + search_height - 1, the one met first
+ * in row-major order on a tie; sky_bottom the largest row <= H/2 of img_bg that holds it; start_height = floor(3 * sky_bottom /
+ * 4).  Every pixel goes u8 / 255. -> HSV -> RGB -> * 255. -> truncating cast in float64, one IEEE operation per NumPy operation
+ * of skimage's rgb2hsv / hsv2rgb, no contraction; rows i <= start_height get S = ((sh-i)/sh) * (s_sky/3) + (i/sh) * s_sky and
+ * V = ((sh-i)/sh) * min(1, 1.5 * v_sky) + (i/sh) * v_sky, the sky colour's HSV taken from float32(c) / float32(255).  Where
+ * inner != 0 out is color.  status int32 [1]: 0 ok; 1 no pixel with inner == 0 in the search rows; 2 start_height == 0 (the
+ * reference fails in both); with a non-zero status out is color unchanged.  workspace: 16 bytes, 4-byte aligned; it holds int32
+ * {sky colour r | g << 8 | b << 16, sky_bottom, start_height, 0} afterwards.  Integer compares and an integer atomic maximum
+ * decide everything: the same bytes on every run.
+ * -1 as well for search_height < 1, search_from < 0, search_from + search_height - 1 > H/2 (sky_bottom might not exist) and
+ * search_height * W > 8192 (the search rows' colours sit in LDS). */
+int ssc_bg_sky_gradient_u8(const uint8_t* color, const uint8_t* inner, int H, int W, int search_from, int search_height,
+                           uint8_t* out, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 /* PIL.Image.resize of an 8-bit image on the device (resize_and_padding_mask_image, input_pipeline.py:199-239: ANTIALIAS =
  * LANCZOS; reverse_resize_image, Pipeline_utils/fg_color_utils.py:137-160: scipy.misc.imresize = PIL bilinear): Pillow's
  * two-pass 8-bit resampler, horizontal then vertical, bit for bit.  src uint8 [H,W,C]; chan >= 0: only that channel,

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sketchycolor_hip.h"
+#include "bg_u8.h"
 
 #define CHECK_LAUNCH() ((int)hipGetLastError())
 
@@ -18,8 +19,6 @@ __device__ __forceinline__ float u8_to_unit(unsigned v) {
     const float d = q * 2.f;
     return d - 1.f;
 }
-
-__device__ __forceinline__ unsigned byte_of(const unsigned (&w)[3], int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
 
 // state[0]: high 32 bits = workgroups that have added, low 32 bits = labels != 0 so far (zeroed by the launcher on the stream).
 // The workgroup whose add completes the ticket count holds the total in the value the atomic returned: an integer sum, exact
@@ -245,16 +244,6 @@ extern "C" int ssc_bg_stage_cached_u8(const uint8_t* fg_cache, int64_t S_fg, con
                        bg_cache, (int)S_bg, seg_cache, (int)S_seg, slot, recolor, (int)N, (int)P, inputs, targets, xd_real, labels,
                        count, (unsigned long long*)workspace);
     return CHECK_LAUNCH();
-}
-
-// deprocess + convert_image_dtype(saturate=True): floor(clamp((x + 1) / 2, 0, 1) * 255 + 0.5), clamped to 0..255; every
-// operation rounded on its own (no fused y * 255 + 0.5).  fminf / fmaxf drop a NaN operand, so a NaN pixel comes out as 0.
-__device__ __forceinline__ unsigned unit_to_u8(float x) {
-#pragma clang fp contract(off)
-    const float h = (x + 1.f) / 2.f;
-    const float y = fminf(fmaxf(h, 0.f), 1.f) * 255.f;
-    const float r = y + 0.5f;
-    return (unsigned)(int)fminf(fmaxf(floorf(r), 0.f), 255.f);
 }
 
 // LOADS: 4 = rows of 4 floats, one 16-byte load per pixel; 3 = dense rows of 3 floats on a 16-byte aligned image, the 12 floats

@@ -179,6 +179,9 @@ SIGNATURES = {
     'ssc_bg_stage_u8': [_P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P],
     'ssc_bg_stage_cached_u8': [_P, _L, _P, _L, _P, _L, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P],
     'ssc_bg_finish_u8': [_P, _I, _P, _P, _L, _P, _P],
+    'ssc_bg_scene_crop_u8': [_P, _P, _L, _P, _P],
+    'ssc_bg_scene_compose_u8': [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P],
+    'ssc_bg_sky_gradient_u8': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_image_metrics_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_image_metrics_f32': [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_image_metrics_bg_f32': [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
@@ -1127,6 +1130,72 @@ def bg_finish_u8(image, fg_u8=None, mask_u8=None, out=None):
     assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, h, w, 3)
     check(lib().ssc_bg_finish_u8(ptr(image), ldc, ptr(fg_u8), ptr(mask_u8), n * h * w, ptr(out), stream_ptr()), 'bg_finish_u8')
     return out
+
+
+def _u8_image(t, h, w):
+    assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == h * w * 3 and tuple(t.shape[-3:]) == (h, w, 3), t.shape
+
+
+def bg_scene_crop_u8(prev_u8, inner_u8, out=None):
+    """The instances of the previous result: prev_u8 uint8 [H,W,3] where inner_u8 uint8 [H,W] is not 0, white elsewhere."""
+    h, w = inner_u8.shape
+    _u8_image(prev_u8, h, w)
+    assert inner_u8.dtype == torch.uint8 and inner_u8.is_contiguous()
+    if out is None:
+        out = torch.empty_like(prev_u8)
+    _u8_image(out, h, w)
+    check(lib().ssc_bg_scene_crop_u8(ptr(prev_u8), ptr(inner_u8), h * w, ptr(out), stream_ptr()), 'bg_scene_crop_u8')
+    return out
+
+
+def bg_scene_compose_u8(image, fg_u8, inner_u8, grass_u8, sketch_u8, out=None, fg_marked=None):
+    """The generator's float image [..,H,W,ldc] (channels 0..2) under bg_finish_u8's cast, fg_u8 over it where inner_u8 is not 0,
+    and over both the strokes of sketch_u8 moved one pixel down and right (red byte 0), except on grass instances (grass_u8
+    uint8 [256], indexed by the mask value) -> (out, fg_marked) uint8 [H,W,3]; fg_marked is fg_u8 with the same strokes."""
+    h, w = inner_u8.shape
+    ldc = image.shape[-1]
+    assert image.dtype == torch.float32 and image.is_contiguous() and ldc >= 3 and image.numel() == h * w * ldc
+    assert inner_u8.dtype == torch.uint8 and inner_u8.is_contiguous()
+    assert grass_u8.dtype == torch.uint8 and grass_u8.is_contiguous() and grass_u8.numel() == 256
+    _u8_image(fg_u8, h, w)
+    _u8_image(sketch_u8, h, w)
+    out = torch.empty_like(fg_u8) if out is None else out
+    fg_marked = torch.empty_like(fg_u8) if fg_marked is None else fg_marked
+    _u8_image(out, h, w)
+    _u8_image(fg_marked, h, w)
+    check(lib().ssc_bg_scene_compose_u8(ptr(image), ldc, ptr(fg_u8), ptr(inner_u8), ptr(grass_u8), ptr(sketch_u8), h, w, ptr(out),
+                                        ptr(fg_marked), 0, stream_ptr()), 'bg_scene_compose_u8')
+    return out, fg_marked
+
+
+def bg_scene_overlay_u8(image_u8, inner_u8, grass_u8, sketch_u8):
+    """Step 3 of bg_scene_compose_u8 alone, in place on image_u8 uint8 [H,W,3]: the moved sketch's strokes, grass excepted."""
+    h, w = inner_u8.shape
+    _u8_image(image_u8, h, w)
+    _u8_image(sketch_u8, h, w)
+    assert inner_u8.dtype == torch.uint8 and inner_u8.is_contiguous()
+    assert grass_u8.dtype == torch.uint8 and grass_u8.is_contiguous() and grass_u8.numel() == 256
+    check(lib().ssc_bg_scene_compose_u8(None, 0, None, ptr(inner_u8), ptr(grass_u8), ptr(sketch_u8), h, w, ptr(image_u8), None, 1,
+                                        stream_ptr()), 'bg_scene_compose_u8 (overlay)')
+    return image_u8
+
+
+def bg_sky_gradient_u8(color_u8, inner_u8, search_from=5, search_height=2, out=None, status=None):
+    """add_color_gradient of the scene pipeline on color_u8 uint8 [H,W,3] under the instance mask inner_u8 uint8 [H,W] ->
+    (out uint8 [H,W,3], status int32 [1], info int32 [4]), all on the device and unread: status 0 = ok, 1 = no background pixel in
+    the search rows, 2 = start_height 0 (out is color_u8 then); info = {sky colour r | g << 8 | b << 16, sky_bottom,
+    start_height, 0}."""
+    h, w = inner_u8.shape
+    _u8_image(color_u8, h, w)
+    assert inner_u8.dtype == torch.uint8 and inner_u8.is_contiguous()
+    out = torch.empty_like(color_u8) if out is None else out
+    _u8_image(out, h, w)
+    status = torch.empty(1, dtype=torch.int32, device=color_u8.device) if status is None else status
+    assert status.dtype == torch.int32 and status.numel() >= 1
+    ws = workspace()
+    check(lib().ssc_bg_sky_gradient_u8(ptr(color_u8), ptr(inner_u8), h, w, search_from, search_height, ptr(out), ptr(status),
+                                       ptr(ws), ws.numel() * 4, stream_ptr()), 'bg_sky_gradient_u8')
+    return out, status, ws[:4].view(torch.int32).clone()
 
 
 METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 / _f32 / _bg_f32 owns (csrc/metrics.hip)
