@@ -253,6 +253,13 @@ int ssc_conv_forward_plan(const ssc_conv_desc* d, int64_t ws_bytes, int* out5);
  * ws_bytes <= 0 stands for a NULL workspace; any other workspace is taken to be 16-byte aligned.  Computed by the functions
  * that make the launch. */
 int ssc_conv_wgrad_plan(const ssc_wgrad_desc* d, int64_t ws_bytes, int* out4);
+/* the launch plan of a filter gradient on the 128 x 128 kernels (wgrad128.hip, wgrad128_bf16.hip; host only, launches nothing):
+ * -10 when neither takes the launch (ssc_conv_wgrad128_supported says no), else 0 and out7 = {arithmetic (0 exact fp32, 1 bf16x6),
+ * taps per tile (the kernels' TPT), gathered side plain (0 / 1), dense path (0 plain by LDS-DMA, 1 plain through registers,
+ * 2 folded norm / activation; the bf16 kernel: 0 plain, 2 transformed), split-K slabs, workgroups in XCD order (0 / 1),
+ * the bf16 kernel's two LDS stages DB (0 / 1; 0 for the exact kernel)}: seven values, DB is the seventh.  ws_bytes <= 0 stands
+ * for a NULL workspace.  Computed by the functions that make the launch. */
+int ssc_conv_wgrad128_plan(const ssc_wgrad_desc* d, int64_t ws_bytes, int* out7);
 
 /* --- layout (elementwise.hip) --- */
 /* dst[n,hw,coff+c] = src[n,c,hw]; tf.transpose NCHW->NHWC (models_collection.py:381) */

@@ -458,6 +458,32 @@ static int wg128_splitk(const ssc_wgrad_desc& d, int64_t ws_bytes, bool have_ws)
 
 void ssc_launch_wgrad_reduce(const float* ws, long count, int splitk, float* out, int accumulate, hipStream_t st);   // igemm.hip
 
+// ---- the choices of a launch: the launchers below and ssc_conv_wgrad128_plan both ask these ----
+// the kernel's DMODE: 0 a plain dense tile by LDS-DMA, 1 plain through registers, 2 folded norm / activation through registers
+static int wg128_dense_mode(const ssc_wgrad_desc& d) {
+    if (!view_plain(d.d)) return 2;
+    static int dma = -1;        // SSC_WGRAD_DMA=0: plain dense tiles through registers (A/B)
+    if (dma < 0) {
+        const char* e = ssc_dev_getenv("SSC_WGRAD_DMA");
+        dma = (e != nullptr && e[0] == '0') ? 0 : 1;
+    }
+    return dma ? 0 : 1;
+}
+// workgroups of a launch: row tiles x column tiles x K slices
+static long wg128_wgs(const ssc_wgrad_desc& d, int splitk) {
+    const long Mtot = (long)d.TH * d.TW * (d.g.C0 + d.g.C1);
+    return ((Mtot + TB - 1) / TB) * ((d.Nn + TB - 1) / TB) * splitk;
+}
+// whole K slices per XCD (the kernel's xcd flag): a split launch whose grid is a multiple of 8
+static int wg128_xcd(long wgs, int splitk) {
+    static int xcd_on = -1;     // SSC_WG128_XCD=0: plain grid order (A/B)
+    if (xcd_on < 0) {
+        const char* e = ssc_dev_getenv("SSC_WG128_XCD");
+        xcd_on = (e != nullptr && e[0] == '0') ? 0 : 1;
+    }
+    return (xcd_on && splitk > 1 && (wgs & 7) == 0) ? 1 : 0;
+}
+
 template <bool GPLAIN, int DMODE, int TPT>
 static int launch_wg128(const ssc_wgrad_desc& d, int splitk, float* ws, hipStream_t st) {
     constexpr size_t lds = (2 + NBB) * BK * TB * sizeof(float) + 2 * TPT * 256 * sizeof(int2);
@@ -471,13 +497,8 @@ static int launch_wg128(const ssc_wgrad_desc& d, int splitk, float* ws, hipStrea
         if (arc != 0) return arc;
     }
     const long out_count = Mtot * d.ldc;
-    const long wgs = ((Mtot + TB - 1) / TB) * ((d.Nn + TB - 1) / TB) * splitk;
-    static int xcd_on = -1;     // SSC_WG128_XCD=0: plain grid order (A/B)
-    if (xcd_on < 0) {
-        const char* e = ssc_dev_getenv("SSC_WG128_XCD");
-        xcd_on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    const int xcd = (xcd_on && splitk > 1 && (wgs & 7) == 0) ? 1 : 0;
+    const long wgs = wg128_wgs(d, splitk);
+    const int xcd = wg128_xcd(wgs, splitk);
     hipLaunchKernelGGL((conv_wgrad128_kernel<GPLAIN, DMODE, TPT>), dim3((unsigned)wgs), dim3(256), lds, st, d, mg,
                        ws, out_count, splitk, xcd);
     if (splitk > 1) ssc_launch_wgrad_reduce(ws, out_count, splitk, d.out, d.accumulate, st);
@@ -486,14 +507,10 @@ static int launch_wg128(const ssc_wgrad_desc& d, int splitk, float* ws, hipStrea
 
 template <int TPT>
 static int launch_wg128_t(const ssc_wgrad_desc& d, int splitk, float* ws, hipStream_t st) {
-    const bool gp = view_plain(d.g), dp = view_plain(d.d);
-    static int dma = -1;        // SSC_WGRAD_DMA=0: plain dense tiles through registers (A/B)
-    if (dma < 0) {
-        const char* e = ssc_dev_getenv("SSC_WGRAD_DMA");
-        dma = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    if (dp && dma) return gp ? launch_wg128<true, 0, TPT>(d, splitk, ws, st) : launch_wg128<false, 0, TPT>(d, splitk, ws, st);
-    if (dp) return gp ? launch_wg128<true, 1, TPT>(d, splitk, ws, st) : launch_wg128<false, 1, TPT>(d, splitk, ws, st);
+    const bool gp = view_plain(d.g);
+    const int dmode = wg128_dense_mode(d);
+    if (dmode == 0) return gp ? launch_wg128<true, 0, TPT>(d, splitk, ws, st) : launch_wg128<false, 0, TPT>(d, splitk, ws, st);
+    if (dmode == 1) return gp ? launch_wg128<true, 1, TPT>(d, splitk, ws, st) : launch_wg128<false, 1, TPT>(d, splitk, ws, st);
     return gp ? launch_wg128<true, 2, TPT>(d, splitk, ws, st) : launch_wg128<false, 2, TPT>(d, splitk, ws, st);
 }
 
@@ -509,6 +526,8 @@ extern "C" int ssc_wg128_timing(unsigned long long* out8, int reset) {
 
 // wgrad128_bf16.hip: the same tile on the bf16 matrix pipe (3-way split of both operands)
 int ssc_launch_wgrad128_bf(const ssc_wgrad_desc& d, int tpt, int splitk, float* ws, hipStream_t st);
+// what that launch chooses: {gathered side plain, dense side plain, DB, xcd}
+void ssc_wgrad128_bf_form(const ssc_wgrad_desc& d, int splitk, int* out4);
 static bool wg128_use_bf() {
     static int on = -1;         // SSC_ARITH=fp32 (everything exact) or SSC_WGRAD_BF16=0 (this kernel only): the exact-fp32 MFMA form
     if (on < 0) {
@@ -521,12 +540,41 @@ static bool wg128_use_bf() {
 
 int ssc_conv_wgrad128_bf_selected(const ssc_wgrad_desc* dp) { return (wg128_use_bf() && dp->exact == 0) ? 1 : 0; }
 
+// which of the two kernels takes a launch: 0 the exact-fp32 one, 1 the bf16 one, -10 neither
+static int wg128_arith(const ssc_wgrad_desc& d) {
+    if (!ssc_conv_wgrad128_supported(&d)) return -10;
+    if (wg128_use_bf() && d.exact == 0) return 1;
+    if (d.Cg_real != d.g.C0 + d.g.C1 || wg128_tpt(d) == 3) return -10;       // (unreachable: those shapes qualify for the bf16 form only)
+    return 0;
+}
+
 extern "C" int ssc_conv_wgrad128(const ssc_wgrad_desc* dp, float* ws, int64_t ws_bytes, void* stream) {
     const ssc_wgrad_desc& d = *dp;
-    if (!ssc_conv_wgrad128_supported(dp)) return -10;
+    const int arith = wg128_arith(d);
+    if (arith < 0) return arith;
     const int sk = wg128_splitk(d, ws_bytes, ws != nullptr);
-    if (wg128_use_bf() && d.exact == 0)
-        return ssc_launch_wgrad128_bf(d, wg128_tpt(d), sk, ws, (hipStream_t)stream);
-    if (d.Cg_real != d.g.C0 + d.g.C1 || wg128_tpt(d) == 3) return -10;       // (unreachable: those shapes qualify for the bf16 form only)
+    if (arith == 1) return ssc_launch_wgrad128_bf(d, wg128_tpt(d), sk, ws, (hipStream_t)stream);
     return wg128_tpt(d) == 2 ? launch_wg128_t<2>(d, sk, ws, (hipStream_t)stream) : launch_wg128_t<1>(d, sk, ws, (hipStream_t)stream);
+}
+
+extern "C" int ssc_conv_wgrad128_plan(const ssc_wgrad_desc* dp, int64_t ws_bytes, int* out7) {
+    // host only: {arithmetic, TPT, gathered side plain, dense path, split-K slabs, xcd, DB}; ws_bytes <= 0 stands for a NULL workspace
+    const ssc_wgrad_desc& d = *dp;
+    const int arith = wg128_arith(d);
+    if (arith < 0) return arith;
+    const int sk = wg128_splitk(d, ws_bytes, ws_bytes > 0);
+    out7[0] = arith;
+    out7[1] = wg128_tpt(d);
+    out7[4] = sk;
+    if (arith == 1) {
+        int f[4];
+        ssc_wgrad128_bf_form(d, sk, f);
+        out7[2] = f[0]; out7[3] = f[1] ? 0 : 2; out7[5] = f[3]; out7[6] = f[2];
+    } else {
+        out7[2] = view_plain(d.g) ? 1 : 0;
+        out7[3] = wg128_dense_mode(d);
+        out7[5] = wg128_xcd(wg128_wgs(d, sk), sk);
+        out7[6] = 0;
+    }
+    return 0;
 }

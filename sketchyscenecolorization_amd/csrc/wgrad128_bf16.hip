@@ -363,11 +363,31 @@ static bool wb_view_plain(const ssc_gview& g) {
            (g.C1 == 0 || (g.ab1 == nullptr && (g.act1 >= 0 ? g.act1 : g.act) == SSC_ACT_NONE));
 }
 
+// ---- the choices of a launch: the launchers below and ssc_wgrad128_bf_form (the plan query of wgrad128.hip) both ask these ----
+static long wb_wgs(const ssc_wgrad_desc& d, int splitk) {
+    const long Mtot = (long)d.TH * d.TW * (d.g.C0 + d.g.C1);
+    return ((Mtot + TB - 1) / TB) * ((d.Nn + TB - 1) / TB) * splitk;
+}
+static int wb_xcd(long wgs, int splitk) { return (splitk > 1 && (wgs & 7) == 0) ? 1 : 0; }
+static int wb_db() {
+    static int db = -1;         // SSC_WGBF_DB=1: two LDS stages, one workgroup per CU (A/B)
+    if (db < 0) {
+        const char* e = ssc_dev_getenv("SSC_WGBF_DB");
+        db = (e != nullptr && e[0] == '1') ? 1 : 0;
+    }
+    return db;
+}
+void ssc_wgrad128_bf_form(const ssc_wgrad_desc& d, int splitk, int* out4) {
+    out4[0] = wb_view_plain(d.g) ? 1 : 0;
+    out4[1] = wb_view_plain(d.d) ? 1 : 0;
+    out4[2] = wb_db();
+    out4[3] = wb_xcd(wb_wgs(d, splitk), splitk);
+}
+
 template <bool GPLAIN, bool DPLAIN, int TPT, bool DB>
 static int launch_wb(const ssc_wgrad_desc& d, int splitk, float* ws, hipStream_t st) {
     constexpr size_t lds = (DB ? 2 : 1) * WB_STAGE + 2 * TPT * 256 * sizeof(int2);
     const int Cg = d.g.C0 + d.g.C1;
-    const long Mtot = (long)d.TH * d.TW * Cg;
     const long P = (long)d.NB * d.PH * d.PW;
     const Magics mg = make_magics((unsigned)Cg, (unsigned)d.TW, (unsigned long)d.PW, (unsigned long)d.PH * d.PW, (unsigned long)P);
     static unsigned long long attr_done = 0;
@@ -376,8 +396,8 @@ static int launch_wb(const ssc_wgrad_desc& d, int splitk, float* ws, hipStream_t
         if (arc != 0) return arc;
     }
     const long out_count = (long)d.TH * d.TW * d.Cg_real * d.ldc;       // rows of the OUTPUT (the slabs' and the reduce's extent)
-    const long wgs = ((Mtot + TB - 1) / TB) * ((d.Nn + TB - 1) / TB) * splitk;
-    const int xcd = (splitk > 1 && (wgs & 7) == 0) ? 1 : 0;
+    const long wgs = wb_wgs(d, splitk);
+    const int xcd = wb_xcd(wgs, splitk);
     hipLaunchKernelGGL((conv_wgrad128_bf_kernel<GPLAIN, DPLAIN, TPT, DB>), dim3((unsigned)wgs), dim3(256), lds, st, d, mg, ws, out_count,
                        splitk, xcd);
     if (splitk > 1) ssc_launch_wgrad_reduce(ws, out_count, splitk, d.out, d.accumulate, st);
@@ -385,12 +405,10 @@ static int launch_wb(const ssc_wgrad_desc& d, int splitk, float* ws, hipStream_t
 }
 
 int ssc_launch_wgrad128_bf(const ssc_wgrad_desc& d, int tpt, int splitk, float* ws, hipStream_t st) {
-    const bool gp = wb_view_plain(d.g), dp = wb_view_plain(d.d);
-    static int db = -1;         // SSC_WGBF_DB=1: two LDS stages, one workgroup per CU (A/B)
-    if (db < 0) {
-        const char* e = ssc_dev_getenv("SSC_WGBF_DB");
-        db = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
+    int form[4];
+    ssc_wgrad128_bf_form(d, splitk, form);
+    const bool gp = form[0] != 0, dp = form[1] != 0;
+    const int db = form[2];
 #define WB_CASE2(T, D)                                                                                              \
     return gp ? (dp ? launch_wb<true, true, T, D>(d, splitk, ws, st) : launch_wb<true, false, T, D>(d, splitk, ws, st)) \
               : (dp ? launch_wb<false, true, T, D>(d, splitk, ws, st) : launch_wb<false, false, T, D>(d, splitk, ws, st))

@@ -5,7 +5,8 @@ device outputs, the raw return code of an entry point, and the two comparison ru
   check_fp32 per element max(that floor, 4 x |float32 oracle - float64 oracle|): for formulas that lose digits in float32 by
              construction, the same way in the reference (the factor 4 allows for expf / logf / tanhf a few ulp off libm)
   check_dot  per element |device - float64 oracle| <= (K + 8) * 2^-24 * S for sums of K fp32 products, S the float64 sum of the
-             absolute products: the any-order dot-product bound, nothing measured in it (tests/test_gpu_wgrad_forms.py)
+             absolute products: the any-order dot-product bound, nothing measured in it (tests/test_gpu_wgrad_forms.py,
+             tests/test_gpu_wgrad128_forms.py)
 
 All print the measured distance before they assert and log it with conftest.parity_log (variant='kernel', never forward=True:
 these are not network outputs)."""
@@ -98,19 +99,23 @@ def check_fp32(test, config, got, ref64, ref32, tol=1e-5, what=''):
 U_FP32 = 2.0 ** -24        # unit roundoff of fp32
 
 
-def check_dot(test, config, got, ref64, S, K, plan=None, what=''):
+def check_dot(test, config, got, ref64, S, K, plan=None, what='', extra_terms=0):
     """An fp32 sum of K products, added up in any order: per element |got - ref64| <= (K + 8) * 2^-24 * S, where S is the float64
     sum of the absolute products of that element.  gamma_K = K*u / (1 - K*u) bounds the rounding of the products and of the K - 1
     additions in whatever order (Higham, Accuracy and Stability of Numerical Algorithms, section 3.1); the 8 more roundings per
     term allow for the folded norm (one fma), the activation's slope product and the float32 slope constant on either factor, and
     the additions of split-K slabs and of an accumulate base, which the caller counts as one more term of S.  (K + 8) * u stands
     for gamma_(K+8): the quotient 1 - (K+8)*u is within 1e-3 of 1 for every K the tests use, K <= 8192.)
+    Beyond K + 8 = 16384 (up to 2^17) the bound is gamma_(K+8) = (K+8)*u / (1 - (K+8)*u) itself.
+    extra_terms: further roundings per term a kernel's arithmetic costs by construction, added to the 8 (the bf16x6 filter
+    gradient: 2, its three dropped products, together below 2^-23 |a*b|).
     plan: what ssc_conv_wgrad_plan reported for the launch, logged with the worst err / bound ratio."""
     got, ref64, S = _f64(got), _f64(ref64), _f64(S)
     assert got.shape == ref64.shape == S.shape, (test, what, got.shape, ref64.shape, S.shape)
-    assert K + 8 <= 16384, K
+    n = K + 8 + extra_terms
+    assert extra_terms >= 0 and n <= 2 ** 17, (K, extra_terms)
     assert bool(torch.isfinite(got).all()), (test, what, config, 'non-finite output')
-    bound = (K + 8) * U_FP32 * S
+    bound = (n * U_FP32 if K + 8 <= 16384 else n * U_FP32 / (1.0 - n * U_FP32)) * S
     err = (got - ref64).abs()
     ratio = torch.where(err > 0, err / torch.clamp(bound, min=1e-300), torch.zeros_like(err))
     k = int(torch.argmax(ratio))

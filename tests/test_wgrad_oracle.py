@@ -7,10 +7,7 @@ import wgrad_oracle as O
 from kernel_check import check_dot
 
 
-@pytest.mark.parametrize('name', [c['name'] for c in O.CASES])
-def test_autograd_reference_equals_tap_loop_reference(name):
-    """(a) autograd through oracle/tf_ops.py == (b) shifted slices + einsum, to 1e-12 of the largest value."""
-    c = O.BY_NAME[name]
+def _agree(c):
     inp = O.make_inputs(c)
     a = O.ref_autograd(c, inp)
     b, S = O.ref_taps(c, inp)
@@ -18,6 +15,32 @@ def test_autograd_reference_equals_tap_loop_reference(name):
     scale = float(b.abs().max())
     assert scale > 0 and bool((S >= b.abs() * (1 - 1e-12)).all())
     assert float((a - b).abs().max()) <= 1e-12 * scale, (float((a - b).abs().max()), scale)
+
+
+@pytest.mark.parametrize('name', [c['name'] for c in O.CASES])
+def test_autograd_reference_equals_tap_loop_reference(name):
+    """(a) autograd through oracle/tf_ops.py == (b) shifted slices + einsum, to 1e-12 of the largest value."""
+    _agree(O.BY_NAME[name])
+
+
+@pytest.mark.parametrize('name', [c['name'] for c in O.CASES128])
+def test_autograd_reference_equals_tap_loop_reference_128(name):
+    """The same on the table of the 128 x 128 kernels, its 65 536-pixel case included."""
+    _agree(O.BY_NAME128[name])
+
+
+@pytest.mark.parametrize('name,gt,dt', O.CARRIER_FORMS, ids=['%s-g%s-d%s' % f for f in O.CARRIER_FORMS])
+def test_autograd_reference_equals_tap_loop_reference_carriers(name, gt, dt):
+    """... and on the carrier cases with either side plain or transformed."""
+    _agree(O.carrier(name, gt, dt))
+
+
+def test_tables_do_not_share_inputs():
+    """CASES seeds from its index (1000 + i), CASES128 and the carrier forms from bases of their own."""
+    seeds = [1000 + i for i in range(len(O.CASES))] + [c['seed'] for c in O.CASES128] + \
+            [O.carrier(*f)['seed'] for f in O.CARRIER_FORMS]
+    assert len(set(seeds)) == len(seeds)
+    assert all('seed' not in c for c in O.CASES)
 
 
 def test_padding_lanes_hold_1e3_and_do_not_reach_the_reference():

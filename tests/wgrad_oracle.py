@@ -1,5 +1,6 @@
-"""The float64 reference of the filter-gradient form (conv_wgrad_kernel of csrc/igemm.hip), written twice, and the table of
-cases tests/test_gpu_wgrad_forms.py runs on the device.
+"""The float64 reference of the filter-gradient form (conv_wgrad_kernel of csrc/igemm.hip), written twice, and the tables of
+cases tests/test_gpu_wgrad_forms.py (CASES) and tests/test_gpu_wgrad128_forms.py (CASES128: the 128 x 128 kernels) run on the
+device.
 
     dF[(ty, tx), cg, cd] = sum over pixels (n, py, px) of  act(a*G + b)[n, py*s + oy + ty, px*s + ox + tx][cg] * act(a*D + b)[n, py, px][cd]
 
@@ -74,6 +75,59 @@ BY_NAME = {c['name']: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
 
 
+# --- the 128 x 128 kernels (csrc/wgrad128.hip exact fp32, csrc/wgrad128_bf16.hip bf16x6): tests/test_gpu_wgrad128_forms.py.
+# expect: tpt, the taps per tile ssc_conv_wgrad128_plan must report; bf_only: the exact kernel does not take the launch (the
+# generic one does).  P = NB * PH * PW >= 256, Nn >= 128 and even, two dense sources only with C0 % 128 == 0.
+LRELU = (False, 2, False, -1)
+NORM_RELU = (True, 1, False, -1)
+CASES128 = [
+    # --- both kernels
+    _case('w1_1x1_p256', 'conv', 1, 16, 16, (128, 0, 128), (128, 0, 128), tpt=1),                              # P exactly 256; TW = 1
+    _case('w1_4x4s2_p300', 'conv', 3, 20, 20, (128, 0, 128), (256, 0, 256), k=4, stride=2, pad=1, gt=NORM_LRELU, tpt=1),   # 300 = 9 * 32 + 12
+    _case('w1_two_gathered', 'conv', 2, 12, 12, (128, 128, 256), (128, 0, 128), k=3, stride=1, pad=1, gt=(True, 2, True, 1), tpt=1),
+    _case('w1_nn130', 'conv', 2, 12, 12, (128, 0, 128), (132, 0, 130), k=3, stride=1, pad=1, tpt=1),           # a column tile of 2 columns
+    _case('w1_deconv_two_dense_norm', 'deconv', 2, 12, 12, (128, 0, 128), (128, 128, 256), dt=(True, 1, True, 2), tpt=1),
+    _case('w1_deconv_512_64_plain', 'deconv', 2, 12, 12, (128, 0, 128), (512, 64, 576), tpt=1),                # last column tile half empty
+    _case('w1_odd_s2', 'conv', 2, 33, 23, (128, 0, 128), (128, 0, 128), k=4, stride=2, pad=1, gt=LRELU, tpt=1),
+    _case('w1_same_4x4s1', 'conv', 2, 12, 12, (256, 0, 256), (128, 0, 128), k=4, stride=1, pad='same', gt=NORM_LRELU, tpt=1),  # pad 1 before, 2 after
+    _case('w1_column_image', 'conv', 2, 160, 1, (128, 0, 128), (128, 0, 128), k=3, stride=1, pad=1, tpt=1),    # PW = 1
+    _case('w1_fc', 'conv', 300, 1, 1, (128, 0, 128), (128, 0, 128), dt=NORM_LRELU, tpt=1),                      # PH * PW = 1
+    _case('w1_mm_1000', 'mm', 1, 1, 1000, (128, 0, 128), (256, 0, 256), gt=NORM_LRELU, tpt=1),
+    _case('w1_split', 'conv', 2, 64, 64, (128, 0, 128), (128, 0, 128), k=3, stride=1, pad=1, gt=NORM_LRELU, tpt=1),        # 8192 pixels: split-K
+    _case('w1_split_xcd', 'conv', 2, 64, 64, (128, 0, 128), (128, 0, 128), k=4, stride=2, pad=1, gt=NORM_LRELU, tpt=1),   # 2048 pixels, 16 row
+                                                                                        # tiles: 10 slices of 7 K-tiles, a grid of 160 in XCD order
+    _case('w2_4x4s2', 'conv', 2, 24, 24, (64, 0, 64), (128, 0, 128), k=4, stride=2, pad=1, gt=LRELU, tpt=2),
+    _case('w2_9taps', 'conv', 2, 15, 15, (64, 0, 64), (192, 0, 192), k=3, stride=1, pad=1, gt=NORM_RELU, tpt=2),           # last row tile: ONE tap
+    _case('w2_div64', 'conv', 1, 256, 256, (64, 0, 64), (128, 0, 128), k=3, stride=1, pad=1, tpt=2),           # P * PH * PW = 2^32
+    # --- the bf16 kernel alone: tiles over the padded row space that span two or three taps
+    _case('b2_132_131', 'conv', 2, 12, 12, (132, 0, 131), (128, 0, 128), k=3, stride=1, pad='same', tpt=2, bf_only=True),
+    _case('b2_260_259_norm', 'conv', 2, 12, 12, (260, 0, 259), (256, 0, 256), k=3, stride=1, pad='same', gt=NORM_LRELU, tpt=2, bf_only=True),
+    _case('b2_192', 'conv', 2, 12, 12, (192, 0, 192), (128, 0, 128), k=3, stride=1, pad='same', tpt=2, bf_only=True),
+    _case('b2_1x1_516_515', 'conv', 3, 12, 12, (516, 0, 515), (256, 0, 256), tpt=2, bf_only=True),             # one tap, 4.03 row tiles
+    _case('b3_68_67', 'conv', 2, 12, 12, (68, 0, 67), (128, 0, 128), k=3, stride=1, pad='same', tpt=3, bf_only=True),
+    _case('b3_96', 'conv', 2, 12, 12, (96, 0, 96), (128, 0, 128), k=3, stride=1, pad='same', tpt=3, bf_only=True),
+    _case('b3_124_121', 'conv', 2, 12, 12, (124, 0, 121), (128, 0, 128), k=3, stride=1, pad='same', gt=NORM_LRELU, tpt=3, bf_only=True),
+]
+for _i, _c in enumerate(CASES128):
+    _c['seed'] = 5000 + _i          # a seed base of its own: CASES seeds from its index, and its inputs do not move
+BY_NAME128 = {c['name']: c for c in CASES128}
+assert len(BY_NAME128) == len(CASES128) and not set(BY_NAME128) & set(BY_NAME)
+
+# The full product of forms: one carrier per taps-per-tile, each with the gathered and the dense side plain (P) or transformed (T)
+CARRIERS = ('w1_two_gathered', 'w2_4x4s2', 'b3_96')
+CARRIER_FORMS = [(n, gt, dt) for n in CARRIERS for gt in 'PT' for dt in 'PT']
+
+
+def carrier(name, gt, dt):
+    """The carrier case `name` with its gathered / dense side plain ('P') or transformed ('T'): norm + lrelu, on a second
+    gathered source norm + relu."""
+    base = BY_NAME128[name]
+    two = base['g'][1] > 0
+    c = dict(base, name='%s/g%s_d%s' % (name, gt, dt), gt=((True, 2, True, 1) if two else NORM_LRELU) if gt == 'T' else PLAIN,
+             dt=NORM_LRELU if dt == 'T' else PLAIN, seed=9000 + CARRIER_FORMS.index((name, gt, dt)))
+    return c
+
+
 def geometry(c):
     """NB, gathered H W, lattice PH PW, TH TW, stride, offset of tap 0 (y, x)."""
     n, h, w, k, s = c['n'], c['h'], c['w'], c['k'], c['stride']
@@ -100,7 +154,7 @@ def _rnd(gen, *shape):
 def make_inputs(c):
     """Seeded float32 CPU tensors of a case: g0, g1, d0, d1 NHWC sources (None where C1 == 0) with 1.0e3 in the padding lanes
     (the last lanes of the last source), gab0, gab1, dab0, dab1 folded norms [a; b] (None: no norm)."""
-    gen = torch.Generator().manual_seed(1000 + CASES.index(BY_NAME[c['name']]))
+    gen = torch.Generator().manual_seed(c['seed'] if 'seed' in c else 1000 + CASES.index(BY_NAME[c['name']]))
     geo = geometry(c)
     out = {}
     for side, (H, W) in (('g', (geo['GH'], geo['GW'])), ('d', (geo['PH'], geo['PW']))):
