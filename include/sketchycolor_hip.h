@@ -381,6 +381,26 @@ int ssc_bg_scene_compose_u8(const float* img, int ldc, const uint8_t* fg, const 
  * search_height * W > 8192 (the search rows' colours sit in LDS). */
 int ssc_bg_sky_gradient_u8(const uint8_t* color, const uint8_t* inner, int H, int W, int search_from, int search_height,
                            uint8_t* out, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+/* --- the instances of a user scene (fg_scene.hip; Pipeline_utils/fg_color_utils.py::build_instance_colorization) ---
+ * uint8 images, integer compares and copies only: the same bytes on every run.  Every access is a byte access, so no pointer but
+ * the road test's out needs an alignment.  Returns -1 for sizes out of range or a missing array, -3 for a misaligned out of the
+ * road test; nothing is launched then.
+ * The mask image (:292-296): small_mask uint8 [bh+1, bw+1] (pred_masks[k], row stride bw + 1) -> out uint8 [bh, bw], one channel:
+ * 0 where the mask byte equals 1, 255 for every other value.  The mask's last row and column lie outside the box slice
+ * [y1:y2, x1:x2] and are not read.  (bh + 1) * (bw + 1) <= 2^24.  ssc_resample_u8 with chan = 0 replicates the channel. */
+int ssc_fg_scene_mask_u8(const uint8_t* small_mask, int bh, int bw, uint8_t* out, void* stream);
+/* is_road_not_single_line (:80-134) on the instance sketch uint8 [S,S,3], a grey image.  s = (red byte < 235), which is what the
+ * reference's two binarisation steps leave of a grey image.  A run end of column j: s[i][j] && !s[i+1][j] for i < S-1, and
+ * s[S-1][j]; the column is valid when it has a positive, even number of them; V = valid columns, Hc = valid rows.  out int32 [3]
+ * = {V >= parallel_width || Hc >= parallel_width, V, Hc} in device memory.  One workgroup, integer sums.  1 <= S <= 4096,
+ * parallel_width >= 1 (the reference's default: 25). */
+int ssc_road_parallel_u8(const uint8_t* sketch, int S, int parallel_width, int32_t* out, void* stream);
+/* The paste (:342-345), in place: for i < bh, j < bw, where inner[y1+i][x1+j] == value, result[y1+i][x1+j] = inst[i][j].  result
+ * uint8 [H,W,3], inner uint8 [H,W], inst uint8 [bh,bw,3] contiguous, value = instance index + 1.  Nothing else is written.
+ * -1 as well for a box that leaves the image (y1, x1 < 0, y1 + bh > H, x1 + bw > W), bh < 1, bw < 1, value outside 1..255,
+ * H * W > 2^24. */
+int ssc_fg_scene_paste_u8(uint8_t* result, const uint8_t* inner, int H, int W, const uint8_t* inst, int y1, int x1, int bh, int bw,
+                          int value, void* stream);
 /* PIL.Image.resize of an 8-bit image on the device (resize_and_padding_mask_image, input_pipeline.py:199-239: ANTIALIAS =
  * LANCZOS; reverse_resize_image, Pipeline_utils/fg_color_utils.py:137-160: scipy.misc.imresize = PIL bilinear): Pillow's
  * two-pass 8-bit resampler, horizontal then vertical, bit for bit.  src uint8 [H,W,C]; chan >= 0: only that channel,

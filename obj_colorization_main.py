@@ -13,6 +13,16 @@ inference_results}``, ``log/param_<first iteration>.json`` and the restart-after
     python obj_colorization_main.py --mode train -bt Pix2Pix -bs 32 -rc device -vf 1000   # data/tfrecord/val scored every 1000
     python obj_colorization_main.py --mode inference -rf <timestamp> --infer_name car.png \
         --instruction 'the car is yellow with blue window'
+    python obj_colorization_main.py --mode scene -rf <timestamp> --image_id 77742204 --inst_indices 7,8 \
+        --instruction 'the bus on the left is yellow with blue windows'
+
+--mode scene paints the named instances of one user scene as the reference's scene pipeline does (Pipeline_utils/fg_color_utils.py
+::build_instance_colorization): ``<scene_dir>/sketches/<id>.png``, ``inner_masks/<id>.mat`` and ``seg_data/<id>_datas.npz`` are
+read, the instruction is cut down to 'the <category> is ...', every instance goes through a forward pass of its own and is pasted
+into --previous_image (default: the sketch) on the device (sketchyscenecolorization_amd/fg_scene.py).
+``outputs/<timestamp>/scene_results/<id>/`` receives ``<id>_inst.png`` and ``scene.json``; nothing is written when the call fails.
+The reference's Instance_Matching step is not part of this: the caller names the instances.  bg_colorization_main.py --mode scene
+takes the result as its --previous_image, and the other way round.
 """
 import argparse
 import json
@@ -26,7 +36,7 @@ from sketchyscenecolorization_amd.obj_lib.config import Config
 
 # (long flag, short flag, type, default, choices, Config / d_params key, help)
 FLAGS = [
-    ('mode', 'md', str, 'train', ['train', 'val', 'test', 'inference'], 'dataset_type', 'what to run'),
+    ('mode', 'md', str, 'train', ['train', 'val', 'test', 'inference', 'scene'], 'dataset_type', 'what to run'),
     ('resume_from', 'rf', str, '', None, 'resume_from', 'timestamp of an earlier run under outputs/ to continue or evaluate'),
     ('batch_size', 'bs', int, 2, None, 'batch_size', 'samples per GPU and step'),
     ('max_iter', 'mi', int, 100000, None, 'max_iter_step', 'last training iteration'),
@@ -57,13 +67,25 @@ FLAGS = [
      'pass in log/validation.jsonl; 0 = never'),
     ('val_records', 'vn', int, 0, None, 'val_records', 'held-out records a pass takes, the first N in file order; 0 = all'),
 ]
-RESULT_DIRS = {'val': 'validation_results', 'test': 'test_results', 'inference': 'inference_results'}
+# --mode scene only: (long flag, short flag, type, default, help); not part of the run parameters
+SCENE_FLAGS = [
+    ('scene_dir', 'sd', str, 'examples', 'directory with sketches/, inner_masks/ and seg_data/'),
+    ('scene_size', 'ss', int, 768, 'square size of the scene (the inner mask has it, the sketch is brought to it)'),
+    ('image_id', 'id', str, None, 'the scene, <id> of sketches/<id>.png'),
+    ('inst_indices', 'ii', str, None, "the instances to paint, comma-separated indices into the scene's segmentation data"),
+    ('previous_image', 'pi', str, '', 'the result of the last instruction, a png of the scene size (default: the sketch)'),
+    ('noise_seed', 'ns', int, -1, '-1: noise drawn on the device as inference mode draws it; n >= 0: the p-th instance of the '
+                                  'call gets torch.randn(1, 256, generator=torch.Generator().manual_seed(n + p))'),
+]
+RESULT_DIRS = {'val': 'validation_results', 'test': 'test_results', 'inference': 'inference_results', 'scene': 'scene_results'}
 
 
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     for name, short, typ, default, choices, _key, text in FLAGS:
         parser.add_argument('--' + name, '-' + short, type=typ, default=default, choices=choices, help=text)
+    for name, short, typ, default, text in SCENE_FLAGS:
+        parser.add_argument('--' + name, '-' + short, type=typ, default=default, help='--mode scene: ' + text)
     return parser
 
 
@@ -118,7 +140,7 @@ def start_or_resume_training(params):
     return main_procedure.train(**params), stamp
 
 
-def evaluate(mode, params):
+def evaluate(mode, params, scene=None):
     stamp = params['resume_from']
     if not is_stamp(stamp):
         print('Invalid resume folder')
@@ -126,19 +148,44 @@ def evaluate(mode, params):
     log_dir, ckpt_dir, root = run_dirs(stamp)
     params.update(log_dir=log_dir, ckpt_dir=ckpt_dir, results_dir=os.path.join(root, RESULT_DIRS[mode]))
     Config.set_from_dict(params)
-    print('Launching %s from checkpoint: %s' % ({'val': 'validation', 'test': 'testing', 'inference': 'inference'}[mode],
-                                                 stamp))
+    print('Launching %s from checkpoint: %s' % ({'val': 'validation', 'test': 'testing', 'inference': 'inference',
+                                                 'scene': 'scene colorization'}[mode], stamp))
     if mode == 'val':
         main_procedure.validation(**params)
     elif mode == 'test':
         main_procedure.test()
+    elif mode == 'scene':
+        return main_procedure.scene(params['instruction'], **scene)
     else:
         main_procedure.inference(params['infer_name'], params['instruction'])
+
+
+def scene_arguments(args):
+    """The checked arguments of --mode scene beside the instruction -> what main_procedure.scene takes."""
+    if args.resume_from == '':
+        raise ValueError('--mode scene needs --resume_from <stamp>: the run whose snapshot colours the instances')
+    if args.image_id is None or args.inst_indices is None or args.instruction == '':
+        raise ValueError("--mode scene needs --image_id <id>, --inst_indices <k,k,...> and --instruction '<text>'")
+    try:
+        indices = [int(k) for k in args.inst_indices.split(',')]
+    except ValueError:
+        raise ValueError('--inst_indices %r: comma-separated instance numbers, e.g. 7,8' % args.inst_indices)
+    if not indices or min(indices) < 0:
+        raise ValueError('--inst_indices %r: at least one instance, none negative' % args.inst_indices)
+    if args.scene_size < 1:
+        raise ValueError('--scene_size %d: a scene has at least one pixel' % args.scene_size)
+    return dict(scene_dir=args.scene_dir, scene_size=args.scene_size, image_id=args.image_id, inst_indices=indices,
+                previous_image=args.previous_image, noise_seed=args.noise_seed)
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     params = {key: getattr(args, name) for name, _s, _t, _d, _c, key, _h in FLAGS}
+    if args.mode == 'scene':
+        return evaluate('scene', params, scene_arguments(args))
+    given = [name for name, _s, _t, default, _h in SCENE_FLAGS if getattr(args, name) != default]
+    if given:
+        raise ValueError('--%s belongs to --mode scene, this is --mode %s' % (', --'.join(given), args.mode))
     if args.mode != 'train':
         if args.mode == 'inference':
             assert args.infer_name != '' and args.instruction != '', '--infer_name and --instruction are required'

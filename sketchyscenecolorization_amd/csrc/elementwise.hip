@@ -1067,7 +1067,7 @@ extern "C" int ssc_residual_merge(const float* x1, const float* ab1, const float
 }
 
 // ------------------------------------------------------------------ info
-extern "C" int ssc_version(void) { return 102; }
+extern "C" int ssc_version(void) { return 103; }
 
 // The sha256 prefix of the kernel sources + C-ABI header this binary was compiled from (build.py passes it; a build made by
 // hand without it says so).  The marker string lets build.py read it from the file without loading the library.

@@ -183,6 +183,9 @@ SIGNATURES = {
     'ssc_bg_scene_crop_u8': [_P, _P, _L, _P, _P],
     'ssc_bg_scene_compose_u8': [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P],
     'ssc_bg_sky_gradient_u8': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    'ssc_fg_scene_mask_u8': [_P, _I, _I, _P, _P],
+    'ssc_road_parallel_u8': [_P, _I, _I, _P, _P],
+    'ssc_fg_scene_paste_u8': [_P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P],
     'ssc_image_metrics_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_image_metrics_f32': [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_image_metrics_bg_f32': [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
@@ -1197,6 +1200,45 @@ def bg_sky_gradient_u8(color_u8, inner_u8, search_from=5, search_height=2, out=N
     check(lib().ssc_bg_sky_gradient_u8(ptr(color_u8), ptr(inner_u8), h, w, search_from, search_height, ptr(out), ptr(status),
                                        ptr(ws), ws.numel() * 4, stream_ptr()), 'bg_sky_gradient_u8')
     return out, status, ws[:4].view(torch.int32).clone()
+
+
+def fg_scene_mask_u8(small_mask_u8, out=None):
+    """The instance's mask image: small_mask_u8 uint8 [bh+1, bw+1] (pred_masks[k]) -> uint8 [bh, bw, 1], 0 where the mask byte
+    equals 1 and 255 elsewhere; the mask's last row and column are outside the box and not read."""
+    assert small_mask_u8.dtype == torch.uint8 and small_mask_u8.is_contiguous() and small_mask_u8.dim() == 2
+    bh, bw = small_mask_u8.shape[0] - 1, small_mask_u8.shape[1] - 1
+    assert bh >= 1 and bw >= 1, tuple(small_mask_u8.shape)
+    if out is None:
+        out = torch.empty((bh, bw, 1), dtype=torch.uint8, device=small_mask_u8.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == bh * bw
+    check(lib().ssc_fg_scene_mask_u8(ptr(small_mask_u8), bh, bw, ptr(out), stream_ptr()), 'fg_scene_mask_u8')
+    return out
+
+
+def road_parallel_u8(sketch_u8, parallel_width=25, out=None):
+    """is_road_not_single_line on the grey instance sketch uint8 [S,S,3] -> int32 [3] on the device, unread: {1 when the road
+    has two sides (V >= parallel_width or Hc >= parallel_width), V, Hc}, the columns and rows with a positive, even number of
+    stroke runs."""
+    s = sketch_u8.shape[0]
+    _u8_image(sketch_u8, s, s)
+    if out is None:
+        out = torch.empty(3, dtype=torch.int32, device=sketch_u8.device)
+    assert out.dtype == torch.int32 and out.numel() >= 3 and out.is_contiguous()
+    check(lib().ssc_road_parallel_u8(ptr(sketch_u8), s, int(parallel_width), ptr(out), stream_ptr()), 'road_parallel_u8')
+    return out
+
+
+def fg_scene_paste_u8(result_u8, inner_u8, inst_u8, y1, x1, value):
+    """In place on result_u8 uint8 [H,W,3]: the pixels of inst_u8 uint8 [bh,bw,3], laid at (y1, x1), where inner_u8 uint8 [H,W]
+    equals value (the instance index + 1); nothing else is written."""
+    h, w = inner_u8.shape
+    _u8_image(result_u8, h, w)
+    assert inner_u8.dtype == torch.uint8 and inner_u8.is_contiguous()
+    bh, bw = int(inst_u8.shape[0]), int(inst_u8.shape[1])
+    _u8_image(inst_u8, bh, bw)
+    check(lib().ssc_fg_scene_paste_u8(ptr(result_u8), ptr(inner_u8), h, w, ptr(inst_u8), int(y1), int(x1), bh, bw, int(value),
+                                      stream_ptr()), 'fg_scene_paste_u8')
+    return result_u8
 
 
 METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 / _f32 / _bg_f32 owns (csrc/metrics.hip)

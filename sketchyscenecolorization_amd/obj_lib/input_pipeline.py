@@ -1,6 +1,7 @@
 """Host side of obj_lib/input_pipeline.py: num_classes (:11-15), the paired TFRecord input queue (:43-154, read
-without TensorFlow through sketchyscenecolorization_amd.tfrecord), split_inputs (:184-196) and the sketch
-pre-processing of the inference path (:199-257)."""
+without TensorFlow through sketchyscenecolorization_amd.tfrecord), split_inputs (:184-196), the sketch
+pre-processing of the inference path (:199-257) and the scene pipeline's way back from the generated instance to its box
+(Pipeline_utils/fg_color_utils.py:137-160), each on the host and on the device."""
 import os
 import random
 
@@ -44,6 +45,22 @@ def resize_and_padding_mask_image(image, new_size, resample_method=None, margin_
                     constant_values=255)
     assert canvas.shape == (new_size, new_size)
     return np.repeat(canvas[:, :, None], 3, axis=2)
+
+
+def reverse_resize_image(inst_u8, box_h, box_w, h_w_ratio=1, margin_size=10):
+    """The way back (Pipeline_utils/fg_color_utils.py:137-160) on the host: cut the padding of the generated [S,S,3] instance,
+    bilinear resize (scipy.misc.imresize = PIL) to the box plus margins, cut the margins -> uint8 [box_h, box_w, 3]."""
+    from PIL import Image
+    s = inst_u8.shape[0]
+    bh, bw = box_h + 2 * margin_size, box_w + 2 * margin_size
+    if bh * h_w_ratio > bw:
+        pad = int(round(s * (bh * h_w_ratio - bw) / (bh * h_w_ratio) / 2.))
+        cut = inst_u8[:, pad:s - pad]
+    else:
+        pad = int(round(s * (bw - bh * h_w_ratio) / bw / 2.))
+        cut = inst_u8[pad:s - pad, :]
+    rev = np.array(Image.fromarray(np.ascontiguousarray(cut), 'RGB').resize((bw, bh), resample=Image.BILINEAR), dtype=np.uint8)
+    return rev[margin_size:margin_size + box_h, margin_size:margin_size + box_w]
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -435,6 +435,50 @@ def inference(img_name, instruction):
     print('Saved file %s' % img_out_filename)
 
 
+def scene(instruction, scene_dir, image_id, inst_indices, previous_image='', noise_seed=-1, scene_size=768):
+    """One instruction on the named instances of one user scene -> the directory <id>_inst.png and scene.json went to
+    (Pipeline_utils/fg_color_utils.py::build_instance_colorization; the work is fg_scene.colorize_instances).  Nothing is
+    written when an instance cannot be coloured."""
+    from PIL import Image
+    from .. import fg_scene
+    T = 15
+    img_dim = SIZE[Config.small_img != 0]
+    sc = fg_scene.load_instances(scene_dir, image_id, scene_size)
+    previous = None
+    if previous_image != '':
+        previous = np.array(Image.open(previous_image).convert('RGB'), dtype=np.uint8)
+        if previous.shape[:2] != (scene_size, scene_size):
+            raise ValueError('--previous_image %s is %d x %d, --scene_size is %d'
+                             % (previous_image, previous.shape[0], previous.shape[1], scene_size))
+    vocab_dict = _load_vocab()
+    models.reset_default_graph()
+    store, _ = models.get_store(Config.block_type, Config.vocab_size, img_dim[0])
+    path = latest_checkpoint(Config.ckpt_dir)
+    print('Restore trained model:', path)
+    restore_checkpoint(store, path)
+    tower = models.get_trainer(Config.block_type, Config.vocab_size, img_dim[0])
+    tower.G.lstm_hybrid = bool(Config.LSTM_hybrid != 0)
+    noise = None
+    if noise_seed >= 0:     # CPU generators: the same vectors can be made without the device
+        noise = torch.cat([torch.randn(1, 256, generator=torch.Generator().manual_seed(noise_seed + p))
+                           for p in range(len(inst_indices))])
+    facts = {}
+    result, text = fg_scene.colorize_instances(tower, sc, instruction, inst_indices, previous, vocab=vocab_dict, text_len=T,
+                                               noise=noise, info=facts)
+    print('## segment_user_input_text: ', text)
+    res_dir = os.path.join(Config.results_dir, sc['image_id'])
+    os.makedirs(res_dir, exist_ok=True)
+    _write_png(os.path.join(res_dir, sc['image_id'] + '_inst.png'), result)
+    with open(os.path.join(res_dir, 'scene.json'), 'w') as fp:
+        json.dump({'text': text, 'instances': [i['index'] for i in facts['instances']],
+                   'classes': [i['class'] for i in facts['instances']],
+                   'boxes': [sc['boxes'][i['index']].tolist() for i in facts['instances']],
+                   'roads': [i['road'] for i in facts['instances']]}, fp, sort_keys=True)
+        fp.write('\n')
+    print('Saved file %s' % (sc['image_id'] + '_inst.png'))
+    return res_dir
+
+
 def test():
     """Loop of the inference body over data/captions/<cat>/test.json (main_procedure.py:361-492)."""
     T = 15

@@ -46,7 +46,7 @@ class GanTrainer(object):
             # discrim_targets argument every discriminator requires -- graph_single.py:377-379, 457-459: a TypeError -- and
             # no CLI flag sets Config.sn.)
             raise NotImplementedError('Config.sn = False (gradient-penalty losses + gradient clipping) is not built')
-        self.block_type = block_type
+        self.block_type, self.img = block_type, int(img)
         self.store = ParamStore(block_type, vocab_size, img, device, seed)
         self.bufs = Buffers(device)
         if block_type == 'Pix2Pix':
