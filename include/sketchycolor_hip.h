@@ -260,6 +260,17 @@ int ssc_conv_wgrad_plan(const ssc_wgrad_desc* d, int64_t ws_bytes, int* out4);
  * the bf16 kernel's two LDS stages DB (0 / 1; 0 for the exact kernel)}: seven values, DB is the seventh.  ws_bytes <= 0 stands
  * for a NULL workspace.  Computed by the functions that make the launch. */
 int ssc_conv_wgrad128_plan(const ssc_wgrad_desc* d, int64_t ws_bytes, int* out7);
+/* the launch plan of a forward conv / data gradient / matmul on the bf16x6 kernels (conv_bf_kernel, conv_bfh_kernel of
+ * igemm_bf16.hip; host only, launches nothing): -10 when they do not take the launch (no filter planes, a shape outside the
+ * bf16 form, SSC_ARITH=fp32, or one of the kernels ssc_conv_forward dispatches earlier takes it), ssc_conv_forward's own error
+ * for a descriptor it rejects, else 0 and out10 = {kernel (0 conv_bf_kernel on 32-k stages, 1 conv_bfh_kernel on 16-k stages),
+ * tile configuration (0 128x128, 1 64x128, 2 128x64, 4 64x64), PLAIN (0 / 1), source form (0 two uniform sources, 1 one uniform,
+ * 2 one with a partly empty last chunk: KM), SS (one LDS stage per operand, 0 / 1), korder (0 one tap, 1 tap by tap, 2 the four
+ * parity classes), grid layout (0 3-D grid, 1 1-D XCD order, 2 XCD order with the four phases adjacent, 3 whole tiles + K slices
+ * combined in the launch, 4 split-K slabs + reduce), split-K slabs, whole tiles (layout 3: the tiles one workgroup computes
+ * alone; otherwise all tiles), K slices per remaining tile}: ten values.  ws_bytes <= 0 stands for a NULL workspace.  Computed by
+ * the functions that make the launch. */
+int ssc_conv_bf_plan(const ssc_conv_desc* d, int64_t ws_bytes, int* out10);
 
 /* --- layout (elementwise.hip) --- */
 /* dst[n,hw,coff+c] = src[n,c,hw]; tf.transpose NCHW->NHWC (models_collection.py:381) */

@@ -64,6 +64,8 @@ int ssc_conv_c3x3_forward(const ssc_conv_desc* dp, float* stat, void* stream);
 bool ssc_bf_hk_enabled();       // igemm_bf16.hip
 int ssc_launch_conv_bf(int cfg, bool plain, const ssc_conv_desc& d, int splitk, float* ws, hipStream_t st, long ts_full, int ts_s,
                        int64_t ws_bytes, int xcd);
+int ssc_conv_bf_form(int cfg, bool plain, const ssc_conv_desc& d, int splitk, bool have_ws, long ts_full, int ts_s, int64_t ws_bytes,
+                     int xcd, int* out10);
 int ssc_sk_configure_bf(const unsigned* cfg4);
 
 #define BK 32
@@ -2015,48 +2017,81 @@ extern "C" int ssc_conv_forward_plan(const ssc_conv_desc* dp, int64_t ws_bytes, 
     return 0;
 }
 
-extern "C" int ssc_conv_forward(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, void* stream) {
-    const ssc_conv_desc& d = *dp;
-    hipStream_t st = (hipStream_t)stream;
+// ---- what ssc_conv_forward does with a descriptor: the launch itself and ssc_conv_bf_plan both ask these ----
+static int fwd_desc_error(const ssc_conv_desc& d) {
     if ((d.x.C0 & 3) || (d.x.C1 & 3) || d.Nstore < d.Nn || d.Nstore > d.ldc) return -1;
     if (d.nphase != 1 && d.nphase != 4) return -2;
     if (d.nphase == 4 && (d.TH != 2 || d.TW != 2 || d.KH != 4 || d.KW != 4 || d.kstep != -2 || d.out_stride != 2 ||
                           d.in_stride != 1))
         return -3;
+    return 0;
+}
+// the kernels dispatched in front of the tiled ones, in the order ssc_conv_forward asks them
+enum { FWD_TILED = 0, FWD_HEAD1, FWD_HEAD1_DGRAD, FWD_NARROW, FWD_FEWCHAN, FWD_PW1X1, FWD_C3X3, FWD_S2N16, FWD_TR4_TINY, FWD_FEWCHAN7,
+       FWD_TR4N16 };
+static int fwd_early_kernel(const ssc_conv_desc* dp, bool have_ws, int64_t ws_bytes) {
+    const ssc_conv_desc& d = *dp;
     // the one-output patch head over a 512-channel tensor and its data gradient (head1.hip): streaming kernels
-    if (ws != nullptr && ssc_head1_forward_supported(dp) && (int64_t)d.NB * d.x.H * d.x.W * 16 * 4 <= ws_bytes)
-        return ssc_head1_forward(dp, ws, ws_bytes, stream);
-    if (ssc_head1_dgrad_supported(dp)) return ssc_head1_dgrad(dp, stream);
-    if (ssc_conv_narrow_supported(dp)) {        // <= 4 output channels
-        int csplit = 1;
-        const int rc = ssc_conv_narrow_forward_ws(dp, ws, ws_bytes, stream, &csplit);
-        if (rc != 0 || csplit == 1) return rc;
-        const long out_count = (long)d.NB * d.OH * d.OW * d.ldc;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((out_count + 255) / 256)), dim3(256), 0, st, ws, out_count,
-                           csplit, d.out, out_count, d.ldc, d.Nn, d.Nstore, d.bias, d.epi, d.accumulate);
-        return (int)hipGetLastError();
+    if (have_ws && ssc_head1_forward_supported(dp) && (int64_t)d.NB * d.x.H * d.x.W * 16 * 4 <= ws_bytes) return FWD_HEAD1;
+    if (ssc_head1_dgrad_supported(dp)) return FWD_HEAD1_DGRAD;
+    if (ssc_conv_narrow_supported(dp)) return FWD_NARROW;           // <= 4 output channels
+    if (ssc_conv_fewchan_supported(dp)) return FWD_FEWCHAN;         // 4x4 stride-2 over 4 or 8 input channels
+    if (ssc_conv_pw1x1_supported(dp)) return FWD_PW1X1;             // 1x1 expansion of a bottleneck: K <= 128, streaming kernel
+    if (ssc_conv_c3x3_supported(dp)) return FWD_C3X3;               // 3x3 of a bottleneck at 16 / 32 channels (either filter orientation)
+    if (ssc_conv_s2n16_supported(dp)) return FWD_S2N16;             // 4x4 stride-2 conv 64 -> <= 16 channels: 16-column MFMA, K split over the waves
+    if (ssc_conv_tr4_tiny_supported(dp)) return FWD_TR4_TINY;       // k = 4 stride-2 transposed conv, <= 4 channels in and out: a thread per lattice pixel
+    if (ssc_conv_fewchan7_supported(dp)) return FWD_FEWCHAN7;       // 7x7 stride-2 conv over the (padded) image channels
+    if (ssc_conv_tr4n16_supported(dp)) return FWD_TR4N16;           // k = 4 stride-2 transposed conv 256 -> <= 16 channels: 16-column MFMA, a phase per workgroup
+    return FWD_TILED;
+}
+static bool fwd_bf_plain(const ssc_conv_desc& d) {
+    const bool plain0 = d.x.ab0 == nullptr && d.x.act == SSC_ACT_NONE;
+    const bool plain1 = d.x.C1 == 0 || (d.x.ab1 == nullptr && (d.x.act1 >= 0 ? d.x.act1 : d.x.act) == SSC_ACT_NONE);
+    return plain0 && plain1;
+}
+
+extern "C" int ssc_conv_bf_plan(const ssc_conv_desc* dp, int64_t ws_bytes, int* out10) {
+    // host only: {kernel, tile, PLAIN, source form, SS, korder, grid layout, split-K slabs, whole tiles, K slices per remaining
+    // tile}; ws_bytes <= 0 stands for a NULL workspace
+    const ssc_conv_desc& d = *dp;
+    const bool have_ws = ws_bytes > 0;
+    const int err = fwd_desc_error(d);
+    if (err != 0) return err;
+    if (fwd_early_kernel(dp, have_ws, ws_bytes) != FWD_TILED || !fwd_is_bf(d)) return -10;
+    const Plan p = plan_fwd(d, ws_bytes, have_ws);
+    if (p.cfg < 0) return -4;
+    return ssc_conv_bf_form(p.cfg, fwd_bf_plain(d), d, p.splitk, have_ws, p.ts_full, p.ts_s, ws_bytes, xcd_order(), out10);
+}
+
+extern "C" int ssc_conv_forward(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, void* stream) {
+    const ssc_conv_desc& d = *dp;
+    hipStream_t st = (hipStream_t)stream;
+    const int err = fwd_desc_error(d);
+    if (err != 0) return err;
+    switch (fwd_early_kernel(dp, ws != nullptr, ws_bytes)) {
+        case FWD_HEAD1: return ssc_head1_forward(dp, ws, ws_bytes, stream);
+        case FWD_HEAD1_DGRAD: return ssc_head1_dgrad(dp, stream);
+        case FWD_NARROW: {
+            int csplit = 1;
+            const int rc = ssc_conv_narrow_forward_ws(dp, ws, ws_bytes, stream, &csplit);
+            if (rc != 0 || csplit == 1) return rc;
+            const long out_count = (long)d.NB * d.OH * d.OW * d.ldc;
+            hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((out_count + 255) / 256)), dim3(256), 0, st, ws, out_count,
+                               csplit, d.out, out_count, d.ldc, d.Nn, d.Nstore, d.bias, d.epi, d.accumulate);
+            return (int)hipGetLastError();
+        }
+        case FWD_FEWCHAN: return ssc_conv_fewchan_forward(dp, num_cu(), stream);
+        case FWD_PW1X1: return ssc_conv_pw1x1_forward(dp, d.stat_partial, stream);
+        case FWD_C3X3: return ssc_conv_c3x3_forward(dp, d.stat_partial, stream);
+        case FWD_S2N16: return ssc_conv_s2n16_forward(dp, d.stat_partial, stream);
+        case FWD_TR4_TINY: return ssc_conv_tr4_tiny_forward(dp, d.stat_partial, stream);
+        case FWD_FEWCHAN7: return ssc_conv_fewchan7_forward(dp, d.stat_partial, stream);
+        case FWD_TR4N16: return ssc_conv_tr4n16_forward(dp, d.stat_partial, stream);
+        default: break;
     }
-    if (ssc_conv_fewchan_supported(dp))         // 4x4 stride-2 over 4 or 8 input channels
-        return ssc_conv_fewchan_forward(dp, num_cu(), stream);
-    if (ssc_conv_pw1x1_supported(dp))           // 1x1 expansion of a bottleneck: K <= 128, streaming kernel
-        return ssc_conv_pw1x1_forward(dp, d.stat_partial, stream);
-    if (ssc_conv_c3x3_supported(dp))            // 3x3 of a bottleneck at 16 / 32 channels (either filter orientation)
-        return ssc_conv_c3x3_forward(dp, d.stat_partial, stream);
-    if (ssc_conv_s2n16_supported(dp))           // 4x4 stride-2 conv 64 -> <= 16 channels: 16-column MFMA, K split over the waves
-        return ssc_conv_s2n16_forward(dp, d.stat_partial, stream);
-    if (ssc_conv_tr4_tiny_supported(dp))        // k = 4 stride-2 transposed conv, <= 4 channels in and out: a thread per lattice pixel
-        return ssc_conv_tr4_tiny_forward(dp, d.stat_partial, stream);
-    if (ssc_conv_fewchan7_supported(dp))        // 7x7 stride-2 conv over the (padded) image channels
-        return ssc_conv_fewchan7_forward(dp, d.stat_partial, stream);
-    if (ssc_conv_tr4n16_supported(dp))          // k = 4 stride-2 transposed conv 256 -> <= 16 channels: 16-column MFMA, a phase per workgroup
-        return ssc_conv_tr4n16_forward(dp, d.stat_partial, stream);
     const Plan p = plan_fwd(d, ws_bytes, ws != nullptr);
     if (p.cfg < 0) return -4;
-    if (fwd_is_bf(d)) {
-        const bool plain0 = d.x.ab0 == nullptr && d.x.act == SSC_ACT_NONE;
-        const bool plain1 = d.x.C1 == 0 || (d.x.ab1 == nullptr && (d.x.act1 >= 0 ? d.x.act1 : d.x.act) == SSC_ACT_NONE);
-        return ssc_launch_conv_bf(p.cfg, plain0 && plain1, d, p.splitk, ws, st, p.ts_full, p.ts_s, ws_bytes, xcd_order());
-    }
+    if (fwd_is_bf(d)) return ssc_launch_conv_bf(p.cfg, fwd_bf_plain(d), d, p.splitk, ws, st, p.ts_full, p.ts_s, ws_bytes, xcd_order());
     g_launch_res = FWD_CFGS[p.cfg].res;
     g_launch_ws_bytes = ws_bytes;
     g_launch_ts_full = p.ts_full;

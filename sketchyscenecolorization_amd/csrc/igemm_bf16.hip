@@ -1175,6 +1175,60 @@ static bool bf_tabs(const ssc_conv_desc& d, BfTabs& t) {
     return true;
 }
 
+// ---- the choices of a launch: the launchers below and ssc_conv_bf_plan (igemm.hip, through ssc_conv_bf_form) both ask these ----
+// SSC_BF_DIAG bit 0: no in-launch K slices (plain tiles), bit 1: no XCD-aware order (diagnostics; the 32-k kernel only)
+static int bf_diag() {
+    static int diag = -1;
+    if (diag < 0) {
+        const char* e = ssc_dev_getenv("SSC_BF_DIAG");
+        diag = e != nullptr ? atoi(e) : 0;
+    }
+    return diag;
+}
+// the K-tile order: 2 the four parity classes of a stride-2 walk over an even tap window, 1 tap by tap, 0 a single tap.
+// pinnable: SSC_BF_KORDER=0 / 1 / 2 pins it (A/B; the 32-k kernel only); default: by the launch's geometry
+static int bf_korder(const ssc_conv_desc& d, bool pinnable) {
+    int kord = -1;
+    if (pinnable) {
+        static int env = -2;
+        if (env == -2) {
+            const char* e = ssc_dev_getenv("SSC_BF_KORDER");
+            env = e != nullptr ? atoi(e) : -1;
+        }
+        kord = env;
+    }
+    const bool par_ok = d.in_stride == 2 && (d.TH & 1) == 0 && (d.TW & 1) == 0;
+    int korder = par_ok ? 2 : 1;
+    if (kord >= 0) korder = (kord == 2 && !par_ok) ? 1 : kord;
+    if (d.TH * d.TW == 1) korder = 0;
+    return korder;
+}
+// the grid of a launch.  layout: 0 the 3-D grid (row tiles, column tiles, phases), 1 a 1-D grid in the XCD-aware order, 2 the
+// same with the four phases of a row tile adjacent, 3 whole tiles + K slices combined in the launch, 4 the 3-D grid times split-K
+// slabs + the reduce kernel.  tiles: row tiles x column tiles x phases; wgs: workgroups of a 1-D grid; full, flags: the kernel's
+// ts_full and ts_s arguments; slices: K slices per tile behind the whole ones
+struct BfGrid { int layout; long tiles, wgs, full; int flags, slices; };
+static BfGrid bf_grid(const ssc_conv_desc& d, int BM, int BN, int splitk, bool have_ws, long ts_full, int ts_s, int64_t ws_bytes,
+                      int xcd, int diag) {
+    const long M = (long)d.NB * d.PH * d.PW;
+    const long mt = (M + BM - 1) / BM;
+    const int nt = (d.Nstore + BN - 1) / BN;
+    const long tiles = mt * nt * d.nphase;
+    const int xflag = 0x10000 | ((xcd >= 2 && d.nphase == 4) ? 0x20000 : 0);
+    if (diag & 2) xcd = 0;
+    if (!(diag & 1) && splitk == 1 && have_ws && d.sk_flags != nullptr && ts_s > 1) {        // whole tiles + K slices combined in the launch
+        const long full = ts_full, tail = tiles - full, s = ts_s;
+        if (full >= 0 && tail > 0 && (int64_t)tail * s * BM * BN * 4 <= ws_bytes && tail * s < SSC_SK_FLAG_WORDS - 1 &&
+            full + tail * s < 0x7fffffffL)
+            return {3, tiles, full + tail * s, full, (int)s | ((xcd && (full & 7) == 0) ? xflag : 0), (int)s};
+    }
+    if (splitk == 1 && xcd) {       // whole tiles only, 1-D grid in the XCD-aware order
+        const long full = tiles & ~7L;
+        if (tiles < 0x7fffffffL && full > 0) return {(xflag & 0x20000) ? 2 : 1, tiles, tiles, full, 1 | xflag, 1};
+    }
+    return {splitk > 1 ? 4 : 0, tiles, 0, 0, 0, 1};
+}
+
 template <int WM, int WN, int SM, int SN, bool PLAIN, bool ONE, bool KM = false, bool SS = false>
 static int launch_bf_t(const ssc_conv_desc& d, int splitk, float* ws, hipStream_t st, long ts_full, int ts_s, int64_t ws_bytes,
                        int xcd) {
@@ -1193,40 +1247,17 @@ static int launch_bf_t(const ssc_conv_desc& d, int splitk, float* ws, hipStream_
     }
     BfTabs tab = {nullptr, nullptr, nullptr, nullptr};
     if (!PLAIN && !bf_tabs(d, tab)) return -5;
-    const int xflag = 0x10000 | ((xcd >= 2 && d.nphase == 4) ? 0x20000 : 0);
-    static int diag = -1;       // SSC_BF_DIAG bit 0: no in-launch K slices (plain tiles), bit 1: no XCD-aware order (diagnostics)
-    if (diag < 0) {
-        const char* e = ssc_dev_getenv("SSC_BF_DIAG");
-        diag = e != nullptr ? atoi(e) : 0;
+    const int korder = bf_korder(d, true);
+    const BfGrid g = bf_grid(d, BM, BN, splitk, ws != nullptr, ts_full, ts_s, ws_bytes, xcd, bf_diag());
+    if (g.layout == 3) {            // whole tiles + K slices combined in the launch
+        hipLaunchKernelGGL((conv_bf_kernel<WM, WN, SM, SN, PLAIN, ONE, KM, SS>), dim3((unsigned)g.wgs), dim3(256), lds, st, d, mg,
+                           ws, out_count, 1, (int)g.full, g.flags, d.sk_flags, tab, korder);
+        return (int)hipGetLastError();
     }
-    if (diag & 2) xcd = 0;
-    static int kord = -2;       // SSC_BF_KORDER=0 / 1 / 2 pins the K-tile order (A/B); default: by the launch's geometry
-    if (kord == -2) {
-        const char* e = ssc_dev_getenv("SSC_BF_KORDER");
-        kord = e != nullptr ? atoi(e) : -1;
-    }
-    const bool par_ok = d.in_stride == 2 && (d.TH & 1) == 0 && (d.TW & 1) == 0;
-    int korder = par_ok ? 2 : 1;
-    if (kord >= 0) korder = (kord == 2 && !par_ok) ? 1 : kord;
-    if (d.TH * d.TW == 1) korder = 0;
-    if (!(diag & 1) && splitk == 1 && ws != nullptr && d.sk_flags != nullptr && ts_s > 1) {        // whole tiles + K slices combined in the launch
-        const long tiles = mt * nt * d.nphase;
-        const long full = ts_full, tail = tiles - full, s = ts_s;
-        if (full >= 0 && tail > 0 && (int64_t)tail * s * BM * BN * 4 <= ws_bytes && tail * s < SSC_SK_FLAG_WORDS - 1 &&
-            full + tail * s < 0x7fffffffL) {
-            hipLaunchKernelGGL((conv_bf_kernel<WM, WN, SM, SN, PLAIN, ONE, KM, SS>), dim3((unsigned)(full + tail * s)), dim3(256), lds, st, d, mg,
-                               ws, out_count, 1, (int)full, (int)s | ((xcd && (full & 7) == 0) ? xflag : 0), d.sk_flags, tab, korder);
-            return (int)hipGetLastError();
-        }
-    }
-    if (splitk == 1 && xcd) {       // whole tiles only, 1-D grid in the XCD-aware order
-        const long tiles = mt * nt * d.nphase;
-        const long full = tiles & ~7L;
-        if (tiles < 0x7fffffffL && full > 0) {
-            hipLaunchKernelGGL((conv_bf_kernel<WM, WN, SM, SN, PLAIN, ONE, KM, SS>), dim3((unsigned)tiles), dim3(256), lds, st, d, mg, ws,
-                               out_count, 1, (int)full, 1 | xflag, (unsigned*)nullptr, tab, korder);
-            return (int)hipGetLastError();
-        }
+    if (g.layout == 1 || g.layout == 2) {       // whole tiles only, 1-D grid in the XCD-aware order
+        hipLaunchKernelGGL((conv_bf_kernel<WM, WN, SM, SN, PLAIN, ONE, KM, SS>), dim3((unsigned)g.wgs), dim3(256), lds, st, d, mg, ws,
+                           out_count, 1, (int)g.full, g.flags, (unsigned*)nullptr, tab, korder);
+        return (int)hipGetLastError();
     }
     dim3 grid((unsigned)mt, (unsigned)nt, (unsigned)(d.nphase * splitk));
     hipLaunchKernelGGL((conv_bf_kernel<WM, WN, SM, SN, PLAIN, ONE, KM, SS>), grid, dim3(256), lds, st, d, mg, ws, out_count, splitk, 0, 0,
@@ -1254,28 +1285,17 @@ static int launch_bfh_t(const ssc_conv_desc& d, int splitk, float* ws, hipStream
     }
     BfTabs tab = {nullptr, nullptr, nullptr, nullptr};
     if (!PLAIN && !bf_tabs(d, tab)) return -5;
-    const int xflag = 0x10000 | ((xcd >= 2 && d.nphase == 4) ? 0x20000 : 0);
-    const bool par_ok = d.in_stride == 2 && (d.TH & 1) == 0 && (d.TW & 1) == 0;
-    int korder = par_ok ? 2 : 1;
-    if (d.TH * d.TW == 1) korder = 0;
-    if (splitk == 1 && ws != nullptr && d.sk_flags != nullptr && ts_s > 1) {
-        const long tiles = mt * nt * d.nphase;
-        const long full = ts_full, tail = tiles - full, s = ts_s;
-        if (full >= 0 && tail > 0 && (int64_t)tail * s * BM * BN * 4 <= ws_bytes && tail * s < SSC_SK_FLAG_WORDS - 1 &&
-            full + tail * s < 0x7fffffffL) {
-            hipLaunchKernelGGL((conv_bfh_kernel<WM, WN, PLAIN, ONE, KM>), dim3((unsigned)(full + tail * s)), dim3(256), lds, st, d, mg, ws, out_count,
-                               1, (int)full, (int)s | ((xcd && (full & 7) == 0) ? xflag : 0), d.sk_flags, tab, korder);
-            return (int)hipGetLastError();
-        }
+    const int korder = bf_korder(d, false);
+    const BfGrid g = bf_grid(d, BM, BN, splitk, ws != nullptr, ts_full, ts_s, ws_bytes, xcd, 0);
+    if (g.layout == 3) {
+        hipLaunchKernelGGL((conv_bfh_kernel<WM, WN, PLAIN, ONE, KM>), dim3((unsigned)g.wgs), dim3(256), lds, st, d, mg, ws, out_count,
+                           1, (int)g.full, g.flags, d.sk_flags, tab, korder);
+        return (int)hipGetLastError();
     }
-    if (splitk == 1 && xcd) {
-        const long tiles = mt * nt * d.nphase;
-        const long full = tiles & ~7L;
-        if (tiles < 0x7fffffffL && full > 0) {
-            hipLaunchKernelGGL((conv_bfh_kernel<WM, WN, PLAIN, ONE, KM>), dim3((unsigned)tiles), dim3(256), lds, st, d, mg, ws, out_count, 1,
-                               (int)full, 1 | xflag, (unsigned*)nullptr, tab, korder);
-            return (int)hipGetLastError();
-        }
+    if (g.layout == 1 || g.layout == 2) {
+        hipLaunchKernelGGL((conv_bfh_kernel<WM, WN, PLAIN, ONE, KM>), dim3((unsigned)g.wgs), dim3(256), lds, st, d, mg, ws, out_count, 1,
+                           (int)g.full, g.flags, (unsigned*)nullptr, tab, korder);
+        return (int)hipGetLastError();
     }
     dim3 grid((unsigned)mt, (unsigned)nt, (unsigned)(d.nphase * splitk));
     hipLaunchKernelGGL((conv_bfh_kernel<WM, WN, PLAIN, ONE, KM>), grid, dim3(256), lds, st, d, mg, ws, out_count, splitk, 0, 0, (unsigned*)nullptr,
@@ -1306,11 +1326,12 @@ bool ssc_bf_hk_enabled() {
     return hk_env != 0;
 }
 
-// cfg: 0 = 128x128, 1 = 64x128, 2 = 128x64, 4 = 64x64 (the ids of igemm.hip's tile table)
-int ssc_launch_conv_bf(int cfg, bool plain, const ssc_conv_desc& d, int splitk, float* ws, hipStream_t st, long ts_full, int ts_s,
-                       int64_t ws_bytes, int xcd) {
-    const bool one = d.x.C1 == 0;
-    const bool km = one && (d.x.C0 % BK) != 0;
+// the instantiation of a launch: one source (ONE), its partly empty last chunk masked (KM), one LDS stage per operand (SS: the
+// 64x128 / 128x64 / 64x64 tiles), the 128 x 128 tile on 16-k stages (hk: conv_bfh_kernel), the tile
+struct BfForm { bool one, km, ss, hk; int BM, BN; };
+static bool bf_form(int cfg, const ssc_conv_desc& d, BfForm& f) {
+    f.one = d.x.C1 == 0;
+    f.km = f.one && (d.x.C0 % BK) != 0;
     // one LDS stage per operand (64x128 / 128x64 / 64x64 tiles) when the caller says the launch shares the chip with other streams'
     // launches (ssc_conv_desc.lds_hint); SSC_BF_SS=0 / 1 under SSC_DEV_SWITCHES pins it (A/B)
     static int ss_env = -2;
@@ -1318,7 +1339,39 @@ int ssc_launch_conv_bf(int cfg, bool plain, const ssc_conv_desc& d, int splitk, 
         const char* e = ssc_dev_getenv("SSC_BF_SS");
         ss_env = e != nullptr ? (e[0] == '1' ? 1 : 0) : -1;
     }
-    const bool ss = ss_env >= 0 ? ss_env == 1 : (d.lds_hint & 1) != 0;
+    f.ss = cfg != 0 && (ss_env >= 0 ? ss_env == 1 : (d.lds_hint & 1) != 0);
+    f.hk = cfg == 0 && ssc_bf_hk_enabled();
+    f.BM = (cfg == 0 || cfg == 2) ? 128 : 64;
+    f.BN = (cfg == 0 || cfg == 1) ? 128 : 64;
+    return cfg == 0 || cfg == 1 || cfg == 2 || cfg == 4;
+}
+
+// what ssc_launch_conv_bf makes of the same arguments (host only, launches nothing; igemm.hip: ssc_conv_bf_plan): out10 =
+// {kernel, tile, PLAIN, source form, SS, korder, grid layout, split-K slabs, whole tiles, K slices per remaining tile}
+int ssc_conv_bf_form(int cfg, bool plain, const ssc_conv_desc& d, int splitk, bool have_ws, long ts_full, int ts_s, int64_t ws_bytes,
+                     int xcd, int* out10) {
+    BfForm f;
+    if (!bf_form(cfg, d, f)) return -4;
+    const BfGrid g = bf_grid(d, f.BM, f.BN, splitk, have_ws, ts_full, ts_s, ws_bytes, xcd, f.hk ? 0 : bf_diag());
+    out10[0] = f.hk ? 1 : 0;
+    out10[1] = cfg;
+    out10[2] = plain ? 1 : 0;
+    out10[3] = f.km ? 2 : (f.one ? 1 : 0);
+    out10[4] = f.ss ? 1 : 0;
+    out10[5] = bf_korder(d, !f.hk);
+    out10[6] = g.layout;
+    out10[7] = splitk;
+    out10[8] = (int)(g.layout == 3 ? g.full : g.tiles);
+    out10[9] = g.slices;
+    return 0;
+}
+
+// cfg: 0 = 128x128, 1 = 64x128, 2 = 128x64, 4 = 64x64 (the ids of igemm.hip's tile table)
+int ssc_launch_conv_bf(int cfg, bool plain, const ssc_conv_desc& d, int splitk, float* ws, hipStream_t st, long ts_full, int ts_s,
+                       int64_t ws_bytes, int xcd) {
+    BfForm f;
+    if (!bf_form(cfg, d, f)) return -4;
+    const bool one = f.one, km = f.km, ss = f.ss;
 #define BF_CASE(WM, WN, SM, SN)                                                                                              \
     return ss ? launch_bf_form<WM, WN, SM, SN, true>(plain, one, km, d, splitk, ws, st, ts_full, ts_s, ws_bytes, xcd)         \
               : launch_bf_form<WM, WN, SM, SN, false>(plain, one, km, d, splitk, ws, st, ts_full, ts_s, ws_bytes, xcd)
@@ -1330,7 +1383,7 @@ int ssc_launch_conv_bf(int cfg, bool plain, const ssc_conv_desc& d, int splitk, 
                         : launch_bfh_t<WMV, WNV, false, true>(d, splitk, ws, st, ts_full, ts_s, ws_bytes, xcd))      \
                : (plain ? launch_bfh_t<WMV, WNV, true, false>(d, splitk, ws, st, ts_full, ts_s, ws_bytes, xcd)       \
                         : launch_bfh_t<WMV, WNV, false, false>(d, splitk, ws, st, ts_full, ts_s, ws_bytes, xcd))
-    if (cfg == 0 && ssc_bf_hk_enabled()) {
+    if (f.hk) {
         BFH_CASE(2, 2);
     }
 #undef BFH_CASE

@@ -99,7 +99,7 @@ def check_fp32(test, config, got, ref64, ref32, tol=1e-5, what=''):
 U_FP32 = 2.0 ** -24        # unit roundoff of fp32
 
 
-def check_dot(test, config, got, ref64, S, K, plan=None, what='', extra_terms=0):
+def check_dot(test, config, got, ref64, S, K, plan=None, what='', extra_terms=0, allow=None):
     """An fp32 sum of K products, added up in any order: per element |got - ref64| <= (K + 8) * 2^-24 * S, where S is the float64
     sum of the absolute products of that element.  gamma_K = K*u / (1 - K*u) bounds the rounding of the products and of the K - 1
     additions in whatever order (Higham, Accuracy and Stability of Numerical Algorithms, section 3.1); the 8 more roundings per
@@ -109,13 +109,26 @@ def check_dot(test, config, got, ref64, S, K, plan=None, what='', extra_terms=0)
     Beyond K + 8 = 16384 (up to 2^17) the bound is gamma_(K+8) = (K+8)*u / (1 - (K+8)*u) itself.
     extra_terms: further roundings per term a kernel's arithmetic costs by construction, added to the 8 (the bf16x6 filter
     gradient: 2, its three dropped products, together below 2^-23 |a*b|).
+    K may be a tensor of S's shape: the terms of every element (the forward tests count the non-zero products per element).
+    allow: an absolute allowance per element, added to the bound (tests/test_gpu_fwd_bf16_forms.py: a 1-Lipschitz epilogue
+    activation evaluated to a few ulp, 8 * 2^-24 * |f(ref)|).  Without either the bound is the one above.
     plan: what ssc_conv_wgrad_plan reported for the launch, logged with the worst err / bound ratio."""
     got, ref64, S = _f64(got), _f64(ref64), _f64(S)
     assert got.shape == ref64.shape == S.shape, (test, what, got.shape, ref64.shape, S.shape)
-    n = K + 8 + extra_terms
-    assert extra_terms >= 0 and n <= 2 ** 17, (K, extra_terms)
+    if isinstance(K, torch.Tensor):
+        K = _f64(K)
+        assert K.shape == S.shape and float(K.max()) + 8 + extra_terms <= 16384 and extra_terms >= 0, (test, what, K.shape)
+        bound = (K + 8 + extra_terms) * U_FP32 * S
+        K = int(K.max())
+    else:
+        n = K + 8 + extra_terms
+        assert extra_terms >= 0 and n <= 2 ** 17, (K, extra_terms)
+        bound = (n * U_FP32 if K + 8 <= 16384 else n * U_FP32 / (1.0 - n * U_FP32)) * S
     assert bool(torch.isfinite(got).all()), (test, what, config, 'non-finite output')
-    bound = (n * U_FP32 if K + 8 <= 16384 else n * U_FP32 / (1.0 - n * U_FP32)) * S
+    if allow is not None:
+        allow = _f64(allow)
+        assert allow.shape == S.shape and bool((allow >= 0).all()), (test, what, allow.shape)
+        bound = bound + allow
     err = (got - ref64).abs()
     ratio = torch.where(err > 0, err / torch.clamp(bound, min=1e-300), torch.zeros_like(err))
     k = int(torch.argmax(ratio))
