@@ -730,6 +730,33 @@ int ssc_fc_small_fwd(const float* x, const float* W, const float* b, int N, int 
 int ssc_fc_small_bwd(const float* x, const float* W, const float* dy, int N, int K, int J, float* dx, float* dW,
                      float* db, int accumulate, void* stream);
 
+/* --- instance matcher (matching.hip): Instance_Matching/RMI_model.py in eval mode on deeplab_model.py, and
+ *     Pipeline_utils/fg_matching_utils.py::build_instance_matching; DESIGN.md section 8.6 --- */
+/* src uint8 [H,W,3] -> out float [H,W,4] = (byte - (104.00698793, 116.66876762, 122.67891434), 0), the means taken off the
+ * channels in RGB order as the reference does; stroke uint8 [H,W] = 1 where the first byte is not 255 */
+int ssc_match_preprocess_u8(const uint8_t* src, int H, int W, float* out, uint8_t* stroke, void* stream);
+/* tf.nn.max_pool(3x3, stride 2, SAME) of relu(ab[c]*x + ab[C+c]), NHWC, C % 4 == 0: out [N, ceil(H/2), ceil(W/2), C].  Taps in
+ * the padding do not take part.  ab == NULL: the plain max-pool of x (no relu). */
+int ssc_max_pool3s2(const float* x, const float* ab, int N, int H, int W, int C, float* out, void* stream);
+/* x [N,H,W,C] -> out [N*r*r, H/r, W/r, C]: sub-image n*r*r + i*r + j holds the pixels (y % r == i, x % r == j) of image n;
+ * r = 2 or 4, H and W multiples of r, C % 4 == 0.  A rate-r 3x3 SAME conv of x is the plain 3x3 SAME conv of out. */
+int ssc_space_to_batch(const float* x, int N, int H, int W, int C, int r, float* out, void* stream);
+/* the way back: x [N*r*r, H/r, W/r, C] -> out [N,H,W,C] */
+int ssc_batch_to_space(const float* x, int N, int H, int W, int C, int r, float* out, void* stream);
+/* out[row] = sum_c relu(0.5*(log(1+1e-3+h[row*ldh+c]) - log(1+1e-3-h[row*ldh+c]))) * w[c] + bias[0]: ssc_squash_fwd and the
+ * 1x1 conv to one channel in one pass; one wavefront per row, fixed summation order.  C % 4 == 0, ldh % 4 == 0 */
+int ssc_squash_project(const float* h, int ldh, const float* w, const float* bias, int64_t rows, int C, float* out,
+                       void* stream);
+/* up [S,S] = tf.image.resize_bilinear(pred [h,w], [S,S]) (legacy form, align_corners = False: src = dst * (in / out));
+ * predicts uint8 [S,S] = (up >= 1e-9) && stroke != 0.  S % 4 == 0 */
+int ssc_match_finish(const float* pred, int h, int w, const uint8_t* stroke, int S, float* up, uint8_t* predicts,
+                     void* stream);
+/* out int64 [N,2]: per instance {#(predicts != 0 && mask != 0), sum of the mask's bytes} over its box; boxes int32 [N,4] =
+ * (y1, x1, y2, x2), both ends included; the mask of instance k is masks[offsets[k] ..], (y2-y1+1) x (x2-x1+1) bytes.  A box that
+ * is empty or leaves the S x S image, or a mask that leaves the mask_bytes of the buffer, gives {-1, -1}. */
+int ssc_instance_occupancy(const uint8_t* predicts, int S, const uint8_t* masks, int64_t mask_bytes, const int32_t* boxes,
+                           const int64_t* offsets, int N, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

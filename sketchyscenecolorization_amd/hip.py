@@ -250,6 +250,13 @@ SIGNATURES = {
     'ssc_mru_blend': [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'ssc_fc_small_fwd': [_P, _P, _P, _I, _I, _I, _P, _P],
     'ssc_fc_small_bwd': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P],
+    'ssc_match_preprocess_u8': [_P, _I, _I, _P, _P, _P],
+    'ssc_max_pool3s2': [_P, _P, _I, _I, _I, _I, _P, _P],
+    'ssc_space_to_batch': [_P, _I, _I, _I, _I, _I, _P, _P],
+    'ssc_batch_to_space': [_P, _I, _I, _I, _I, _I, _P, _P],
+    'ssc_squash_project': [_P, _I, _P, _P, _L, _I, _P, _P],
+    'ssc_match_finish': [_P, _I, _I, _P, _I, _P, _P, _P],
+    'ssc_instance_occupancy': [_P, _I, _P, _L, _P, _P, _I, _P, _P],
 }
 
 
@@ -1240,6 +1247,106 @@ def fg_scene_paste_u8(result_u8, inner_u8, inst_u8, y1, x1, value):
     check(lib().ssc_fg_scene_paste_u8(ptr(result_u8), ptr(inner_u8), h, w, ptr(inst_u8), int(y1), int(x1), bh, bw, int(value),
                                       stream_ptr()), 'fg_scene_paste_u8')
     return result_u8
+
+
+# ---------------------------------------------------------------------------
+# instance matcher (csrc/matching.hip; matching.py)
+# ---------------------------------------------------------------------------
+def match_preprocess_u8(sketch_u8, out=None, stroke=None):
+    """sketch uint8 [H,W,3] -> (float [1,H,W,4]: the bytes minus the matcher's channel means, a zero fourth channel;
+    stroke uint8 [H,W]: 1 where the first byte is not 255)."""
+    h, w = int(sketch_u8.shape[0]), int(sketch_u8.shape[1])
+    _u8_image(sketch_u8, h, w)
+    if out is None:
+        out = torch.empty((1, h, w, 4), dtype=torch.float32, device=sketch_u8.device)
+    if stroke is None:
+        stroke = torch.empty((h, w), dtype=torch.uint8, device=sketch_u8.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == h * w * 4
+    assert stroke.dtype == torch.uint8 and stroke.is_contiguous() and stroke.numel() == h * w
+    check(lib().ssc_match_preprocess_u8(ptr(sketch_u8), h, w, ptr(out), ptr(stroke), stream_ptr()), 'match_preprocess_u8')
+    return out, stroke
+
+
+def max_pool3s2(x, ab=None, out=None):
+    """tf.nn.max_pool(3x3, stride 2, SAME) of relu(a*x + b) (ab [2C]; None: of x itself), x float [N,H,W,C] ->
+    [N, ceil(H/2), ceil(W/2), C]."""
+    n, h, w, c = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and (ab is None or (ab.numel() == 2 * c and ab.is_contiguous()))
+    if out is None:
+        out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and tuple(out.shape) == (n, (h + 1) // 2, (w + 1) // 2, c), tuple(out.shape)
+    check(lib().ssc_max_pool3s2(ptr(x), ptr(ab), n, h, w, c, ptr(out), stream_ptr()), 'max_pool3s2')
+    return out
+
+
+def space_to_batch(x, r, out=None):
+    """x float [N,H,W,C] -> [N*r*r, H/r, W/r, C]; sub-image n*r*r + i*r + j holds the pixels (y % r == i, x % r == j)."""
+    n, h, w, c = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and h % r == 0 and w % r == 0, (tuple(x.shape), r)
+    if out is None:
+        out = torch.empty((n * r * r, h // r, w // r, c), dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and tuple(out.shape) == (n * r * r, h // r, w // r, c), tuple(out.shape)
+    check(lib().ssc_space_to_batch(ptr(x), n, h, w, c, r, ptr(out), stream_ptr()), 'space_to_batch')
+    return out
+
+
+def batch_to_space(x, r, out=None):
+    """The inverse of space_to_batch: x float [N*r*r, h, w, C] -> [N, h*r, w*r, C]."""
+    nb, h, w, c = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and nb % (r * r) == 0, (tuple(x.shape), r)
+    n = nb // (r * r)
+    if out is None:
+        out = torch.empty((n, h * r, w * r, c), dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and tuple(out.shape) == (n, h * r, w * r, c), tuple(out.shape)
+    check(lib().ssc_batch_to_space(ptr(x), n, h * r, w * r, c, r, ptr(out), stream_ptr()), 'batch_to_space')
+    return out
+
+
+def squash_project(h, w, bias, C=None, out=None):
+    """out[row] = sum over the first C columns of squash(h[row]) * w + bias[0]; h float [rows, ldh] (the padded state of the
+    multimodal LSTM), w float [>= C], bias float [1]."""
+    rows, ldh = h.shape
+    C = ldh if C is None else int(C)
+    assert h.dtype == torch.float32 and h.is_contiguous() and w.is_contiguous() and w.numel() >= C and bias.numel() >= 1
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=h.device)
+    assert out.is_contiguous() and out.numel() == rows
+    check(lib().ssc_squash_project(ptr(h), ldh, ptr(w), ptr(bias), rows, C, ptr(out), stream_ptr()), 'squash_project')
+    return out
+
+
+def match_finish(pred, stroke_u8, up=None, predicts=None):
+    """pred float [h,w], stroke uint8 [S,S] -> (up float [S,S]: the legacy bilinear upsampling; predicts uint8 [S,S] =
+    (up >= 1e-9) and stroke)."""
+    h, w = pred.shape
+    s = int(stroke_u8.shape[0])
+    assert pred.dtype == torch.float32 and pred.is_contiguous()
+    assert stroke_u8.dtype == torch.uint8 and stroke_u8.is_contiguous() and tuple(stroke_u8.shape) == (s, s)
+    if up is None:
+        up = torch.empty((s, s), dtype=torch.float32, device=pred.device)
+    if predicts is None:
+        predicts = torch.empty((s, s), dtype=torch.uint8, device=pred.device)
+    assert up.is_contiguous() and tuple(up.shape) == (s, s) and predicts.dtype == torch.uint8 and tuple(predicts.shape) == (s, s)
+    check(lib().ssc_match_finish(ptr(pred), h, w, ptr(stroke_u8), s, ptr(up), ptr(predicts), stream_ptr()), 'match_finish')
+    return up, predicts
+
+
+def instance_occupancy(predicts_u8, masks_u8, boxes, offsets, out=None):
+    """predicts uint8 [S,S]; masks_u8: every instance's small mask, one after the other; boxes int32 [N,4] = (y1, x1, y2, x2),
+    both ends included; offsets int64 [N] into masks_u8 -> int64 [N,2] on the device, unread: {pixels of the box where predicts
+    and the mask are both non-zero, sum of the mask's bytes}; {-1, -1} for a box or a mask that leaves its buffer."""
+    s = int(predicts_u8.shape[0])
+    n = int(boxes.shape[0])
+    assert predicts_u8.dtype == torch.uint8 and predicts_u8.is_contiguous() and tuple(predicts_u8.shape) == (s, s)
+    assert masks_u8.dtype == torch.uint8 and masks_u8.is_contiguous() and masks_u8.dim() == 1
+    assert boxes.dtype == torch.int32 and boxes.is_contiguous() and tuple(boxes.shape) == (n, 4)
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() == n
+    if out is None:
+        out = torch.empty((n, 2), dtype=torch.int64, device=predicts_u8.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == 2 * n
+    check(lib().ssc_instance_occupancy(ptr(predicts_u8), s, ptr(masks_u8), masks_u8.numel(), ptr(boxes), ptr(offsets), n, ptr(out),
+                                       stream_ptr()), 'instance_occupancy')
+    return out
 
 
 METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 / _f32 / _bg_f32 owns (csrc/metrics.hip)

@@ -1,0 +1,556 @@
+"""The instance matcher of the scene pipeline, inference only, batch 1 (Pipeline_utils/fg_matching_utils.py::
+build_instance_matching): RMI_model.py in eval mode (fusion_type 'RMI', no attention) on the DeepLab-ResNet backbone of
+deeplab_model.py (is_intermediate, frozen norms), then get_pred_instance_mask's choice of the instances the prediction covers.
+DESIGN.md section 8.6.
+
+    sketch uint8 [S,S,3] --ssc_match_preprocess_u8--> x [1,S,S,4], stroke [S,S]
+    backbone: 7x7 s2 conv, max-pool (ssc_max_pool3s2), bottleneck units [3,4,23,3] -- hip.conv_forward with the producer's frozen
+              norm and relu folded into the consumer's View, ssc_residual_merge at every unit's end.  Groups 4 and 5 (atrous
+              rates 2 and 4) run in the space-to-batch layout, where their 3x3 convs are plain ones: ssc_space_to_batch(2) in
+              front of either group, ssc_batch_to_space(2) twice behind the last unit.
+    head:     1x1 projection + l2 norm, word LSTM, multimodal LSTM per location (hip.lstm_step_fwd on gate blocks padded to a
+              multiple of 32), ssc_squash_project, ssc_match_finish -> up [S,S], predicts [S,S]
+    choice:   ssc_instance_occupancy -> int64 counts; the quotient and the comparison with 0.5 in float64 on the host
+
+Not here: training, the other backbones, attention, post_processing_mask_with_segmentation."""
+import os
+import re
+
+import numpy as np
+
+NORM_EPS = 0.001
+OCCUPIED_THRESH = 0.5
+UNK, PAD = '<unk>', '<pad>'
+_SPLIT = re.compile(r'(\W+)')
+NORM_PARTS = ('beta', 'gamma', 'factor', 'mean', 'variance')
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# host: text, spatial table, folding and padding
+# ---------------------------------------------------------------------------------------------------------------------------
+def load_vocab(path):
+    """One word per line -> {word: line number} (load_vocab_dict_from_file)."""
+    with open(path) as f:
+        words = [w.strip() for w in f.readlines()]
+    return {w: n for n, w in enumerate(words)}
+
+
+def sentence_tokens(text):
+    """The words the matcher reads: split on (\\W+), lower-cased, without blanks and '-', without a final '.'."""
+    words = [w.lower() for w in _SPLIT.split(text.strip()) if len(w.strip()) > 0 and w != '-']
+    if words and words[-1] == '.':
+        words = words[:-1]
+    return words
+
+
+def preprocess_sentence(text, vocab, T=15):
+    """-> (T vocabulary indices, the number of real ones): unknown words become <unk>, a long sentence is cut at T, a short one
+    padded on the right with <pad>.  ValueError for a sentence without a token."""
+    words = sentence_tokens(text)
+    if not words:
+        raise ValueError('%r holds no word for the matcher' % (text,))
+    idx = [vocab[w] if w in vocab else vocab[UNK] for w in words][:T]
+    n = len(idx)
+    return idx + [vocab[PAD]] * (T - n), n
+
+
+def spatial_features(h, w):
+    """generate_spatial_batch for one image: float32 [h,w,8] = (xmin, ymin, xmax, ymax, xctr, yctr, 1/w, 1/h), in [-1, 1]."""
+    out = np.zeros((h, w, 8), dtype=np.float32)
+    for y in range(h):
+        for x in range(w):
+            xmin, xmax = x / w * 2 - 1, (x + 1) / w * 2 - 1
+            ymin, ymax = y / h * 2 - 1, (y + 1) / h * 2 - 1
+            out[y, x, :] = [xmin, ymin, xmax, ymax, (xmin + xmax) / 2, (ymin + ymax) / 2, 1 / w, 1 / h]
+    return out
+
+
+def fold_norm(beta, gamma, factor, mean, variance):
+    """The frozen norm y = (x - mean/factor) * rsqrt(variance/factor + 0.001) * gamma + beta as y = a*x + b: float32 [2C] =
+    [a | b], worked out in float64."""
+    beta, gamma, mean, variance = (np.asarray(v, np.float64).reshape(-1) for v in (beta, gamma, mean, variance))
+    factor = float(np.asarray(factor, np.float64).reshape(-1)[0])
+    a = gamma / np.sqrt(variance / factor + NORM_EPS)
+    return np.concatenate([a, beta - mean / factor * a]).astype(np.float32)
+
+
+def pad32(c):
+    return -(-c // 32) * 32
+
+
+def pad_gate_columns(k, c, cp):
+    """[..., 4c] (gate blocks i, j, f, o) -> [..., 4cp]: every block laid out at the padded width, zeros between."""
+    k = np.asarray(k)
+    out = np.zeros(k.shape[:-1] + (4 * cp,), dtype=k.dtype)
+    for g in range(4):
+        out[..., g * cp:g * cp + c] = k[..., g * c:(g + 1) * c]
+    return out
+
+
+def pad_rows(k, rows):
+    k = np.asarray(k)
+    out = np.zeros((rows,) + k.shape[1:], dtype=k.dtype)
+    out[:k.shape[0]] = k
+    return out
+
+
+def pad_lstm(kernel, bias, n_in, c):
+    """LSTMCell's kernel [n_in + c, 4c] and bias [4c] -> (Kx [n_in, 4cp], Kh [cp, 4cp], bias [4cp]), cp = c rounded up to a
+    multiple of 32.  The padded units see zero gates: c' = c*sigmoid(1) + sigmoid(0)*tanh(0) stays 0 and h' = tanh(0)*sigmoid(0)
+    stays 0, and their zero rows of Kh give nothing to the real units."""
+    kernel, bias = np.asarray(kernel), np.asarray(bias)
+    cp = pad32(c)
+    assert kernel.shape == (n_in + c, 4 * c) and bias.shape == (4 * c,), (kernel.shape, bias.shape, n_in, c)
+    return (pad_gate_columns(kernel[:n_in], c, cp), pad_rows(pad_gate_columns(kernel[n_in:], c, cp), cp),
+            pad_gate_columns(bias, c, cp))
+
+
+class MatchConfig(object):
+    """The sizes of the matcher.  The defaults are the released model; the tests run small ones through the same code."""
+
+    def __init__(self, size=768, units=(3, 4, 23, 3), filters=(64, 256, 512, 1024, 2048), v_emb=1000, w_emb=1000, w_rnn=1000,
+                 m_rnn=500, vocab_size=76, max_len=15):
+        self.size, self.units, self.filters = int(size), tuple(int(u) for u in units), tuple(int(f) for f in filters)
+        self.v_emb, self.w_emb, self.w_rnn, self.m_rnn = int(v_emb), int(w_emb), int(w_rnn), int(m_rnn)
+        self.vocab_size, self.max_len = int(vocab_size), int(max_len)
+        if self.size < 32 or self.size % 32:
+            raise ValueError('size %d: the matcher needs a multiple of 32 (its 1/8 map is cut into 4 x 4 sub-images)' % self.size)
+        if len(self.units) != 4 or min(self.units) < 1 or len(self.filters) != 5:
+            raise ValueError('units %r / filters %r: four groups of at least one unit, five widths' % (self.units, self.filters))
+        for name, c in [('filters[0]', self.filters[0])] + [('filters[%d] / 4' % k, f // 4) for k, f in enumerate(self.filters) if k] + \
+                [('v_emb', self.v_emb), ('w_emb', self.w_emb), ('w_rnn', self.w_rnn), ('m_rnn', self.m_rnn)]:
+            if c < 4 or c % 4:
+                raise ValueError('%s = %d: every channel count must be a multiple of 4' % (name, c))
+        if any(f % 4 for f in self.filters):
+            raise ValueError('filters %r: every channel count must be a multiple of 4' % (self.filters,))
+        if self.vocab_size < 2 or self.max_len < 1:
+            raise ValueError('vocab_size %d, max_len %d' % (self.vocab_size, self.max_len))
+
+    @property
+    def feat(self):
+        return self.size // 8
+
+    def unit_list(self):
+        """[(scope, cin, cout, stride, rate)] of the bottleneck units in order."""
+        out, f = [], self.filters
+        for g, (n, stride, rate) in enumerate(zip(self.units, (1, 2, 1, 1), (1, 1, 2, 4))):
+            for i in range(n):
+                out.append(('ResNet/group_%d_%d' % (g + 2, i), f[g] if i == 0 else f[g + 1], f[g + 1], stride if i == 0 else 1, rate))
+        return out
+
+    def variable_shapes(self):
+        """{checkpoint name: shape} of everything inference reads."""
+        f, s = self.filters, {}
+
+        def norm(scope, c):
+            for p in NORM_PARTS:
+                s[scope + '/' + p] = (1,) if p == 'factor' else (c,)
+        s['ResNet/group_1/conv1/DW'] = (7, 7, 3, f[0])
+        norm('ResNet/group_1/bn_conv1', f[0])
+        for scope, cin, cout, _stride, _rate in self.unit_list():
+            c4 = cout // 4
+            for blk, shape in (('block_1', (1, 1, cin, c4)), ('block_2', (3, 3, c4, c4)), ('block_3', (1, 1, c4, cout))) + \
+                    ((('block_add', (1, 1, cin, cout)),) if cin != cout else ()):
+                s['%s/%s/conv/DW' % (scope, blk)] = shape
+                norm('%s/%s/bn' % (scope, blk), shape[3])
+        h = 'text_sketchyscene/'
+        s[h + 'visual_feat_projection/DW'] = (1, 1, f[4], self.v_emb)
+        s[h + 'visual_feat_projection/biases'] = (self.v_emb,)
+        s[h + 'embedding'] = (self.vocab_size, self.w_emb)
+        s[h + 'wLSTM/lstm_cell/kernel'] = (self.w_emb + self.w_rnn, 4 * self.w_rnn)
+        s[h + 'wLSTM/lstm_cell/bias'] = (4 * self.w_rnn,)
+        s[h + 'mLSTM/lstm_cell/kernel'] = (self.v_emb + self.w_emb + self.w_rnn + 8 + self.m_rnn, 4 * self.m_rnn)
+        s[h + 'mLSTM/lstm_cell/bias'] = (4 * self.m_rnn,)
+        s[h + 'm_lstm_output_projection/DW'] = (1, 1, self.m_rnn, 1)
+        s[h + 'm_lstm_output_projection/biases'] = (1,)
+        return s
+
+
+OLD_CELL_NAMES = {'/lstm_cell/kernel': '/lstm_cell/weights', '/lstm_cell/bias': '/lstm_cell/biases'}
+
+
+def random_variables(config, seed=0):
+    """Float32 variables under the checkpoint names: the reference's initialisers for the weights, and norms that are not the
+    identity (so that a wrong fold shows)."""
+    rng = np.random.RandomState(seed)
+    out = {}
+    for name, shape in config.variable_shapes().items():
+        leaf = name.rsplit('/', 1)[1]
+        n = int(np.prod(shape))
+        if leaf == 'DW' and name.startswith('ResNet/'):
+            v = rng.randn(*shape) * np.sqrt(2.0 / (shape[0] * shape[1] * shape[3]))
+        elif leaf == 'DW':
+            v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[2] + shape[3]))
+        elif leaf == 'kernel':
+            v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[0] + shape[1]))
+        elif leaf == 'embedding':
+            v = rng.uniform(-0.08, 0.08, shape)
+        elif leaf in ('gamma', 'variance'):
+            v = rng.uniform(0.5, 1.5, shape)
+        elif leaf == 'factor':
+            v = rng.uniform(0.8, 1.25, shape)
+        elif leaf in ('beta', 'mean', 'bias', 'biases'):
+            v = rng.randn(n).reshape(shape) * 0.1
+        else:
+            raise AssertionError(name)
+        out[name] = np.ascontiguousarray(v, dtype=np.float32)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the model on the device
+# ---------------------------------------------------------------------------------------------------------------------------
+class MatchModel(object):
+    """Weights in one flat device buffer (registered with hip, so that the bf16 planes of its filters are kept), every
+    intermediate buffer allocated at first use and kept: a forward pass allocates nothing."""
+
+    def __init__(self, config=None, device='cuda'):
+        import torch
+        from . import hip
+        self.cfg = config if config is not None else MatchConfig()
+        self.device = torch.device(device)
+        c = self.cfg
+        self.cw, self.cm = pad32(c.w_rnn), pad32(c.m_rnn)
+        self.host = None            # {checkpoint name: float32 array} of the loaded weights
+        self._layout, n = {}, 0
+        for name, shape in self._device_shapes().items():
+            self._layout[name] = (n, shape)
+            n += -(-int(np.prod(shape)) // 64) * 64         # every tensor starts on a 256-byte boundary
+        self.flat = torch.zeros(n, dtype=torch.float32, device=self.device)
+        self._range = hip.register_param_buffer(self.flat)
+        self.d = {name: self.flat[o:o + int(np.prod(shape))].view(shape) for name, (o, shape) in self._layout.items()}
+        self._bufs = {}
+        self.one = torch.ones(1, dtype=torch.int32, device=self.device)
+        self.loaded = False
+
+    def close(self):
+        from . import hip
+        if self._range is not None:
+            hip.release_param_buffer(self._range)
+            self._range = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _device_shapes(self):
+        """What the kernels read: conv filters as stored, every norm as its [a | b] table, the LSTM kernels cut by input rows
+        and padded by gate blocks, the spatial table."""
+        c, s = self.cfg, {}
+        for name, shape in c.variable_shapes().items():
+            scope, leaf = name.rsplit('/', 1)
+            if name.startswith('ResNet/'):
+                if leaf == 'DW':
+                    s[name] = shape
+                elif leaf == 'gamma':
+                    s[scope] = (2 * shape[0],)
+        cw, cm = self.cw, self.cm
+        s['vproj/w'], s['vproj/b'] = (1, 1, c.filters[4], c.v_emb), (c.v_emb,)
+        s['embedding'] = (c.vocab_size, c.w_emb)
+        s['w/Kx'], s['w/Kh'], s['w/b'] = (c.w_emb, 4 * cw), (cw, 4 * cw), (4 * cw,)
+        s['m/Kv'], s['m/Kw'], s['m/Kl'], s['m/Ks'] = (c.v_emb, 4 * cm), (c.w_emb, 4 * cm), (cw, 4 * cm), (8, 4 * cm)
+        s['m/Kh'], s['m/b'] = (cm, 4 * cm), (4 * cm,)
+        s['proj/w'], s['proj/b'] = (cm,), (1,)
+        s['spatial'] = (c.feat * c.feat, 8)
+        return s
+
+    # ------------------------------------------------------------------ weights
+    def load_dict(self, variables):
+        """Take {checkpoint name: array}: every variable of MatchConfig.variable_shapes (the LSTM cells also under their older
+        names weights / biases); anything else -- optimizer slots, global_step -- is ignored.  ValueError names a variable that
+        is missing or has another shape."""
+        import torch
+        c, host = self.cfg, {}
+        for name, shape in c.variable_shapes().items():
+            src = name
+            if src not in variables:
+                for new, old in OLD_CELL_NAMES.items():
+                    if name.endswith(new) and name[:-len(new)] + old in variables:
+                        src = name[:-len(new)] + old
+            if src not in variables:
+                raise ValueError('the checkpoint has no variable %s' % name)
+            v = np.asarray(variables[src])
+            if tuple(v.shape) != tuple(shape):
+                raise ValueError('variable %s is %s, the model needs %s' % (src, tuple(v.shape), tuple(shape)))
+            host[name] = np.ascontiguousarray(v, dtype=np.float32)
+        dev = {}
+        for name, v in host.items():
+            scope, leaf = name.rsplit('/', 1)
+            if name.startswith('ResNet/'):
+                if leaf == 'DW':
+                    dev[name] = v
+                elif leaf == 'gamma':
+                    dev[scope] = fold_norm(*[host[scope + '/' + p] for p in NORM_PARTS])
+        h = 'text_sketchyscene/'
+        dev['vproj/w'], dev['vproj/b'] = host[h + 'visual_feat_projection/DW'], host[h + 'visual_feat_projection/biases']
+        dev['embedding'] = host[h + 'embedding']
+        dev['w/Kx'], dev['w/Kh'], dev['w/b'] = pad_lstm(host[h + 'wLSTM/lstm_cell/kernel'], host[h + 'wLSTM/lstm_cell/bias'],
+                                                        c.w_emb, c.w_rnn)
+        kx, dev['m/Kh'], dev['m/b'] = pad_lstm(host[h + 'mLSTM/lstm_cell/kernel'], host[h + 'mLSTM/lstm_cell/bias'],
+                                               c.v_emb + c.w_emb + c.w_rnn + 8, c.m_rnn)
+        o = c.v_emb + c.w_emb
+        dev['m/Kv'], dev['m/Kw'] = kx[:c.v_emb], kx[c.v_emb:o]
+        dev['m/Kl'], dev['m/Ks'] = pad_rows(kx[o:o + c.w_rnn], self.cw), kx[o + c.w_rnn:]
+        dev['proj/w'] = pad_rows(host[h + 'm_lstm_output_projection/DW'].reshape(-1), self.cm)
+        dev['proj/b'] = host[h + 'm_lstm_output_projection/biases']
+        dev['spatial'] = spatial_features(c.feat, c.feat).reshape(-1, 8)
+        assert set(dev) == set(self.d), set(dev) ^ set(self.d)
+        for name, v in dev.items():
+            self.d[name].copy_(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).view(self.d[name].shape))
+        self.host, self.loaded = host, True
+
+    def init_random(self, seed=0):
+        self.load_dict(random_variables(self.cfg, seed))
+
+    def load_tf_checkpoint(self, prefix):
+        from . import tf_checkpoint
+        if not tf_checkpoint.is_tf_checkpoint(prefix):
+            raise ValueError('%s.index: no such TensorFlow checkpoint' % prefix)
+        self.load_dict(tf_checkpoint.read_checkpoint(prefix))
+
+    # ------------------------------------------------------------------ buffers
+    def _buf(self, tag, shape, dtype=None, zero=False):
+        import torch
+        key = (tag,) + tuple(shape)
+        b = self._bufs.get(key)
+        if b is None:
+            make = torch.zeros if zero else torch.empty
+            b = self._bufs[key] = make(tuple(shape), dtype=dtype or torch.float32, device=self.device)
+        return b
+
+    # ------------------------------------------------------------------ backbone
+    def unit(self, x, scope, stride, slot=0):
+        """One bottleneck unit on x float [N,H,W,cin] (materialised) -> relu(norm(block_3) + shortcut) [N,H/stride,W/stride,cout].
+        Each raw conv output is read by its consumer through the producer's folded norm and relu."""
+        from . import hip
+        from .hip import ACT_RELU, View
+        d = self.d
+        n, h, w, cin = x.shape
+        oh, ow = -(-h // stride), -(-w // stride)
+        w1, w2, w3 = (d['%s/block_%d/conv/DW' % (scope, k)] for k in (1, 2, 3))
+        c4, cout = w1.shape[3], w3.shape[3]
+        r1 = self._buf('r1', (n, oh, ow, c4))
+        hip.conv_forward(View(x), w1, stride, 0, r1, same=True)
+        r2 = self._buf('r2', (n, oh, ow, c4))
+        hip.conv_forward(View(r1, None, d[scope + '/block_1/bn'], ACT_RELU), w2, 1, 0, r2, same=True)
+        r3 = self._buf('r3', (n, oh, ow, cout))
+        hip.conv_forward(View(r2, None, d[scope + '/block_2/bn'], ACT_RELU), w3, 1, 0, r3, same=True)
+        out = self._buf('out%d' % slot, (n, oh, ow, cout))
+        assert out.data_ptr() != x.data_ptr()
+        wadd = d.get(scope + '/block_add/conv/DW')
+        if wadd is not None:
+            sc = self._buf('sc', (n, oh, ow, cout))
+            hip.conv_forward(View(x), wadd, stride, 0, sc, same=True)
+            hip.call('ssc_residual_merge', r3, d[scope + '/block_3/bn'], sc, d[scope + '/block_add/bn'], ACT_RELU, out,
+                     n * oh * ow, cout)
+        else:
+            assert cin == cout and stride == 1, (scope, cin, cout, stride)
+            hip.call('ssc_residual_merge', r3, d[scope + '/block_3/bn'], x, None, ACT_RELU, out, n * oh * ow, cout)
+        return out
+
+    def regroup(self, x, rate_from, rate_to):
+        """x in the space-to-batch layout of rate_from (1: the image itself) -> the layout of rate_to (2 or 4): one
+        ssc_space_to_batch(2).  Applied to the rate-2 layout it leaves sub-image (n*4 + i1*2 + j1)*4 + i2*2 + j2 with the pixels
+        y % 4 == 2*i2 + i1, x % 4 == 2*j2 + j1: every sub-image is one residue class mod 4, which is all a rate-4 conv asks."""
+        from . import hip
+        assert rate_to == 2 * rate_from, (rate_from, rate_to)
+        n, h, w, c = x.shape
+        return hip.space_to_batch(x, 2, out=self._buf('s2b', (n * 4, h // 2, w // 2, c)))
+
+    def ungroup(self, x, rate):
+        """The way back from ``regroup``: one ssc_batch_to_space(2) per halving of the rate."""
+        from . import hip
+        while rate > 1:
+            nb, h, w, c = x.shape
+            x = hip.batch_to_space(x, 2, out=self._buf('b2s', (nb // 4, h * 2, w * 2, c)))
+            rate //= 2
+        return x
+
+    def backbone(self, x4):
+        """x4 float [1,S,S,4] (ssc_match_preprocess_u8) -> the visual feature [1,S/8,S/8,filters[4]]."""
+        from . import hip
+        from .hip import View
+        c, d = self.cfg, self.d
+        s = c.size
+        r0 = self._buf('conv1', (1, s // 2, s // 2, c.filters[0]))
+        hip.conv_forward(View(x4), d['ResNet/group_1/conv1/DW'], 2, 0, r0, same=True)
+        x = hip.max_pool3s2(r0, d['ResNet/group_1/bn_conv1'], out=self._buf('pool', (1, s // 4, s // 4, c.filters[0])))
+        cur = 1
+        for k, (scope, _cin, _cout, stride, rate) in enumerate(c.unit_list()):
+            while cur < rate:
+                x = self.regroup(x, cur, cur * 2)
+                cur *= 2
+            x = self.unit(x, scope, stride, k & 1)
+        return self.ungroup(x, cur)     # group_last's relu: the last unit's output is one already
+
+    # ------------------------------------------------------------------ head
+    def _lstm_planes(self, tag, rows, C):
+        import torch
+        from . import hip
+        if not hip.lstm_bf(C, 4 * C):
+            return None
+        return self._buf(tag, (2, hip.lstm_hplanes_floats(rows, C)), zero=True)
+
+    def head(self, feat, tok, seq_len):
+        """feat float [1,h,w,filters[4]], tok int32 [T] on the device, seq_len on the host -> pred float [h,w]."""
+        import torch
+        from . import hip
+        from .hip import View
+        c, d = self.cfg, self.d
+        _, fh, fw, _ = feat.shape
+        R, L, cw, cm = fh * fw, int(seq_len), self.cw, self.cm
+        assert 1 <= L <= c.max_len and (fh, fw) == (c.feat, c.feat)
+        one = self.one      # the step mask: every row is live (t < seq_len is decided here, on the host)
+        # visual: projection, l2 norm, and its share (with the spatial table's) of the multimodal gates
+        vp = self._buf('vproj', (1, fh, fw, c.v_emb))
+        hip.conv_forward(View(feat), d['vproj/w'], 1, 0, vp, bias=d['vproj/b'], same=True)
+        vis, vis_ss = self._buf('vis', (R, c.v_emb)), self._buf('vis_ss', (R,))
+        hip.call('ssc_row_l2norm_fwd', vp, c.v_emb, None, R, c.v_emb, vis, vis_ss)
+        gs = self._buf('g_static', (R, 4 * cm))
+        hip.matmul(vis, d['m/Kv'], gs)
+        hip.matmul(d['spatial'], d['m/Ks'], gs, accumulate=True)
+        # words: embedding, the word LSTM over the seq_len real words
+        emb = self._buf('emb', (c.max_len, c.w_emb))
+        hip.call('ssc_embedding_gather', d['embedding'], tok, L, c.w_emb, emb)
+        ew = self._buf('ew', (c.max_len, 4 * cw))
+        hip.matmul(emb[:L], d['w/Kx'], ew[:L], bias=d['w/b'])
+        cs, hs = self._buf('cw', (c.max_len + 1, cw), zero=True), self._buf('hw', (c.max_len + 1, cw), zero=True)
+        acts_w = None if hip.lstm_bf(cw, 4 * cw) else self._buf('acts_w', (1, 4 * cw))
+        hp = self._lstm_planes('hpw', 1, cw)
+        for t in range(L):
+            hip.lstm_step_fwd(hs[t], d['w/Kh'], 4 * cw, ew[t:t + 1], None, 1, one, 1, cs[t], 1, cw, t > 0, cs[t + 1], hs[t + 1], acts_w,
+                              hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
+        lang, lang_ss = self._buf('lang', (c.max_len, cw)), self._buf('lang_ss', (c.max_len,))
+        hip.call('ssc_row_l2norm_fwd', hs[1:], cw, None, L, cw, lang, lang_ss)
+        gt = self._buf('g_t', (c.max_len, 4 * cm))
+        hip.matmul(emb[:L], d['m/Kw'], gt[:L], bias=d['m/b'])
+        hip.matmul(lang[:L], d['m/Kl'], gt[:L], accumulate=True)
+        # multimodal LSTM: every location a row, the word's share of the gates the same for all of them
+        ca, ha = self._buf('ca', (2, R, cm)), self._buf('ha', (2, R, cm))
+        hip.fill(ca[0], 0.0)
+        hip.fill(ha[0], 0.0)
+        acts_m = None if hip.lstm_bf(cm, 4 * cm) else self._buf('acts_m', (R, 4 * cm))
+        hp = self._lstm_planes('hpm', R, cm)
+        for t in range(L):
+            a, b = t & 1, (t + 1) & 1
+            hip.lstm_step_fwd(ha[a], d['m/Kh'], 4 * cm, gs, gt[t:t + 1], R, one, R, ca[a], R, cm, t > 0, ca[b], ha[b], acts_m,
+                              hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
+        pred = hip.squash_project(ha[L & 1], d['proj/w'], d['proj/b'], C=c.m_rnn, out=self._buf('pred', (R,)))
+        return pred.view(fh, fw)
+
+    # ------------------------------------------------------------------ the whole pass
+    def upload(self, sketch_u8, indices, seq_len):
+        """The inputs into their device buffers; -> (sketch uint8 [S,S,3], tok int32 [T], seq_len)."""
+        import torch
+        c = self.cfg
+        if not self.loaded:
+            raise RuntimeError('the matcher has no weights: load_tf_checkpoint or init_random first')
+        sk = sketch_u8 if isinstance(sketch_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sketch_u8))
+        if sk.dtype != torch.uint8 or tuple(sk.shape) != (c.size, c.size, 3):
+            raise ValueError('the sketch is %s %s, the matcher reads uint8 [%d, %d, 3]' % (sk.dtype, tuple(sk.shape), c.size, c.size))
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        seq_len = int(seq_len)
+        if idx.shape[0] != c.max_len or not 1 <= seq_len <= c.max_len:
+            raise ValueError('%d indices with %d real ones: the matcher reads %d, at least one real' % (idx.shape[0], seq_len, c.max_len))
+        if idx.min() < 0 or idx.max() >= c.vocab_size:
+            raise ValueError('word index %d outside the vocabulary of %d' % (int(idx.max() if idx.max() >= c.vocab_size else idx.min()),
+                                                                             c.vocab_size))
+        skd = self._buf('sketch', (c.size, c.size, 3), torch.uint8)
+        skd.copy_(sk)
+        tok = self._buf('tok', (c.max_len,), torch.int32)
+        tok.copy_(torch.from_numpy(idx.astype(np.int32)))
+        return skd, tok, seq_len
+
+    def forward(self, sketch_u8, indices, seq_len):
+        """sketch uint8 [S,S,3] (host or device), the sentence's T indices and its real length ->
+        (up float [S,S], predicts uint8 [S,S]) on the device, in buffers the next call overwrites."""
+        import torch
+        from . import hip
+        c = self.cfg
+        skd, tok, seq_len = self.upload(sketch_u8, indices, seq_len)
+        x4, stroke = hip.match_preprocess_u8(skd, out=self._buf('x4', (1, c.size, c.size, 4)),
+                                             stroke=self._buf('stroke', (c.size, c.size), torch.uint8))
+        pred = self.head(self.backbone(x4), tok, seq_len)
+        return hip.match_finish(pred, stroke, up=self._buf('up', (c.size, c.size)),
+                                predicts=self._buf('predicts', (c.size, c.size), torch.uint8))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the choice of the instances
+# ---------------------------------------------------------------------------------------------------------------------------
+def pack_masks(boxes, masks, size):
+    """-> (uint8 buffer of the small masks one after the other, int64 offsets).  ValueError for a box that is empty or leaves
+    the size x size image and for a mask of another shape than its box (both ends of a box belong to it)."""
+    boxes = np.asarray(boxes, dtype=np.int32).reshape(-1, 4)
+    if len(boxes) != len(masks) or len(boxes) == 0:
+        raise ValueError('%d boxes and %d masks' % (len(boxes), len(masks)))
+    offsets, parts, n = [], [], 0
+    for k, ((y1, x1, y2, x2), m) in enumerate(zip(boxes.tolist(), masks)):
+        m = np.ascontiguousarray(m, dtype=np.uint8)
+        if y1 < 0 or x1 < 0 or y2 < y1 or x2 < x1 or y2 >= size or x2 >= size:
+            raise ValueError('the box (%d, %d, %d, %d) of instance %d is empty or leaves the %d x %d image' % (y1, x1, y2, x2, k, size, size))
+        if m.shape != (y2 - y1 + 1, x2 - x1 + 1):
+            raise ValueError('the mask of instance %d is %s, its box needs %s' % (k, m.shape, (y2 - y1 + 1, x2 - x1 + 1)))
+        offsets.append(n)
+        parts.append(m.reshape(-1))
+        n += m.size
+    return np.concatenate(parts), np.asarray(offsets, dtype=np.int64)
+
+
+def select_instances(counts):
+    """int64 [N,2] = (intersection, sum of the mask's bytes) -> (matched indices in instance order, float64 scores): the
+    quotient in float64, matched where it is above 0.5; an empty mask (0 / 0, nan) is not matched."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, 2)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        scores = counts[:, 0].astype(np.float64) / counts[:, 1].astype(np.float64)
+    return [int(k) for k in np.nonzero(scores > OCCUPIED_THRESH)[0]], scores
+
+
+def _counts(predicts_d, buf, boxes, offsets):
+    import torch
+    from . import hip
+    dev = predicts_d.device
+    counts = hip.instance_occupancy(predicts_d, torch.from_numpy(buf).to(dev),
+                                    torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)).to(dev),
+                                    torch.from_numpy(offsets).to(dev)).cpu().numpy()
+    if (counts < 0).any():
+        raise RuntimeError('ssc_instance_occupancy refused instance %d' % int(np.nonzero(counts[:, 0] < 0)[0][0]))
+    return counts
+
+
+def instance_counts(predicts_d, boxes, masks):
+    """predicts uint8 [S,S] on the device -> int64 [N,2] on the host (ssc_instance_occupancy)."""
+    buf, offsets = pack_masks(boxes, masks, int(predicts_d.shape[0]))
+    return _counts(predicts_d, buf, boxes, offsets)
+
+
+def match_instances(model, scene, text, vocab):
+    """scene: what fg_scene.load_instances returns (sketch, boxes, masks, class_ids) at the model's size ->
+    (matched instance indices, float64 occupancy of every instance, info: tokens, indices, seq_len, counts, up, predicts).
+    A bad sentence or a bad box is refused before any launch."""
+    T = model.cfg.max_len
+    indices, seq_len = preprocess_sentence(text, vocab, T)
+    buf, offsets = pack_masks(scene['boxes'], scene['masks'], model.cfg.size)
+    up, predicts = model.forward(scene['sketch'], indices, seq_len)
+    counts = _counts(predicts, buf, scene['boxes'], offsets)
+    matched, scores = select_instances(counts)
+    info = {'tokens': sentence_tokens(text)[:T], 'indices': list(indices), 'seq_len': seq_len, 'counts': counts,
+            'up': up.cpu().numpy(), 'predicts': predicts.cpu().numpy()}
+    return matched, scores, info
+
+
+def resolve_snapshot(path):
+    """A checkpoint prefix, or a directory with TensorFlow's ``checkpoint`` file -> the prefix.  ValueError when neither."""
+    if os.path.exists(path + '.index'):
+        return path
+    idx = os.path.join(path, 'checkpoint')
+    if os.path.isdir(path) and os.path.exists(idx):
+        with open(idx) as f:
+            line = f.readline()
+        if '"' in line:
+            prefix = os.path.join(path, os.path.basename(line.split('"')[1]))
+            if os.path.exists(prefix + '.index'):
+                return prefix
+    raise ValueError('--snapshot %r: neither a checkpoint prefix (<prefix>.index) nor a directory whose checkpoint file names one' % path)
