@@ -757,6 +757,17 @@ int ssc_match_finish(const float* pred, int h, int w, const uint8_t* stroke, int
 int ssc_instance_occupancy(const uint8_t* predicts, int S, const uint8_t* masks, int64_t mask_bytes, const int32_t* boxes,
                            const int64_t* offsets, int N, int64_t* out, void* stream);
 
+/* --- the matcher's evaluation (match_eval.hip): Instance_Matching/matching_main.py --mode eval; DESIGN.md section 8.7 --- */
+/* out int64 [256]: out[g] = #{p < n : labels[p] == g && (gate == NULL || gate[p] != 0)}.  The entry point zeroes out on the
+ * stream; every workgroup keeps 256 bins in LDS and adds its non-empty ones to out as 64-bit integers: the same bits on every
+ * run.  16-byte loads where the addresses allow them (any alignment of labels and gate is taken), 1 <= n <= 2^24 */
+int ssc_label_hist_u8(const uint8_t* labels, const uint8_t* gate, int64_t n, int64_t* out, void* stream);
+/* out int64 [N,256]: out[k][g] = #{pixels of instance k's box with mask byte != 0 && labels == g}; labels uint8 [S,S]; boxes,
+ * offsets and masks as for ssc_instance_occupancy (both ends of a box included; boxes may overlap).  A box that is empty or
+ * leaves the S x S image, or a mask that leaves the mask_bytes of the buffer, gives a row of -1. */
+int ssc_instance_label_hist(const uint8_t* labels, int S, const uint8_t* masks, int64_t mask_bytes, const int32_t* boxes,
+                            const int64_t* offsets, int N, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,14 @@ build_instance_matching): the RMI matcher's forward pass and the choice by mask 
     python match_main.py --snapshot outputs/match_snapshot --image_id 77742204 --instruction 'the bus on the left is yellow'
 
 prints one line ``matched_inst_indices 7,8`` -- what ``obj_colorization_main.py --mode scene ... --inst_indices`` takes -- and
-writes <results_dir>/<id>/match.json and <id>_match.png (the prediction on the strokes, x 255)."""
+writes <results_dir>/<id>/match.json and <id>_match.png (the prediction on the strokes, x 255).
+
+    python match_main.py --mode eval --snapshot outputs/match_snapshot --dataset val --data_base_dir ../data \
+        --captions_base_dir data --seg_data_dir outputs/inst_segm_output_data
+
+scores the checkpoint on a split as Instance_Matching/matching_main.py --mode eval does (sketchyscenecolorization_amd/
+match_eval.py): it prints precision@{0.5 .. 0.9}, the overall IoU and mask AP@[0.5:0.95], appends that
+block to <eval_result_root>/deeplab_RMI_<split>_result.txt and writes <eval_result_root>/eval_<split>.json."""
 import argparse
 import json
 import os
@@ -21,12 +28,24 @@ FLAGS = [
     ('instruction', str, '', "e.g. 'the bus on the left is yellow'"),
     ('results_dir', str, 'outputs/match_results', 'where <id>/match.json and <id>/<id>_match.png go'),
 ]
+EVAL_FLAGS = [
+    ('data_base_dir', str, '../data', 'eval: the SketchyScene data, with <split>/INSTANCE_GT and <split>/DRAWING_GT'),
+    ('captions_base_dir', str, 'data', 'eval: the directory of sentence_instance_<split>.json'),
+    ('seg_data_dir', str, 'outputs/inst_segm_output_data', 'eval: the instance segmentation output, <split>/seg_data/<id>_datas.npz'),
+    ('max_scenes', int, 0, 'eval: only the first N scenes of the caption file (0: all of them)'),
+    ('augment_seed', int, None, 'eval: add random colour attributes to the captions as training does, drawn from random.Random(K); '
+                                'default: the captions as they are in the file'),
+    ('eval_result_root', str, 'outputs/eval_results', 'eval: where the result block and eval_<split>.json go'),
+]
 
 
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    for name, typ, default, text in FLAGS:
+    for name, typ, default, text in FLAGS + EVAL_FLAGS:
         p.add_argument('--' + name, type=typ, default=default, help=text)
+    p.add_argument('--mode', type=str, default='match', help="'match' (one scene and one instruction) or 'eval' (a split)")
+    p.add_argument('--dataset', type=str, default='val', help="eval: the split, 'val' or 'test'")
+    p.add_argument('--mask_ap', type=int, default=1, help='eval: 1 to compute mask AP, 0 for IoU and precision only')
     return p
 
 
@@ -56,10 +75,87 @@ def checked_arguments(args):
     return config, prefix, vocab
 
 
-def main(argv=None, config=None):
+def checked_eval_arguments(args):
+    """--mode eval: every bad argument and every missing file is a ValueError here, before the weights are read or anything is
+    written.  -> (config, snapshot prefix, vocab, the scenes of the caption file that will be scored)."""
+    from sketchyscenecolorization_amd import match_eval, matching
+    if args.snapshot == '':
+        raise ValueError('--snapshot <directory or checkpoint prefix> is needed: the matcher has no weights of its own')
+    if args.dataset not in ('val', 'test'):
+        raise ValueError("--dataset %r: 'val' or 'test'" % args.dataset)
+    if args.mask_ap not in (0, 1):
+        raise ValueError('--mask_ap %d: 0 or 1' % args.mask_ap)
+    if args.max_scenes < 0:
+        raise ValueError('--max_scenes %d: a count, 0 for every scene' % args.max_scenes)
+    if args.text_len < 1:
+        raise ValueError('--text_len %d: at least one word' % args.text_len)
+    if args.eval_result_root == '':
+        raise ValueError('--eval_result_root is empty')
+    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len)
+    if not os.path.isfile(args.vocab_file):
+        raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
+    vocab = matching.load_vocab(args.vocab_file)
+    if len(vocab) != args.vocab_size or matching.UNK not in vocab or matching.PAD not in vocab:
+        raise ValueError('--vocab_file %r holds %d words, --vocab_size is %d; <unk> and <pad> must be among them'
+                         % (args.vocab_file, len(vocab), args.vocab_size))
+    prefix = matching.resolve_snapshot(args.snapshot)
+    scenes = match_eval.read_captions(args.captions_base_dir, args.dataset)
+    if args.max_scenes:
+        scenes = scenes[:args.max_scenes]
+    if not scenes:
+        raise ValueError('--captions_base_dir %r: no scene in the caption file of %r' % (args.captions_base_dir, args.dataset))
+    for image_id, pairs in scenes:
+        for path in match_eval.ground_truth_paths(args.data_base_dir, args.dataset, image_id) + \
+                (match_eval.seg_data_path(args.seg_data_dir, args.dataset, image_id),):
+            if not os.path.isfile(path):
+                raise ValueError('scene %s: %s: no such file' % (image_id, path))
+        for caption, _idx in pairs:
+            if not matching.sentence_tokens(caption):
+                raise ValueError('scene %s: the caption %r holds no word' % (image_id, caption))
+            if args.augment_seed is not None and match_eval.caption_category(caption)[0] is None:
+                raise ValueError('scene %s: --augment_seed: the caption %r names no category' % (image_id, caption))
+    return config, prefix, vocab, scenes
+
+
+def evaluate(args, config=None, predicts_out=None):
+    """--mode eval.  ``predicts_out``: a path that receives every caption's predicts, uint8 [captions, S, S], as .npy."""
+    cfg, prefix, vocab, scenes = checked_eval_arguments(args)
+    if config is not None:
+        if (config.size, config.vocab_size, config.max_len) != (cfg.size, cfg.vocab_size, cfg.max_len):
+            raise ValueError('the given configuration and --scene_size / --vocab_size / --text_len disagree')
+        cfg = config
+    import random
+    import numpy as np
+    from sketchyscenecolorization_amd import match_eval, matching
+    model = matching.MatchModel(cfg)
+    model.load_tf_checkpoint(prefix)
+    rng = None if args.augment_seed is None else random.Random(args.augment_seed)
+    kept = [] if predicts_out is not None else None
+    totals, records = match_eval.evaluate(model, vocab, scenes, args.data_base_dir, args.dataset, args.seg_data_dir,
+                                          mask_ap=bool(args.mask_ap), rng=rng, keep_predicts=kept, log=print)
+    model.close()
+    block = totals.block(prefix)
+    print(block)
+    os.makedirs(args.eval_result_root, exist_ok=True)
+    with open(os.path.join(args.eval_result_root, 'deeplab_RMI_%s_result.txt' % args.dataset), 'a') as f:
+        f.write(block)
+    record = dict(totals.record(), split=args.dataset, snapshot=prefix, scenes=len(scenes), augment_seed=args.augment_seed,
+                  per_caption=records)
+    with open(os.path.join(args.eval_result_root, 'eval_%s.json' % args.dataset), 'w') as f:
+        json.dump(record, f, indent=1)
+    if predicts_out is not None:
+        np.save(predicts_out, np.stack(kept))
+    return totals
+
+
+def main(argv=None, config=None, predicts_out=None):
     """``config``: a MatchConfig other than the released model's (the tests' small models); its size, vocabulary size and
-    text length must be the flags'."""
+    text length must be the flags'.  ``predicts_out``: --mode eval only, see ``evaluate``."""
     args = build_parser().parse_args(argv)
+    if args.mode == 'eval':
+        return evaluate(args, config, predicts_out)
+    if args.mode != 'match':
+        raise ValueError("--mode %r: 'match' or 'eval'" % args.mode)
     cfg, prefix, vocab = checked_arguments(args)
     if config is not None:
         if (config.size, config.vocab_size, config.max_len) != (cfg.size, cfg.vocab_size, cfg.max_len):

@@ -257,6 +257,8 @@ SIGNATURES = {
     'ssc_squash_project': [_P, _I, _P, _P, _L, _I, _P, _P],
     'ssc_match_finish': [_P, _I, _I, _P, _I, _P, _P, _P],
     'ssc_instance_occupancy': [_P, _I, _P, _L, _P, _P, _I, _P, _P],
+    'ssc_label_hist_u8': [_P, _P, _L, _P, _P],
+    'ssc_instance_label_hist': [_P, _I, _P, _L, _P, _P, _I, _P, _P],
 }
 
 
@@ -1346,6 +1348,40 @@ def instance_occupancy(predicts_u8, masks_u8, boxes, offsets, out=None):
     assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == 2 * n
     check(lib().ssc_instance_occupancy(ptr(predicts_u8), s, ptr(masks_u8), masks_u8.numel(), ptr(boxes), ptr(offsets), n, ptr(out),
                                        stream_ptr()), 'instance_occupancy')
+    return out
+
+
+# ---------------------------------------------------------------------------
+# the matcher's evaluation (csrc/match_eval.hip; match_eval.py)
+# ---------------------------------------------------------------------------
+def label_hist_u8(labels_u8, gate_u8=None, out=None):
+    """labels uint8, any shape; gate uint8 of as many bytes, or None -> int64 [256] on the device, unread:
+    out[g] = the number of pixels with labels == g (and gate != 0).  Integer sums: the same bits on every run."""
+    n = labels_u8.numel()
+    assert labels_u8.dtype == torch.uint8 and labels_u8.is_contiguous() and n >= 1
+    assert gate_u8 is None or (gate_u8.dtype == torch.uint8 and gate_u8.is_contiguous() and gate_u8.numel() == n)
+    if out is None:
+        out = torch.empty(256, dtype=torch.int64, device=labels_u8.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == 256
+    check(lib().ssc_label_hist_u8(ptr(labels_u8), ptr(gate_u8), n, ptr(out), stream_ptr()), 'label_hist_u8')
+    return out
+
+
+def instance_label_hist(labels_u8, masks_u8, boxes, offsets, out=None):
+    """labels uint8 [S,S]; masks_u8, boxes int32 [N,4], offsets int64 [N] as for instance_occupancy -> int64 [N,256] on the device,
+    unread: out[k][g] = the pixels of instance k's box where its mask is non-zero and labels == g; a row of -1 for a box or a
+    mask that leaves its buffer."""
+    s = int(labels_u8.shape[0])
+    n = int(boxes.shape[0])
+    assert labels_u8.dtype == torch.uint8 and labels_u8.is_contiguous() and tuple(labels_u8.shape) == (s, s)
+    assert masks_u8.dtype == torch.uint8 and masks_u8.is_contiguous() and masks_u8.dim() == 1
+    assert boxes.dtype == torch.int32 and boxes.is_contiguous() and tuple(boxes.shape) == (n, 4)
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() == n
+    if out is None:
+        out = torch.empty((n, 256), dtype=torch.int64, device=labels_u8.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == 256 * n
+    check(lib().ssc_instance_label_hist(ptr(labels_u8), s, ptr(masks_u8), masks_u8.numel(), ptr(boxes), ptr(offsets), n, ptr(out),
+                                        stream_ptr()), 'instance_label_hist')
     return out
 
 

@@ -12,6 +12,9 @@ DESIGN.md section 8.6.
               multiple of 32), ssc_squash_project, ssc_match_finish -> up [S,S], predicts [S,S]
     choice:   ssc_instance_occupancy -> int64 counts; the quotient and the comparison with 0.5 in float64 on the host
 
+``features`` and ``predict`` are the pass in two halves -- the backbone once per scene, the head once per caption -- for the
+evaluation on a split (match_eval.py).
+
 Not here: training, the other backbones, attention, post_processing_mask_with_segmentation."""
 import os
 import re
@@ -473,6 +476,47 @@ class MatchModel(object):
         x4, stroke = hip.match_preprocess_u8(skd, out=self._buf('x4', (1, c.size, c.size, 4)),
                                              stroke=self._buf('stroke', (c.size, c.size), torch.uint8))
         pred = self.head(self.backbone(x4), tok, seq_len)
+        return hip.match_finish(pred, stroke, up=self._buf('up', (c.size, c.size)),
+                                predicts=self._buf('predicts', (c.size, c.size), torch.uint8))
+
+    # ------------------------------------------------------------------ the pass in two halves (match_eval.py)
+    def features(self, sketch_u8):
+        """The half of ``forward`` that does not read the sentence: sketch uint8 [S,S,3] (host or device) -> (feat float
+        [1,S/8,S/8,filters[4]], stroke uint8 [S,S]), both in buffers of their own that only the next ``features`` overwrites --
+        no ``head``, ``predict`` or ``forward`` call touches them."""
+        import torch
+        from . import hip
+        c = self.cfg
+        if not self.loaded:
+            raise RuntimeError('the matcher has no weights: load_tf_checkpoint or init_random first')
+        sk = sketch_u8 if isinstance(sketch_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sketch_u8))
+        if sk.dtype != torch.uint8 or tuple(sk.shape) != (c.size, c.size, 3):
+            raise ValueError('the sketch is %s %s, the matcher reads uint8 [%d, %d, 3]' % (sk.dtype, tuple(sk.shape), c.size, c.size))
+        skd = self._buf('sketch', (c.size, c.size, 3), torch.uint8)
+        skd.copy_(sk)
+        x4, _ = hip.match_preprocess_u8(skd, out=self._buf('x4', (1, c.size, c.size, 4)),
+                                        stroke=self._buf('stroke_kept', (c.size, c.size), torch.uint8))
+        feat = self.backbone(x4)
+        kept = self._buf('feat_kept', tuple(feat.shape))
+        kept.copy_(feat)
+        return kept, self._buf('stroke_kept', (c.size, c.size), torch.uint8)
+
+    def predict(self, feat, stroke, indices, seq_len):
+        """The other half: what ``features`` returned, the sentence's T indices and its real length -> (up float [S,S],
+        predicts uint8 [S,S]) in the buffers ``forward`` fills, with the bits ``forward`` gives for that sketch and sentence."""
+        import torch
+        from . import hip
+        c = self.cfg
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        seq_len = int(seq_len)
+        if idx.shape[0] != c.max_len or not 1 <= seq_len <= c.max_len:
+            raise ValueError('%d indices with %d real ones: the matcher reads %d, at least one real' % (idx.shape[0], seq_len, c.max_len))
+        if idx.min() < 0 or idx.max() >= c.vocab_size:
+            raise ValueError('word index %d outside the vocabulary of %d' % (int(idx.max() if idx.max() >= c.vocab_size else idx.min()),
+                                                                             c.vocab_size))
+        tok = self._buf('tok', (c.max_len,), torch.int32)
+        tok.copy_(torch.from_numpy(idx.astype(np.int32)))
+        pred = self.head(feat, tok, seq_len)
         return hip.match_finish(pred, stroke, up=self._buf('up', (c.size, c.size)),
                                 predicts=self._buf('predicts', (c.size, c.size), torch.uint8))
 
