@@ -768,6 +768,22 @@ int ssc_label_hist_u8(const uint8_t* labels, const uint8_t* gate, int64_t n, int
 int ssc_instance_label_hist(const uint8_t* labels, int S, const uint8_t* masks, int64_t mask_bytes, const int32_t* boxes,
                             const int64_t* offsets, int N, int64_t* out, void* stream);
 
+/* --- training the matcher's fusion head (match_train.hip): RMI_model.py::train_op, utils/loss.py; DESIGN.md section 8.8 --- */
+/* The class loss on the up-sampled logits and its gradient on the head's map.  pred float [h,w]; S = k*h = k*w; up = the legacy
+ * bilinear up-sampling ssc_match_finish computes; a pixel p is live when sketch[3p] <= 104 (sketch uint8 [S,S,3]); its target is
+ * z = lut[labels[p]] != 0 (labels uint8 [S,S], lut uint8 [256]).  loss_acc += sum over the live pixels of max(u,0) - u*z +
+ * log1p(exp(-|u|)) (fp32 terms, added in double); live[0] = their number; dpred[i][j] = sum over the live pixels of
+ * (sigmoid(u) - z) * (the weight of pred[i][j] in that pixel's interpolation).  A gather, one workgroup per cell; fixed-order sums,
+ * the same bits on every run.  ws: 16 bytes per cell of pred.  -1 for sizes that do not fit or too small a workspace */
+int ssc_match_loss_grad(const float* pred, int h, int w, const uint8_t* sketch, const uint8_t* labels, const uint8_t* lut, int S,
+                        double* loss_acc, int64_t* live, float* dpred, float* ws, int64_t ws_bytes, void* stream);
+/* The backward of ssc_squash_project: with s = 0.5*(log(1.001+v) - log(1.001-v)), v = hh[r*ldh+c]:
+ * dh[r][c] = s > 0 ? dpred[r]*w[c]*0.5*(1/(1.001+v) + 1/(1.001-v)) : 0 (columns C .. ldh-1: 0); dw[c] = sum_r dpred[r]*max(s,0);
+ * db[0] = sum_r dpred[r].  The sums in two stages of a fixed order through ws: ceil(rows / max(16, ceil(rows / 64))) * (C + 1)
+ * floats.  C % 4 == 0, ldh % 4 == 0 */
+int ssc_squash_project_bwd(const float* hh, int ldh, const float* w, const float* dpred, int64_t rows, int C, float* dh, float* dw,
+                           float* db, float* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

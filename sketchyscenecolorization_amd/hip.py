@@ -259,6 +259,8 @@ SIGNATURES = {
     'ssc_instance_occupancy': [_P, _I, _P, _L, _P, _P, _I, _P, _P],
     'ssc_label_hist_u8': [_P, _P, _L, _P, _P],
     'ssc_instance_label_hist': [_P, _I, _P, _L, _P, _P, _I, _P, _P],
+    'ssc_match_loss_grad': [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P],
+    'ssc_squash_project_bwd': [_P, _I, _P, _P, _L, _I, _P, _P, _P, _P, _L, _P],
 }
 
 
@@ -1383,6 +1385,64 @@ def instance_label_hist(labels_u8, masks_u8, boxes, offsets, out=None):
     check(lib().ssc_instance_label_hist(ptr(labels_u8), s, ptr(masks_u8), masks_u8.numel(), ptr(boxes), ptr(offsets), n, ptr(out),
                                         stream_ptr()), 'instance_label_hist')
     return out
+
+
+# ---------------------------------------------------------------------------
+# training the matcher's fusion head (csrc/match_train.hip; match_train.py)
+# ---------------------------------------------------------------------------
+def match_loss_grad_workspace_bytes(h, w):
+    """What ssc_match_loss_grad needs: a double and an int64 per cell of pred."""
+    return 16 * int(h) * int(w)
+
+
+def match_loss_grad(pred, sketch_u8, labels_u8, lut_u8, loss_acc, live=None, dpred=None, ws=None):
+    """pred float [h,w]; sketch uint8 [S,S,3], labels uint8 [S,S], lut uint8 [256]; loss_acc a double device scalar that the
+    kernel adds into -> (dpred float [h,w], live int64 [1]): the summed sigmoid cross entropy of the up-sampled logits over the
+    pixels whose first sketch byte is <= 104, against lut[labels] != 0, and its gradient on pred."""
+    h, w = pred.shape
+    s = int(labels_u8.shape[0])
+    assert pred.dtype == torch.float32 and pred.is_contiguous()
+    assert sketch_u8.dtype == torch.uint8 and sketch_u8.is_contiguous() and tuple(sketch_u8.shape) == (s, s, 3)
+    assert labels_u8.dtype == torch.uint8 and labels_u8.is_contiguous() and tuple(labels_u8.shape) == (s, s)
+    assert lut_u8.dtype == torch.uint8 and lut_u8.is_contiguous() and lut_u8.numel() == 256
+    assert loss_acc.dtype == torch.float64 and loss_acc.numel() >= 1
+    if live is None:
+        live = torch.empty(1, dtype=torch.int64, device=pred.device)
+    if dpred is None:
+        dpred = torch.empty((h, w), dtype=torch.float32, device=pred.device)
+    assert live.dtype == torch.int64 and dpred.is_contiguous() and dpred.numel() == h * w
+    if ws is None:
+        ws = workspace()
+    check(lib().ssc_match_loss_grad(ptr(pred), h, w, ptr(sketch_u8), ptr(labels_u8), ptr(lut_u8), s, ptr(loss_acc), ptr(live),
+                                    ptr(dpred), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()), 'match_loss_grad')
+    return dpred, live
+
+
+def squash_project_bwd_workspace_bytes(rows, C):
+    """What ssc_squash_project_bwd needs: C + 1 floats per row group (at most 64 groups of at least 16 rows)."""
+    grp = max(16, -(-int(rows) // 64))
+    return -(-int(rows) // grp) * (int(C) + 1) * 4
+
+
+def squash_project_bwd(h, w, dpred, C=None, dh=None, dw=None, db=None, ws=None):
+    """The backward of squash_project: h float [rows, ldh], w float [>= C], dpred float [rows] -> (dh [rows, ldh] with zero pad
+    columns, dw [C] written into the first C entries of ``dw``, db [1])."""
+    rows, ldh = h.shape
+    C = ldh if C is None else int(C)
+    assert h.dtype == torch.float32 and h.is_contiguous() and w.is_contiguous() and w.numel() >= C
+    assert dpred.is_contiguous() and dpred.numel() == rows
+    if dh is None:
+        dh = torch.empty((rows, ldh), dtype=torch.float32, device=h.device)
+    if dw is None:
+        dw = torch.empty(C, dtype=torch.float32, device=h.device)
+    if db is None:
+        db = torch.empty(1, dtype=torch.float32, device=h.device)
+    assert dh.is_contiguous() and tuple(dh.shape) == (rows, ldh) and dw.is_contiguous() and dw.numel() >= C and db.numel() >= 1
+    if ws is None:
+        ws = workspace()
+    check(lib().ssc_squash_project_bwd(ptr(h), ldh, ptr(w), ptr(dpred), rows, C, ptr(dh), ptr(dw), ptr(db), ptr(ws),
+                                       ws.numel() * ws.element_size(), stream_ptr()), 'squash_project_bwd')
+    return dh, dw, db
 
 
 METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 / _f32 / _bg_f32 owns (csrc/metrics.hip)

@@ -1,0 +1,489 @@
+"""Training the matcher's fusion head (Instance_Matching/matching_main.py::train, RMI_model.py::train_op with
+train_fusion_var_only, utils/loss.py): the DeepLab backbone stays frozen, the text_sketchyscene/* head -- the visual projection,
+the embedding, the word LSTM, the multimodal LSTM and the output projection -- learns.  DESIGN.md section 8.8.
+
+    per iteration  MatchModel.features (frozen backbone) -> head_train (the arithmetic of MatchModel.head, every step's state kept)
+                   -> ssc_match_loss_grad (summed sigmoid cross entropy of the up-sampled logits over the stroke pixels, its
+                   gradient on the 1/8 map) -> backward (ssc_squash_project_bwd, BPTT of both cells on the caption branch's
+                   kernels) -> ssc_l2_reg on the two DW -> ssc_adam_tf per tensor (gradient x 2 on the two biases) ->
+                   hip.refresh_splits
+
+The trained parameters are the head's entries of MatchModel.flat, in the device layout (LSTM kernels cut by input rows and padded
+by gate blocks); the gradient and the two Adam slots are buffers of that layout.  A padded entry has a zero gradient by
+construction and Adam leaves a zero with zero moments at zero.
+
+Not here: training the backbone, training_ignore_bg = False, the other backbones, attention, dropout, summaries, batches, several
+devices, a captured step."""
+import json
+import os
+import random
+
+import numpy as np
+
+from . import matching
+
+HEAD = 'text_sketchyscene/'
+BETA1, BETA2, EPSILON = 0.9, 0.999, 1e-8
+MODEL_NAME = 'deeplab_RMI'
+LIVE_MAX_BYTE = 104         # im[..., 0] < 0 with mu_0 = 104.00698793
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# host: names, schedule, initialisation, layout
+# ---------------------------------------------------------------------------------------------------------------------------
+def head_variable_names(config):
+    """The trained variables under their checkpoint names, in variable_shapes' order."""
+    return [n for n in config.variable_shapes() if n.startswith(HEAD)]
+
+
+def is_regularized(name):
+    """loss.py::l2_regularization_loss: the trained variables whose name contains 'DW'."""
+    return 'DW' in name
+
+
+def grad_scale(name):
+    """RMI_model.py::train_op: the gradient of a variable whose name contains 'biases' is doubled before Adam.  Under the
+    checkpoint names lstm_cell/bias the LSTM biases are not among them."""
+    return 2.0 if 'biases' in name else 1.0
+
+
+def polynomial_decay(step, start_lr=2.5e-4, end_lr=1e-5, decay_steps=75000, power=0.9):
+    """tf.train.polynomial_decay without cycle, in float64."""
+    s = min(float(step), float(decay_steps))
+    return (float(start_lr) - float(end_lr)) * (1.0 - s / float(decay_steps)) ** float(power) + float(end_lr)
+
+
+def adam_step_size(lr, t):
+    """lr_t of tf.train.AdamOptimizer for its t-th update (t >= 1)."""
+    return float(lr) * np.sqrt(1.0 - BETA2 ** t) / (1.0 - BETA1 ** t)
+
+
+def init_head(config, seed=0):
+    """{checkpoint name: float32 array} of a fresh head, the reference's initialisers drawn from numpy.random.RandomState(seed):
+    Xavier-uniform for the two DW, uniform +-0.08 for the embedding, Glorot-uniform for the LSTM kernels, zero biases.  (TF's
+    own random streams are not reproduced.)"""
+    rng = np.random.RandomState(seed)
+    out = {}
+    shapes = config.variable_shapes()
+    for name in head_variable_names(config):
+        shape = shapes[name]
+        leaf = name.rsplit('/', 1)[1]
+        if leaf == 'DW':
+            v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[2] + shape[3]))
+        elif leaf == 'kernel':
+            v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[0] + shape[1]))
+        elif leaf == 'embedding':
+            v = rng.uniform(-0.08, 0.08, shape)
+        else:
+            v = np.zeros(shape)
+        out[name] = np.ascontiguousarray(v, dtype=np.float32)
+    return out
+
+
+def unpad_gate_columns(k, c, cp):
+    """The inverse of matching.pad_gate_columns: [..., 4cp] -> [..., 4c]."""
+    k = np.asarray(k)
+    return np.concatenate([k[..., g * cp:g * cp + c] for g in range(4)], axis=-1)
+
+
+def pack_head(config, host):
+    """{checkpoint name: array} of the head -> {device name: float32 array}, as MatchModel.load_dict lays them out."""
+    c = config
+    cw, cm = matching.pad32(c.w_rnn), matching.pad32(c.m_rnn)
+    dev = {'vproj/w': host[HEAD + 'visual_feat_projection/DW'], 'vproj/b': host[HEAD + 'visual_feat_projection/biases'],
+           'embedding': host[HEAD + 'embedding']}
+    dev['w/Kx'], dev['w/Kh'], dev['w/b'] = matching.pad_lstm(host[HEAD + 'wLSTM/lstm_cell/kernel'], host[HEAD + 'wLSTM/lstm_cell/bias'],
+                                                           c.w_emb, c.w_rnn)
+    kx, dev['m/Kh'], dev['m/b'] = matching.pad_lstm(host[HEAD + 'mLSTM/lstm_cell/kernel'], host[HEAD + 'mLSTM/lstm_cell/bias'],
+                                                  c.v_emb + c.w_emb + c.w_rnn + 8, c.m_rnn)
+    o = c.v_emb + c.w_emb
+    dev['m/Kv'], dev['m/Kw'] = kx[:c.v_emb], kx[c.v_emb:o]
+    dev['m/Kl'], dev['m/Ks'] = matching.pad_rows(kx[o:o + c.w_rnn], cw), kx[o + c.w_rnn:]
+    dev['proj/w'] = matching.pad_rows(np.asarray(host[HEAD + 'm_lstm_output_projection/DW']).reshape(-1), cm)
+    dev['proj/b'] = host[HEAD + 'm_lstm_output_projection/biases']
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in dev.items()}
+
+
+def unpack_head(config, dev):
+    """The inverse of ``pack_head``: pad_lstm, pad_rows and the cut of the multimodal kernel's rows undone."""
+    c = config
+    cw, cm = matching.pad32(c.w_rnn), matching.pad32(c.m_rnn)
+    d = {k: np.asarray(v, dtype=np.float32) for k, v in dev.items()}
+    out = {HEAD + 'visual_feat_projection/DW': d['vproj/w'].reshape(1, 1, c.filters[4], c.v_emb),
+           HEAD + 'visual_feat_projection/biases': d['vproj/b'].reshape(c.v_emb),
+           HEAD + 'embedding': d['embedding'].reshape(c.vocab_size, c.w_emb)}
+    out[HEAD + 'wLSTM/lstm_cell/kernel'] = np.concatenate(
+        [unpad_gate_columns(d['w/Kx'], c.w_rnn, cw), unpad_gate_columns(d['w/Kh'][:c.w_rnn], c.w_rnn, cw)], axis=0)
+    out[HEAD + 'wLSTM/lstm_cell/bias'] = unpad_gate_columns(d['w/b'], c.w_rnn, cw)
+    out[HEAD + 'mLSTM/lstm_cell/kernel'] = np.concatenate(
+        [unpad_gate_columns(k, c.m_rnn, cm) for k in (d['m/Kv'], d['m/Kw'], d['m/Kl'][:c.w_rnn], d['m/Ks'], d['m/Kh'][:c.m_rnn])], axis=0)
+    out[HEAD + 'mLSTM/lstm_cell/bias'] = unpad_gate_columns(d['m/b'], c.m_rnn, cm)
+    out[HEAD + 'm_lstm_output_projection/DW'] = d['proj/w'][:c.m_rnn].reshape(1, 1, c.m_rnn, 1)
+    out[HEAD + 'm_lstm_output_projection/biases'] = d['proj/b'].reshape(1)
+    return {k: np.array(v, dtype=np.float32, order='C', copy=True) for k, v in out.items()}
+
+
+# device name -> the checkpoint variable whose name decides its regulariser and its gradient scale
+DEVICE_TO_VARIABLE = {
+    'vproj/w': 'visual_feat_projection/DW', 'vproj/b': 'visual_feat_projection/biases', 'embedding': 'embedding',
+    'w/Kx': 'wLSTM/lstm_cell/kernel', 'w/Kh': 'wLSTM/lstm_cell/kernel', 'w/b': 'wLSTM/lstm_cell/bias',
+    'm/Kv': 'mLSTM/lstm_cell/kernel', 'm/Kw': 'mLSTM/lstm_cell/kernel', 'm/Kl': 'mLSTM/lstm_cell/kernel',
+    'm/Ks': 'mLSTM/lstm_cell/kernel', 'm/Kh': 'mLSTM/lstm_cell/kernel', 'm/b': 'mLSTM/lstm_cell/bias',
+    'proj/w': 'm_lstm_output_projection/DW', 'proj/b': 'm_lstm_output_projection/biases',
+}
+HEAD_DEVICE_NAMES = tuple(DEVICE_TO_VARIABLE)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the order of the training tuples
+# ---------------------------------------------------------------------------------------------------------------------------
+def training_tuples(scenes):
+    """match_eval.read_captions' list -> [(image id, caption, inst_indices)] in the file's order."""
+    return [(image_id, caption, list(idx)) for image_id, pairs in scenes for caption, idx in pairs]
+
+
+class TupleCursor(object):
+    """The reference's walk over its tuples: an index list shuffled by ``rng`` every time the cursor wraps to 0, one tuple per
+    iteration.  ``state`` / ``restore`` carry the cursor, the shuffled order and the generator over a snapshot."""
+
+    def __init__(self, n, rng):
+        if n < 1:
+            raise ValueError('no training tuple')
+        self.n, self.rng, self.cursor, self.order = int(n), rng, -1, list(range(int(n)))
+
+    def next(self):
+        self.cursor = (self.cursor + 1) % self.n
+        if self.cursor == 0:
+            self.rng.shuffle(self.order)
+        return self.order[self.cursor]
+
+    def state(self):
+        version, internal, gauss = self.rng.getstate()
+        return {'cursor': self.cursor, 'order': list(self.order), 'rng': [version, list(internal), gauss]}
+
+    def restore(self, state):
+        if len(state['order']) != self.n:
+            raise ValueError('the saved order holds %d tuples, the caption file %d' % (len(state['order']), self.n))
+        self.cursor, self.order = int(state['cursor']), [int(i) for i in state['order']]
+        version, internal, gauss = state['rng']
+        self.rng.setstate((version, tuple(internal), gauss))
+
+
+def caption_lut(labels_of_caption):
+    """The labels of a caption's instances (match_eval.caption_labels) -> uint8 [256]: 1 at every label of the target."""
+    lut = np.zeros(256, dtype=np.uint8)
+    lut[np.asarray(sorted(set(int(g) for g in labels_of_caption)), dtype=np.int64)] = 1
+    return lut
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the trainer on the device
+# ---------------------------------------------------------------------------------------------------------------------------
+class MatchTrainer(object):
+    """Wraps a loaded MatchModel.  ``g``, ``m`` and ``v`` are views into the gradient buffer and the two Adam slot buffers by the
+    device names of the head."""
+
+    def __init__(self, model, weight_decay=5e-4):
+        import torch
+        if not model.loaded:
+            raise RuntimeError('the matcher has no weights: load_tf_checkpoint, load_dict or init_random first')
+        self.model, self.cfg = model, model.cfg
+        self.weight_decay = float(weight_decay)
+        lay = model._layout
+        assert [n for n in lay if n in DEVICE_TO_VARIABLE] == list(HEAD_DEVICE_NAMES), list(lay)
+        self.lo, self.hi = lay[HEAD_DEVICE_NAMES[0]][0], lay['spatial'][0]
+        # the head is one stretch of the flat buffer: every trained tensor in it, nothing else
+        inside = [n for n, (o, _s) in lay.items() if self.lo <= o < self.hi]
+        assert inside == list(HEAD_DEVICE_NAMES), inside
+        self.params = model.flat[self.lo:self.hi]
+        self.grad, self.adam_m, self.adam_v = (torch.zeros(self.hi - self.lo, dtype=torch.float32, device=model.device) for _ in range(3))
+        self.spans = {}
+        for k, name in enumerate(HEAD_DEVICE_NAMES):
+            o, shape = lay[name]
+            end = lay[HEAD_DEVICE_NAMES[k + 1]][0] if k + 1 < len(HEAD_DEVICE_NAMES) else self.hi
+            self.spans[name] = (o - self.lo, int(np.prod(shape)), end - o, shape)          # offset, real size, padded size
+        self.g, self.m, self.v = ({n: buf[o:o + size].view(shape) for n, (o, size, _p, shape) in self.spans.items()}
+                                  for buf in (self.grad, self.adam_m, self.adam_v))
+        self.step_count = 0
+        self._loss = torch.zeros(2, dtype=torch.float64, device=model.device)
+        self._live = torch.zeros(2, dtype=torch.int64, device=model.device)
+        self._loss_host, self._loss_event = None, [None, None]
+        self._ctx = None
+
+    # ------------------------------------------------------------------ forward
+    def head_train(self, feat, tok, seq_len):
+        """The arithmetic of MatchModel.head -- the same launches on the same operands, so ``pred`` has its bits -- with the cell
+        state, the output and the activated gates of every step of both cells kept for ``backward``."""
+        from . import hip
+        from .hip import View
+        mdl, c, d = self.model, self.cfg, self.model.d
+        buf = mdl._buf
+        _, fh, fw, _ = feat.shape
+        R, L, cw, cm = fh * fw, int(seq_len), mdl.cw, mdl.cm
+        assert 1 <= L <= c.max_len and (fh, fw) == (c.feat, c.feat)
+        one = mdl.one
+        vp = buf('vproj', (1, fh, fw, c.v_emb))
+        hip.conv_forward(View(feat), d['vproj/w'], 1, 0, vp, bias=d['vproj/b'], same=True)
+        vis, vis_ss = buf('vis', (R, c.v_emb)), buf('vis_ss', (R,))
+        hip.call('ssc_row_l2norm_fwd', vp, c.v_emb, None, R, c.v_emb, vis, vis_ss)
+        gs = buf('g_static', (R, 4 * cm))
+        hip.matmul(vis, d['m/Kv'], gs)
+        hip.matmul(d['spatial'], d['m/Ks'], gs, accumulate=True)
+        emb = buf('emb', (c.max_len, c.w_emb))
+        hip.call('ssc_embedding_gather', d['embedding'], tok, L, c.w_emb, emb)
+        ew = buf('ew', (c.max_len, 4 * cw))
+        hip.matmul(emb[:L], d['w/Kx'], ew[:L], bias=d['w/b'])
+        cs, hs = buf('cw', (c.max_len + 1, cw), zero=True), buf('hw', (c.max_len + 1, cw), zero=True)
+        acts_w = buf('t_acts_w', (c.max_len, 4 * cw))
+        hp = mdl._lstm_planes('hpw', 1, cw)
+        for t in range(L):
+            hip.lstm_step_fwd(hs[t], d['w/Kh'], 4 * cw, ew[t:t + 1], None, 1, one, 1, cs[t], 1, cw, t > 0, cs[t + 1], hs[t + 1],
+                              acts_w[t:t + 1], hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1],
+                              hp_out=None if hp is None else hp[t & 1])
+        lang, lang_ss = buf('lang', (c.max_len, cw)), buf('lang_ss', (c.max_len,))
+        hip.call('ssc_row_l2norm_fwd', hs[1:], cw, None, L, cw, lang, lang_ss)
+        gt = buf('g_t', (c.max_len, 4 * cm))
+        hip.matmul(emb[:L], d['m/Kw'], gt[:L], bias=d['m/b'])
+        hip.matmul(lang[:L], d['m/Kl'], gt[:L], accumulate=True)
+        # state 0 of the multimodal cell is zero and nobody writes it: the steps store the states 1 .. L
+        ca, ha = buf('t_ca', (c.max_len + 1, R, cm), zero=True), buf('t_ha', (c.max_len + 1, R, cm), zero=True)
+        acts_m = buf('t_acts_m', (c.max_len, R, 4 * cm))
+        hp = mdl._lstm_planes('hpm', R, cm)
+        for t in range(L):
+            hip.lstm_step_fwd(ha[t], d['m/Kh'], 4 * cm, gs, gt[t:t + 1], R, one, R, ca[t], R, cm, t > 0, ca[t + 1], ha[t + 1], acts_m[t],
+                              hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
+        pred = hip.squash_project(ha[L], d['proj/w'], d['proj/b'], C=c.m_rnn, out=buf('t_pred', (R,)))
+        self._ctx = dict(feat=feat, tok=tok, L=L, R=R, fh=fh, fw=fw, vis=vis, vis_ss=vis_ss, emb=emb, cs=cs, hs=hs, acts_w=acts_w,
+                         lang=lang, lang_ss=lang_ss, ca=ca, ha=ha, acts_m=acts_m)
+        return pred.view(fh, fw)
+
+    # ------------------------------------------------------------------ backward
+    def backward(self, dpred):
+        """dpred float [h,w]: the gradient on ``head_train``'s pred.  Fills the gradient of every trained tensor (device layout);
+        nothing goes into the backbone."""
+        import torch
+        from . import hip
+        from .hip import View
+        mdl, c, d, g, x = self.model, self.cfg, self.model.d, self.g, self._ctx
+        if x is None:
+            raise RuntimeError('backward without a head_train before it')
+        buf = mdl._buf
+        L, R, cw, cm = x['L'], x['R'], mdl.cw, mdl.cm
+        G4 = 4 * cm
+        one = mdl.one
+        ca, ha, acts_m = x['ca'], x['ha'], x['acts_m']
+        ws = hip.workspace()
+        # 1. the projection and the squash
+        dh, dh2 = buf('b_dh0', (R, cm)), buf('b_dh1', (R, cm))
+        dc, dc2 = buf('b_dc0', (R, cm)), buf('b_dc1', (R, cm))
+        hip.squash_project_bwd(ha[L], d['proj/w'], dpred.reshape(-1), C=c.m_rnn, dh=dh, dw=g['proj/w'], db=g['proj/b'], ws=ws)
+        # 2. the multimodal cell back through its steps: the gate gradients of every step are kept, their sum is the gradient of
+        #    the step-invariant share of the gates
+        dg_all, dgs = buf('b_dg_all', (c.max_len, R, G4)), buf('b_dgs', (R, G4))
+        hip.fill(dc, 0.0)
+        hip.fill(dgs, 0.0)
+        for t in range(L - 1, -1, -1):
+            hip.call('ssc_lstm_pointwise_bwd', dh, dc, acts_m[t], ca[t], ca[t + 1], one, R, R, cm, dg_all[t], dc2, dh2, dgs)
+            if t > 0:       # h_0 = 0: nothing upstream of it
+                hip.matmul_nt(dg_all[t], d['m/Kh'], dh2, accumulate=True)
+            dh, dh2 = dh2, dh
+            dc, dc2 = dc2, dc
+        # 3. its filter gradients, batched over the steps
+        if L > 1:
+            hip.matmul_tn(ha[1:L].reshape((L - 1) * R, cm), dg_all[1:L].reshape((L - 1) * R, G4), g['m/Kh'])
+        else:
+            hip.fill(g['m/Kh'], 0.0)
+        hip.matmul_tn(x['vis'], dgs, g['m/Kv'])
+        hip.matmul_tn(d['spatial'], dgs, g['m/Ks'])
+        # 4. the words' share of the gates: one row per step
+        dr = buf('b_dr', (c.max_len, G4))
+        hip.call('ssc_group_rowsum', dg_all, G4, L, R, G4, dr, 0)
+        hip.call('ssc_group_rowsum', dr, G4, 1, L, G4, g['m/b'], 0)
+        emb, lang = x['emb'], x['lang']
+        hip.matmul_tn(emb[:L], dr[:L], g['m/Kw'])
+        hip.matmul_tn(lang[:L], dr[:L], g['m/Kl'])
+        demb, dlang = buf('b_demb', (c.max_len, c.w_emb)), buf('b_dlang', (c.max_len, cw))
+        hip.matmul_nt(dr[:L], d['m/Kw'], demb[:L])
+        hip.matmul_nt(dr[:L], d['m/Kl'], dlang[:L])
+        dhw = buf('b_dhw', (c.max_len, cw))
+        hip.call('ssc_row_l2norm_bwd', lang, x['lang_ss'], dlang, L, cw, dhw, 0)
+        # 5. the word cell back through its steps, then the embedding
+        cs, hs, acts_w = x['cs'], x['hs'], x['acts_w']
+        dew = buf('b_dew', (c.max_len, 4 * cw))
+        wh, wh2, wc, wc2 = (buf('b_w%d' % k, (1, cw)) for k in range(4))
+        hip.fill(wh, 0.0)
+        hip.fill(wc, 0.0)
+        for t in range(L - 1, -1, -1):
+            hip.call('ssc_axpy', wh, dhw[t:t + 1], 1.0, cw)
+            hip.call('ssc_lstm_pointwise_bwd', wh, wc, acts_w[t:t + 1], cs[t:t + 1], cs[t + 1:t + 2], one, 1, 1, cw, dew[t:t + 1], wc2,
+                     wh2, None)
+            if t > 0:
+                hip.matmul_nt(dew[t:t + 1], d['w/Kh'], wh2, accumulate=True)
+            wh, wh2 = wh2, wh
+            wc, wc2 = wc2, wc
+        if L > 1:
+            hip.matmul_tn(hs[1:L], dew[1:L], g['w/Kh'])
+        else:
+            hip.fill(g['w/Kh'], 0.0)
+        hip.matmul_tn(emb[:L], dew[:L], g['w/Kx'])
+        hip.matmul_nt(dew[:L], d['w/Kx'], demb[:L], accumulate=True)
+        hip.call('ssc_group_rowsum', dew, 4 * cw, 1, L, 4 * cw, g['w/b'], 0)
+        hip.fill(g['embedding'], 0.0)
+        hip.call('ssc_embedding_scatter_add', g['embedding'], c.vocab_size, x['tok'], L, c.w_emb, demb)
+        # 6. the visual branch, down to the projection's filter
+        dvis, dvp = buf('b_dvis', (R, c.v_emb)), buf('b_dvp', (R, c.v_emb))
+        hip.matmul_nt(dgs, d['m/Kv'], dvis)
+        hip.call('ssc_row_l2norm_bwd', x['vis'], x['vis_ss'], dvis, R, c.v_emb, dvp, 0)
+        hip.conv_wgrad(View(x['feat']), View(dvp.view(1, x['fh'], x['fw'], c.v_emb)), g['vproj/w'], 1, 0)
+        hip.join_wgrad()
+        hip.call('ssc_group_rowsum', dvp, c.v_emb, 1, R, c.v_emb, g['vproj/b'], 0)
+
+    # ------------------------------------------------------------------ loss, optimiser
+    def loss_and_grad(self, pred, sketch_d, labels_d, lut_d, slot=0):
+        """-> dpred float [h,w]; the class loss is added into the double of ``slot`` (zeroed here), the live count stored."""
+        from . import hip
+        fh, fw = pred.shape
+        self._loss[slot:slot + 1].zero_()
+        dpred = self.model._buf('t_dpred', (fh, fw))
+        hip.match_loss_grad(pred, sketch_d, labels_d, lut_d, self._loss[slot:slot + 1], live=self._live[slot:slot + 1], dpred=dpred,
+                            ws=hip.workspace())
+        return dpred
+
+    def apply(self, lr):
+        """The regulariser's gradient on the two DW, then TF's Adam on every trained tensor with the gradient of the two biases
+        doubled, then the bf16 planes of the changed filters."""
+        from . import hip
+        self.step_count += 1
+        lr_t = adam_step_size(lr, self.step_count)
+        for name, (o, size, padded, _shape) in self.spans.items():
+            if is_regularized(DEVICE_TO_VARIABLE[name]) and self.weight_decay != 0.0:
+                hip.call('ssc_l2_reg', self.params[o:o + size], size, self.weight_decay, None, self.grad[o:o + size])
+        for name, (o, _size, padded, _shape) in self.spans.items():
+            hip.call('ssc_adam_tf', self.params[o:o + padded], self.grad[o:o + padded], self.adam_m[o:o + padded],
+                     self.adam_v[o:o + padded], padded, lr_t, None, BETA1, BETA2, EPSILON, grad_scale(DEVICE_TO_VARIABLE[name]))
+        hip.refresh_splits(self.params)
+
+    def upload_scene(self, labels_u8):
+        """The scene's label map uint8 [S,S] into its device buffer (once per scene)."""
+        import torch
+        c = self.cfg
+        labels = np.ascontiguousarray(labels_u8, dtype=np.uint8)
+        if labels.shape != (c.size, c.size):
+            raise ValueError('the label map is %s, the matcher trains on [%d, %d]' % (labels.shape, c.size, c.size))
+        d = self.model._buf('t_labels', (c.size, c.size), torch.uint8)
+        d.copy_(torch.from_numpy(labels))
+        return d
+
+    def step(self, scene, lut, tok, seq_len, lr):
+        """scene: {'sketch': uint8 [S,S,3], 'labels': uint8 [S,S]} (host arrays, or a dict ``upload_scene`` has been applied to:
+        'labels_d'); lut uint8 [256]; tok the sentence's max_len indices; seq_len its real length; lr the step's learning rate.
+        One iteration.  -> the class loss of the PREVIOUS step (None at the first): the value is read one step late, the step
+        itself never waits for the device.  ``last_loss`` reads the current one on demand."""
+        import torch
+        c, mdl = self.cfg, self.model
+        idx = np.asarray(tok, dtype=np.int64).reshape(-1)
+        seq_len = int(seq_len)
+        if idx.shape[0] != c.max_len or not 1 <= seq_len <= c.max_len:
+            raise ValueError('%d indices with %d real ones: the matcher reads %d, at least one real' % (idx.shape[0], seq_len, c.max_len))
+        if idx.min() < 0 or idx.max() >= c.vocab_size:
+            raise ValueError('a word index outside the vocabulary of %d' % c.vocab_size)
+        lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1)
+        if lut.shape[0] != 256:
+            raise ValueError('the lut holds %d bytes, not 256' % lut.shape[0])
+        prev = self._take_loss((self.step_count + 1) & 1)
+        slot = self.step_count & 1
+        feat, _stroke = mdl.features(scene['sketch'])
+        sketch_d = mdl._buf('sketch', (c.size, c.size, 3), torch.uint8)
+        labels_d = scene['labels_d'] if 'labels_d' in scene else self.upload_scene(scene['labels'])
+        tok_d = mdl._buf('tok', (c.max_len,), torch.int32)
+        tok_d.copy_(torch.from_numpy(idx.astype(np.int32)))
+        lut_d = mdl._buf('t_lut', (256,), torch.uint8)
+        lut_d.copy_(torch.from_numpy(lut))
+        pred = self.head_train(feat, tok_d, seq_len)
+        dpred = self.loss_and_grad(pred, sketch_d, labels_d, lut_d, slot)
+        if self._loss_host is None:
+            self._loss_host = torch.zeros(2, dtype=torch.float64).pin_memory()
+        self._loss_host[slot:slot + 1].copy_(self._loss[slot:slot + 1], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._loss_event[slot] = ev
+        self.backward(dpred)
+        self.apply(lr)
+        return prev
+
+    def _take_loss(self, slot):
+        ev = self._loss_event[slot]
+        if ev is None:
+            return None
+        ev.synchronize()
+        return float(self._loss_host[slot])
+
+    def last_loss(self):
+        """The class loss of the latest step (waits for it)."""
+        return self._take_loss((self.step_count + 1) & 1)
+
+    # ------------------------------------------------------------------ weights in and out
+    def _export(self, views):
+        return unpack_head(self.cfg, {n: views[n].detach().cpu().numpy() for n in HEAD_DEVICE_NAMES})
+
+    def export_variables(self):
+        """{checkpoint name: array}: the head out of the device layout, and the backbone's arrays as they were loaded.
+        MatchModel.load_dict of it reproduces the device buffer bit for bit."""
+        out = {k: v for k, v in self.model.host.items() if not k.startswith(HEAD)}
+        out.update(self._export(self.model.d))
+        return out
+
+    def export_gradients(self):
+        return self._export(self.g)
+
+    def snapshot_tensors(self):
+        """What a snapshot holds: every variable, the Adam slots of the trained ones as <name>/Adam and <name>/Adam_1,
+        beta1_power, beta2_power and the step as Variable."""
+        out = self.export_variables()
+        for suffix, views in (('/Adam', self.m), ('/Adam_1', self.v)):
+            for name, a in self._export(views).items():
+                out[name + suffix] = a
+        out['beta1_power'] = np.float32(BETA1 ** (self.step_count + 1))
+        out['beta2_power'] = np.float32(BETA2 ** (self.step_count + 1))
+        out['Variable'] = np.int32(self.step_count)
+        return out
+
+    def load_slots(self, tensors, step):
+        """The Adam slots and the step out of a snapshot's tensors."""
+        import torch
+        for suffix, views in (('/Adam', self.m), ('/Adam_1', self.v)):
+            host = {}
+            for name in head_variable_names(self.cfg):
+                if name + suffix not in tensors:
+                    raise ValueError('the snapshot has no %s: it was not written by training' % (name + suffix))
+                host[name] = tensors[name + suffix]
+            for n, a in pack_head(self.cfg, host).items():
+                views[n].copy_(torch.from_numpy(a).view(views[n].shape))
+        self.step_count = int(step)
+
+
+def snapshot_prefix(snapshot_root, iteration):
+    return os.path.join(snapshot_root, '%s_iter_%d.tfmodel' % (MODEL_NAME, iteration))
+
+
+def write_snapshot(trainer, snapshot_root, iteration, cursor):
+    """<snapshot_root>/deeplab_RMI_iter_<n>.tfmodel.{index, data-00000-of-00001}, the ``checkpoint`` file that names it and
+    <prefix>.train_state.json with the cursor, the shuffled order and the generator's state.  -> the prefix."""
+    from . import tf_checkpoint
+    os.makedirs(snapshot_root, exist_ok=True)
+    prefix = snapshot_prefix(snapshot_root, iteration)
+    tf_checkpoint.write_checkpoint(prefix, trainer.snapshot_tensors())
+    with open(prefix + '.train_state.json', 'w') as f:
+        json.dump(dict(cursor.state(), iteration=int(iteration)), f)
+    base = os.path.basename(prefix)
+    with open(os.path.join(snapshot_root, 'checkpoint'), 'w') as f:
+        f.write('model_checkpoint_path: "%s"\nall_model_checkpoint_paths: "%s"\n' % (base, base))
+    return prefix
+
+
+def snapshot_iteration(prefix):
+    """The iteration in a snapshot's name, as the reference reads it: between the last '_' and the last '.'."""
+    try:
+        return int(prefix[prefix.rfind('_') + 1:prefix.rfind('.')])
+    except ValueError:
+        raise ValueError('%r: no iteration in the snapshot name' % prefix)

@@ -15,7 +15,8 @@ DESIGN.md section 8.6.
 ``features`` and ``predict`` are the pass in two halves -- the backbone once per scene, the head once per caption -- for the
 evaluation on a split (match_eval.py).
 
-Not here: training, the other backbones, attention, post_processing_mask_with_segmentation."""
+Not here: training (match_train.py), the other backbones, attention,
+post_processing_mask_with_segmentation."""
 import os
 import re
 
