@@ -24,6 +24,7 @@ import torch
 from . import hip
 from .params import Buffers, ParamStore
 from .residual import ResidualGenerator
+from .step_graphs import FAILED, StepGraphs
 
 _TOWERS = {}
 MASK_CLASSES = 3        # data_processing.image_processing.load_region_mask writes the classes 0, 1, 2
@@ -112,8 +113,8 @@ class BGTrainer(object):
         # step sizes live in device memory so that one captured graph serves every step.
         self.use_graphs = bool(use_graphs)
         self.lr_dev = torch.zeros(2, dtype=torch.float32, device=device)
-        self._static, self._graphs, self._seen = {}, {}, set()
-        self._graph_gen = {}        # graph key -> hip.split_generation() at its capture
+        self._step_graphs, self._static = StepGraphs(), {}
+        self._graphs = self._step_graphs.graphs
         # D(real) -- forward, its loss term, backward into the discriminator's gradient buffer -- does not depend on the generator:
         # it runs on a stream of its own beside the generator forward, in the CUs that pass's many small launches leave idle
         # (SSC_BG_OVERLAP_REAL=0: everything in line, as rounds 3-5)
@@ -354,26 +355,11 @@ class BGTrainer(object):
             self._gctx = gradients()
             self._adam_launch()
 
-        g = self._graphs.get(key)
-        if g is None:
-            if key not in self._seen:
-                self._seen.add(key)
-                impl()
-                return self._gctx
-            try:
-                g = hip.new_graph()
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    impl()
-            except Exception as e:      # never lose a training run to graph capture
-                print('hipGraph capture failed (%r): continuing with eager launches' % (e,))
-                self.use_graphs = False
-                torch.cuda.synchronize()
-                impl()
-                return self._gctx
-            self._graphs[key] = g
-            self._graph_gen[key] = hip.split_generation()
-        hip.resplit_stale()         # weights replaced through torch since the planes were made (trainer.py: _run_step_inner)
-        g.replay()
-        for sc in (self.store.discriminator, self.store.generator):
-            hip.refresh_new_splits(sc.flat, self._graph_gen[key])
+        outcome, _ = self._step_graphs.run(key, impl, (self.store.discriminator.flat, self.store.generator.flat))
+        if outcome == FAILED:       # never lose a training run to graph capture: eager launches from here on
+            self.use_graphs = False
+            torch.cuda.synchronize()
+            if self._real_stream is not None:       # it forked inside the abandoned capture: not used again
+                self._real_stream = torch.cuda.Stream()
+            impl()
         return self._gctx

@@ -25,6 +25,7 @@ from .hip import _dev_env
 from .dist_utils import GradReducer
 from .params import Buffers, ParamStore
 from .pix2pix import Pix2PixDiscriminator, Pix2PixGenerator
+from .step_graphs import CAPTURED, EAGER, FAILED, StepGraphs
 
 
 class GanTrainer(object):
@@ -95,9 +96,8 @@ class GanTrainer(object):
         # hipGraph replay of whole D-/G-steps (the ~550 launches of a step are host-bound otherwise):
         # a step shape is run eagerly the first time, captured the second time, replayed afterwards
         self.use_graphs = bool(use_graphs)
-        self._capturing = False
-        self._graphs, self._seen, self._static = {}, set(), {}
-        self._graph_gen = {}        # graph key -> hip.split_generation() at its capture
+        self._step_graphs, self._static = StepGraphs(), {}     # (the inference pass's graphs too: _infer)
+        self._graphs = self._step_graphs.graphs
         # world > 1: collectives are NOT captured.  A step is captured as a chain of graph segments that end where
         # the backward pass hands a gradient section to the reducer; replay = segment, eager RCCL all-reduce on the
         # side stream, next segment, ...  (same overlap as eager mode, no dependence on graph-capturable RCCL).
@@ -230,15 +230,14 @@ class GanTrainer(object):
         self._seg['ops'].append(op)
         self._seg_begin_graph()
 
-    def _capture_segments(self, impl, sbatch):
+    def _capture_segments(self, impl):
         stream = torch.cuda.Stream()
         stream.wait_stream(torch.cuda.current_stream())
         self._seg = {'ops': [], 'pool': torch.cuda.graph_pool_handle(), 'cur': None, 'mark': 0}
-        self._capturing = True
         try:
             with torch.cuda.stream(stream):
                 self._seg_begin_graph()
-                impl(sbatch)
+                impl()
                 self._seg_end_graph()
         except Exception:
             cur = self._seg.get('cur') if self._seg else None
@@ -249,7 +248,6 @@ class GanTrainer(object):
                     pass
             raise
         finally:
-            self._capturing = False
             ops, self._seg = (self._seg['ops'] if self._seg else []), None
         torch.cuda.current_stream().wait_stream(stream)
         return ops
@@ -311,15 +309,8 @@ class GanTrainer(object):
         """The device tensors a replayed 'd' / 'g' step reads its inputs from (graphs replay fixed addresses), allocated
         after ``like`` and filled with it.  An input pipeline that writes the next batch straight into them -- and passes them as the step's
         batch, with the host-side ``text`` -- saves the per-step device copies; any other batch is copied in."""
-        st = self._static_inputs(kind, like)
-        for k, v in st.items():
-            if like[k].data_ptr() != v.data_ptr():
-                v.copy_(like[k])
         out = dict(like)
-        out.update(st)
-        if self.G.lstm_hybrid and not isinstance(like['text'], dict):
-            # the caption tokens too: time-major ids and skip mask on the device (own buffers per step kind)
-            out['text'] = self.G.text.prepare(like['text'], 'g' + kind)
+        out.update(self._static_batch(kind, like))
         return out
 
     def _static_batch(self, kind, batch):
@@ -330,6 +321,7 @@ class GanTrainer(object):
                 v.copy_(batch[k])
         sbatch = dict(st)
         if self.G.lstm_hybrid and not isinstance(batch['text'], dict):      # a dict: already prepared (input_buffers)
+            # the caption tokens too: time-major ids and skip mask on the device (own buffers per step kind)
             sbatch['text'] = self.G.text.prepare(batch['text'], 'g' + kind)
         else:
             sbatch['text'] = batch['text']
@@ -374,46 +366,20 @@ class GanTrainer(object):
         elif use_real:
             key = key + ('use_real',)
         if kind == 'd':
-            impl = lambda b, a=ahead: self._d_impl(b, a, use_real)
+            impl = lambda: self._d_impl(sbatch, ahead, use_real)
         else:
-            impl = lambda b, r=real: self._g_impl(b, use_ahead, r)
+            impl = lambda: self._g_impl(sbatch, use_ahead, real)
         self._adam_prepare(scope, idx, lr * self.decay(counter))
-        g = self._graphs.get(key)
-        if g is None:
-            if key not in self._seen:       # first time: eager (allocates buffers, sets kernel attributes)
-                self._seen.add(key)
-                return impl(sbatch)
-            try:
-                if self.segment_graphs:
-                    g = self._capture_segments(impl, sbatch)
-                else:
-                    g = hip.new_graph()
-                    self._capturing = True
-                    try:
-                        with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                            impl(sbatch)
-                    finally:
-                        self._capturing = False
-            except Exception as e:      # never lose a training run to graph capture: fall back to eager launches
-                print('hipGraph capture failed (%r): continuing with eager launches' % (e,))
-                self.use_graphs = False
-                self._seg = None
-                self._g_done, self._d_late_sent = set(), False      # nothing of the abandoned capture was exchanged
-                torch.cuda.synchronize()
-                scope.adam_t -= 1       # _adam_prepare ran once for this step already
-                self._adam_prepare(scope, idx, lr * self.decay(counter))
-                return impl(sbatch)
-            self._graphs[key] = g
-            self._graph_gen[key] = hip.split_generation()
-        # bf16 planes and replayed graphs (hip.resplit_stale / refresh_new_splits): weights replaced through torch since the
-        # last launch are split again in front of the replay; filters that met their first bf16 launch after this graph was
-        # captured are not in its optimizer refresh and are split behind it
-        hip.resplit_stale()
-        if isinstance(g, list):
-            self._replay_segments(g)
-        else:
-            g.replay()
-        hip.refresh_new_splits(scope.flat, self._graph_gen[key])
+        seg = {'capture': self._capture_segments, 'replay': self._replay_segments} if self.segment_graphs else {}
+        outcome, _ = self._step_graphs.run(key, impl, (scope.flat,), **seg)
+        if outcome == FAILED:       # never lose a training run to graph capture: eager launches from here on
+            self.use_graphs = False
+            self._seg = None
+            self._g_done, self._d_late_sent = set(), False      # nothing of the abandoned capture was exchanged
+            torch.cuda.synchronize()
+            scope.adam_t -= 1       # _adam_prepare ran once for this step already
+            self._adam_prepare(scope, idx, lr * self.decay(counter))
+            impl()
         return self.loss[1:2] if kind == 'd' else self.loss[0:1]
 
     def _g_forward(self, batch, tag='g', **kw):
@@ -883,28 +849,20 @@ class GanTrainer(object):
         for name, src in (('sk', sketches), ('nv', noise_vec), ('lb', labels)):
             if src is not None and src.data_ptr() != st[name].data_ptr():
                 st[name].copy_(src)
-        g = self._graphs.get(key)
-        if g is None:
-            if key not in self._seen:
-                self._seen.add(key)
-                res = body(st['sk'], prep, st['nv'], st['lb'])
-                self.infer_nhwc = made['nhwc']
-                return res
-            try:
-                g = hip.new_graph()
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    self._static[key] = body(st['sk'], prep, st['nv'], st['lb'])
-            except Exception as e:      # never lose a request to graph capture
-                print('hipGraph capture of the inference pass failed (%r): continuing with eager launches' % (e,))
-                self.use_graphs_infer = False
-                torch.cuda.synchronize()
-                res = body(sketches, text, noise_vec, labels)
-                self.infer_nhwc = made['nhwc']
-                return res
-            self._graphs[key] = g
-            self._static[key + ('nhwc',)] = made['nhwc']
-        hip.resplit_stale()         # weights replaced through torch (load_dict, a restore) since the planes were made
-        g.replay()
+
+        def impl():
+            made['res'] = body(st['sk'], prep, st['nv'], st['lb'])
+
+        outcome, _ = self._step_graphs.run(key, impl, label='hipGraph capture of the inference pass')
+        if outcome == FAILED:
+            self.use_graphs_infer = False
+            torch.cuda.synchronize()
+            made['res'] = body(sketches, text, noise_vec, labels)
+        if outcome in (EAGER, FAILED):
+            self.infer_nhwc = made['nhwc']
+            return made['res']
+        if outcome == CAPTURED:     # the graph's own output tensors
+            self._static[key], self._static[key + ('nhwc',)] = made['res'], made['nhwc']
         self.infer_nhwc = self._static[key + ('nhwc',)]
         return self._static[key].clone() if clone else self._static[key]
 

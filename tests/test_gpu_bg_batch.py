@@ -180,6 +180,58 @@ def test_train_step_u8_is_the_float_step(use_graphs):
     assert all(np.isfinite(la)) and all(abs(x - y) <= 1e-9 * max(1.0, abs(y)) for x, y in zip(la, lb)), (la, lb)
 
 
+def _filter_with_planes(hip, scope, name=None):
+    """(name, plane entries) of one filter of ``scope`` that owns persistent bf16 planes: the first by name, or ``name``."""
+    lo, hi = scope.flat.data_ptr(), scope.flat.data_ptr() + scope.flat.numel() * scope.flat.element_size()
+    at = {v.data_ptr(): n for n, v in scope.p.items()}
+    owned = {}
+    for e in hip._SPLITS.values():
+        if e.param and lo <= e.key[0] < hi and e.key[0] in at:
+            owned.setdefault(at[e.key[0]], []).append(e)
+    if name is None:
+        assert owned, 'no generator filter owns persistent planes at this size'
+        name = sorted(owned)[0]
+    assert name in owned, (name, 'owns no planes on this trainer')
+    return name, owned[name]
+
+
+def test_replayed_step_follows_a_filter_written_through_torch():
+    """A replayed Background step launches into the ADDRESSES of the filters' bf16 planes: a filter scaled in place through its
+    store view between two replays must reach its planes in front of the next one (hip.resplit_stale), or the step would train
+    on with the old weights in its bf16 layers.  Three uint8 steps at N = 2, 64 x 64 (eager, captured, replayed) on a trainer
+    with graphs and on one without, one generator filter halved on both, a fourth step: every weight and both Adam states
+    stay bit for bit the eager trainer's.  64 x 64 at N = 2 is the size used: generator filters own planes there (the test
+    fails, it does not pass, where none does)."""
+    import bg_colorization_main as bgcli
+    from sketchyscenecolorization_amd import hip
+    from sketchyscenecolorization_amd.bg_colorization import BGTrainer
+    if not hip.ARITH_BF16:
+        pytest.skip('SSC_ARITH=fp32: no planes')
+    scenes = bgcli.Scenes({'image_size': 64, 'text_len': 8, 'data_base_dir': 'no_such_dir', 'mode': 'train', 'vocab_size': 18})
+    a = BGTrainer(image_size=64, max_steps=10, seed=4, use_graphs=True)
+    b = BGTrainer(image_size=64, max_steps=10, seed=4, use_graphs=False)
+
+    def step(idxs):
+        fg, bg, tok, lab = _scene_batch(scenes, idxs)
+        for tr in (a, b):
+            tr.train_step_u8(fg, bg, tok, lab)
+        torch.cuda.synchronize()
+        _assert_same_state(a, b)
+
+    for idxs in ((0, 5), (3, 3), (7, 1)):
+        step(idxs)
+    assert len(a._graphs) == 1 and a.use_graphs and not b._graphs, 'the uint8 step was not captured'
+    name, planes_a = _filter_with_planes(hip, a.store.generator)
+    _, planes_b = _filter_with_planes(hip, b.store.generator, name)
+    before = a.store.generator.flat.clone()
+    for tr in (a, b):
+        tr.store.generator.p[name].mul_(0.5)
+    assert all(e.version != e.w._version for e in planes_a + planes_b), 'the planes do not know their filter was written'
+    step((2, 6))
+    assert all(e.version == e.w._version for e in planes_a + planes_b), (name, 'a plane was not split again')
+    assert not torch.equal(a.store.generator.flat, before)
+
+
 def _hand_trained(bgcli, nb, steps, seed):
     """The trainer the command line builds after random.seed(seed), stepped on the float path over the scenes it draws."""
     from sketchyscenecolorization_amd.bg_colorization import BGTrainer
