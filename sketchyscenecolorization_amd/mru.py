@@ -21,14 +21,9 @@ MFMA kernel with bias (+ lrelu for the gates) in its epilogue.  Fusions that cha
 import torch
 
 from . import hip
-from .hip import _dev_env
 from .hip import ACT_MIU, ACT_NONE, ACT_PRELU, View
+from .net_common import GradSlots, _rows, class_head_backward, class_head_forward
 from .text_fusion import TextFusion
-
-import os as _os
-_SPLIT_DGRAD = _dev_env('SSC_MRU_SPLIT_DGRAD', '1') == '1'
-_FUSE_MINMAX = _dev_env('SSC_MRU_FUSE_MINMAX', '1') == '1'           # gate extrema out of the conv epilogue (A/B)
-_FUSE_CBN_STATS = _dev_env('SSC_MRU_FUSE_STATS', '1') == '1'      # conditional-norm statistics out of the conv epilogue (A/B)
 
 ENC_UNITS = [(1, 8, 64), (2, 64, 128), (3, 128, 256), (4, 256, 512)]                 # (unit, C_h, D); inp = 3 ch
 DEC_UNITS = [(0, 512, 384), (2, 384, 256), (4, 256, 128), (6, 128, 128), (8, 128, 64)]      # (unit_num, C_h, D)
@@ -37,15 +32,11 @@ N_LABELS = 25
 REG_CONV = 1e-5     # ly.l2_regularizer(weight_decay_rate=1e-5) on the block convs (mru.py:600, 664 -> :381, 545)
 
 
-def _rows(t):
-    return t.view(-1, t.shape[-1])
-
-
 def _pad4(c):
     return (c + 3) // 4 * 4
 
 
-class _MRUBlocks(object):
+class _MRUBlocks(GradSlots):
     """mru_conv_block_v3 forward / backward shared by the generator's encoder (conditional norm + miu_relu, plain
     weights) and the discriminator (prelu, spectral-normed weights)."""
 
@@ -75,17 +66,6 @@ class _MRUBlocks(object):
         if self._sn is not None:
             return self._sn[pre]['wbar'].view(self.s[pre + '/weights'].shape)
         return self.s[pre + '/weights']
-
-    def _gslot(self, t):
-        key = t.data_ptr()
-        if key in self._gdone:
-            return self._gdone[key], True
-        g = self.b.get('grad_of/%d' % key, t.shape)
-        self._gdone[key] = g
-        return g, False
-
-    def _gget(self, t):
-        return self._gdone.get(t.data_ptr())
 
     def _gset(self, t, g):
         self._gdone[t.data_ptr()] = g
@@ -157,12 +137,12 @@ class _MRUBlocks(object):
             co = cout if nstore is None else nstore
             out = self.b.get(tag + '/' + pre + '/' + name, (xv.N, -(-xv.H // stride), -(-xv.W // stride), co))
         bn = None
-        if stats and _FUSE_CBN_STATS and self.cond_norm and accumulate_into is None and nstore is None and epi == 0:
+        if stats and self.cond_norm and accumulate_into is None and nstore is None and epi == 0:
             ab = self.b.get(tag + '/' + pre + '/ab0', (2 * cout,))
             st = self.b.get(tag + '/' + pre + '/st', (2 * cout,))
             bn = (self._const(cout, 1.0), self._const(cout, 0.0), ab, st)
             self._pre_stats[out.data_ptr()] = pre
-        if minmax is not None and (accumulate_into is not None or nstore is not None or not _FUSE_MINMAX):
+        if minmax is not None and (accumulate_into is not None or nstore is not None):
             hip.conv_forward(xv, self._w(pre), stride, 0, out, bias=s[pre + '/biases'], epi=epi, same=True,
                              accumulate=accumulate_into is not None, nstore=nstore)
             hip.minmax_hw(out, minmax)
@@ -200,8 +180,8 @@ class _MRUBlocks(object):
         wide = n_all // 64 * 64
         # [h, sketch] inputs: 128 + 3 (or 256 + 3 ...) channels.  As one launch the 3 extra columns cost a whole 64-column
         # tile of matrix work (131 -> 192 columns computed); split: the multiple of 64 on the tile kernel, the rest (<= 4
-        # columns) on the narrow kernel (SSC_MRU_SPLIT_DGRAD=0: one launch)
-        if _SPLIT_DGRAD and k_real is None and n_off == 0 and 0 < n_all - wide <= 4 and wide >= 64 and n_st - wide <= 4 \
+        # columns) on the narrow kernel
+        if k_real is None and n_off == 0 and 0 < n_all - wide <= 4 and wide >= 64 and n_st - wide <= 4 \
                 and dy.shape[-1] % 32 == 0:
             hip.conv_dgrad(View(dy), w, 1, (k - 1) // 2, out, n_off=0, nn=wide, nstore=wide, accumulate=accumulate)
             hip.conv_dgrad(View(dy), w, 1, (k - 1) // 2, out, n_off=wide, nn=n_all - wide, nstore=n_st - wide,
@@ -610,10 +590,7 @@ class MRUDiscriminator(_MRUBlocks):
         C = img.shape[-1]
         mean = B.get(tag + '/img_mean', (N, C))
         hip.call('ssc_act_mean_hw', img, None, ACT_NONE, N, P4, C, mean)
-        K = s['discriminator/fully_connected/weights'].shape[1]
-        logits = B.get(tag + '/logits', (N, K))
-        hip.call('ssc_fc_small_fwd', mean, sn['discriminator/fully_connected']['wbar'],
-                 s['discriminator/fully_connected/biases'], N, C, K, logits)
+        logits = class_head_forward(s, B, tag, mean, sn['discriminator/fully_connected']['wbar'])
         return {'tag': tag, 'N': N, 'xd': xd, 'x0': x0, 'pyr': pyr, 'h0raw': h0raw, 'h0': h0, 'tape': tape,
                 'pre_last': pre_last, 'img': img, 'mean': mean, 'logits': logits, 'disc': disc, 'P4': P4}
 
@@ -629,15 +606,8 @@ class MRUDiscriminator(_MRUBlocks):
         g_img = B.get(tag + '/gb/g_img', img.shape)
         self._conv_dgrad('discriminator/Conv_1', dl5, g_img, k_real=1)
         if dlogits is not None:
-            st = sn['discriminator/fully_connected']
-            dmean = B.get(tag + '/gb/dmean', (N, C))
-            K = dlogits.shape[1]
-            gw, gb_, acc = None, None, 0
-            if need_params:
-                gb_ = s.grad('discriminator/fully_connected/biases')
-                gw, acc = st['gwbar'], int(st['n_acc'] > 0)
-                st['n_acc'] += 1
-            hip.call('ssc_fc_small_bwd', ctx['mean'], st['wbar'], dlogits, N, C, K, dmean, gw, gb_, acc)
+            dmean = class_head_backward(s, ctx['mean'], sn['discriminator/fully_connected'], dlogits,
+                                        B.get(tag + '/gb/dmean', (N, C)), need_params)
             hip.call('ssc_add_row_bcast', g_img, dmean, 1.0 / ctx['P4'], N, ctx['P4'], C)
         g_pl = B.get(tag + '/gb/g_pre_last', pre_last.shape)
         self._na_bwd(tag, 'discriminator/mru_conv_unit_last_norm', pre_last, None, None, g_img, C, g_pl, False,

@@ -8,23 +8,13 @@ applied, together with the lrelu/relu of the *next* block and the skip concat,
 inside that block's tile loads (hip.View).  Nothing normalised, activated or
 concatenated is ever written to HBM.
 """
-import os
-
 import torch
 
 from . import hip
 from .hip import _dev_env
 from .hip import ACT_LRELU, ACT_NONE, ACT_RELU, View
+from .net_common import SnClassHead, _rows
 from .text_fusion import TextFusion
-
-
-def _rows(t):
-    return t if t.dim() == 2 else t.view(-1, t.shape[-1])
-
-
-_MERGE_DDGRAD = _dev_env('SSC_MERGE_DDGRAD', '1') == '1'
-_DBWD_WGRAD_FIRST = _dev_env('SSC_DBWD_WGRAD_FIRST', '1') == '1'   # discriminator backward: filter gradient of layer k in front of its data gradient (round-3 order; the round-4 order -- behind the data gradient and the sums' fold -- measured 0.3 ms slower per iteration on one box, profiles/r05_ab_envsets.txt)
-_BNBWD2 = _dev_env('SSC_BNBWD2', '1') == '1'      # norm-backward sums of both halves out of the merged launch's epilogue (A/B)
 
 
 class Pix2PixGenerator(object):
@@ -134,23 +124,6 @@ class Pix2PixGenerator(object):
         hip.nhwc_to_nchw(ctx['out'], o, ctx['out_coff'])
         return o
 
-    bn_stream = None        # helper stream of backward (set by the trainer): see _fork
-
-    def _fork(self, fn):
-        """Issue fn's launches on the helper stream, ordered after everything issued so far on the current stream.
-        Returns whether a fork happened (then _join() before the next dependent or full-size launch)."""
-        st = self.bn_stream if hip.PROFILE is None else None
-        if st is None:
-            fn()
-            return False
-        st.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(st):
-            fn()
-        return True
-
-    def _join(self):
-        torch.cuda.current_stream().wait_stream(self.bn_stream)
-
     def _sums(self, tag, name, x, ab, stats, sources=1):
         x2d = _rows(x)
         buf = self.b.get(tag + '/gb/bnsums_' + name, (hip.BnBwdSums.rows_needed(x2d.shape[0], sources), 2 * x2d.shape[1]))
@@ -181,40 +154,28 @@ class Pix2PixGenerator(object):
                   hip.deconv_wgrad(v, dyv, s.grad('generator/decoder_%d/deconv/filter' % k)))
             if hold:
                 held.append(wg)
-            g0 = B.get(tag + '/gb/d%d_in0' % k, (N, v.H, v.W, v.C0))
-            g1 = B.get(tag + '/gb/d%d_in1' % k, (N, v.H, v.W, v.C1))
             # the two per-channel sums of each norm's backward are taken by the epilogues of the data-gradient launches
             # that produce its incoming gradients (hip.BnBwdSums): decoder_{k+1}'s norm from g0, encoder_k's from g1 + gin
-            merged = _MERGE_DDGRAD and 2 <= k <= 4
             sums_d = self._sums(tag, 'd%d' % (k + 1), d[k + 1], abd[k + 1], std[k + 1]) if k < 5 else None
             if 2 <= k <= 4:
                 sums_e[k] = self._sums(tag, 'e%d' % k, e[k], ab[k], st[k], sources=2)
-            if merged:
                 # decoder_k reads concat[decoder_{k+1}, encoder_k]: the gradients of the two halves are the SAME gather of dy
                 # against two column ranges of the filter.  One launch over both ranges (twice the tiles: 288 instead of
                 # 2 x 144 for decoder_4 -- half-empty launches otherwise) into one buffer, the halves read back through
                 # strided row views; 17.77 -> 17.65 ms per step.  The norm-backward sums of BOTH sites come out of its
                 # epilogue: a column tile lies in one half, so each workgroup takes the tables of its own tensor.
                 g01 = B.get(tag + '/gb/d%d_in01' % k, (N, v.H, v.W, v.C0 + v.C1))
-                if _BNBWD2:
-                    hip.deconv_dgrad(dyv, f, g01, n_off=0, nn=v.C0 + v.C1,
-                                     bnbwd=[sums_d.take(ACT_RELU), sums_e[k].take(ACT_RELU)])
-                else:
-                    hip.deconv_dgrad(dyv, f, g01, n_off=0, nn=v.C0 + v.C1)
-                    for sm in (sums_d, sums_e[k]):
-                        sm.sources += 1
-                        sm.missed += 1
+                hip.deconv_dgrad(dyv, f, g01, n_off=0, nn=v.C0 + v.C1,
+                                 bnbwd=[sums_d.take(ACT_RELU), sums_e[k].take(ACT_RELU)])
                 r01 = g01.view(-1, v.C0 + v.C1)
                 g0, g1 = r01[:, :v.C0], r01[:, v.C0:]
-            else:
+            else:       # k = 1 (the skip half feeds no norm) and k = 5 (no decoder above): one launch per half
+                g0 = B.get(tag + '/gb/d%d_in0' % k, (N, v.H, v.W, v.C0))
+                g1 = B.get(tag + '/gb/d%d_in1' % k, (N, v.H, v.W, v.C1))
                 hip.deconv_dgrad(dyv, f, g0, n_off=0, nn=v.C0, bnbwd=(sums_d.take(ACT_RELU) if sums_d else None))
-
-            def rest(wg=wg, dyv=dyv, f=f, g1=g1, v=v, k=k, merged=merged):
-                if not merged:
-                    hip.deconv_dgrad(dyv, f, g1, n_off=v.C0, nn=v.C1, bnbwd=(sums_e[k].take(ACT_RELU) if sums_e[k] else None))
-                if not hold:
-                    wg()
-            forked = self._fork(rest)
+                hip.deconv_dgrad(dyv, f, g1, n_off=v.C0, nn=v.C1)
+            if not hold:
+                wg()
             if k < 5:
                 g_skip[k] = g1          # through relu to encoder_k's output
                 src = d[k + 1]
@@ -225,8 +186,6 @@ class Pix2PixGenerator(object):
                 gcur = dx
             else:
                 g_feat, g_noise = g0, g1
-            if forked:
-                self._join()
         # noise head
         P = ctx['noise'].shape[1] * ctx['noise'].shape[2]
         cd = ctx['noise'].shape[3]
@@ -287,8 +246,7 @@ class Pix2PixGenerator(object):
             live = sums_e[k - 1] is not None and not sums_e[k - 1].missed
             hip.conv_dgrad(dyv, w, 2, 1, gin, bnbwd=(sums_e[k - 1].take(ACT_LRELU) if live else None))
             dx = B.get(tag + '/gb/de%d' % (k - 1), e[k - 1].shape)
-            forked = self._fork(lambda xin=xin, dyv=dyv, k=k:
-                                hip.conv_wgrad(xin, dyv, s.grad('generator/encoder_%d/conv/filter' % k), 2, 1))
+            hip.conv_wgrad(xin, dyv, s.grad('generator/encoder_%d/conv/filter' % k), 2, 1)
             if k - 1 >= 2:
                 hip.bn_act_backward(_rows(e[k - 1]), ab[k - 1], st[k - 1], _rows(gin), ACT_LRELU, _rows(dx),
                                     g2=_rows(g_skip[k - 1]), act2=ACT_RELU,
@@ -297,8 +255,6 @@ class Pix2PixGenerator(object):
             else:
                 hip.bn_act_backward(_rows(e[1]), None, None, _rows(gin), ACT_LRELU, _rows(dx),
                                     g2=_rows(g_skip[1]), act2=ACT_RELU)
-            if forked:
-                self._join()
             gcur = dx
             if k == 5 and not text_pending:
                 done('encoder_5')       # its filter, scale and offset gradients are final (trainer._sections)
@@ -314,29 +270,14 @@ class Pix2PixGenerator(object):
 _HEAD1_FUSED = _dev_env('SSC_HEAD1_FUSED', '0') == '1'
 
 
-class Pix2PixDiscriminator(object):
-    """discriminate_pix2pix: 70x70-style PatchGAN + spectral-normed auxiliary classifier."""
+class Pix2PixDiscriminator(SnClassHead):
+    """discriminate_pix2pix: 70x70-style PatchGAN + spectral-normed auxiliary classifier (net_common.SnClassHead)."""
 
     def __init__(self, store, bufs, sn=True):
         self.s, self.b = store, bufs
         self.sn = bool(sn)
         self.chans = [8, 64, 128, 256, 512, 1]
         self.strides = [None, 2, 2, 2, 1, 1]
-
-    def prepare_sn(self, tag='d/sn', u=None):
-        """One power iteration on fully_connected/weights (sn.py), shared by every call of this step.
-        tag / u: buffers and starting vector of a pass that runs beside another step's (the discriminator's real pass run
-        ahead inside the generator step starts from the u that step is about to assign: trainer._d_real_pass)."""
-        s, B = self.s, self.b
-        W = s['discriminator/fully_connected/weights']
-        m, n = W.shape
-        if not self.sn:
-            return {'wbar': W}
-        sn = {'v': B.get(tag + '/v', (m,)), 'u_new': B.get(tag + '/u_new', (1, n)), 'wbar': B.get(tag + '/wbar', (m, n)),
-              'aux': B.get(tag + '/aux', (4,)), 'gwbar': B.get(tag + '/gwbar', (m, n)), 'n_acc': 0,
-              'scratch': B.get(tag + '/scratch', (m,)), 'u': (u if u is not None else s['discriminator/fully_connected/u'])}
-        hip.call('ssc_sn_forward', W, sn['u'], m, n, sn['v'], sn['u_new'], sn['wbar'], sn['aux'])
-        return sn
 
     def forward(self, xd, sn, tag):
         """xd NHWC [N,H,W,8] = [discrim_inputs(3), discrim_targets(3), 0, 0]."""
@@ -368,9 +309,7 @@ class Pix2PixDiscriminator(object):
         P4 = l[4].shape[1] * l[4].shape[2]
         img = B.get(tag + '/img', (N, 512))
         hip.call('ssc_act_mean_hw', l[4], ab[4], ACT_LRELU, N, P4, 512, img)
-        K = s['discriminator/fully_connected/weights'].shape[1]
-        logits = B.get(tag + '/logits', (N, K))
-        hip.call('ssc_fc_small_fwd', img, sn['wbar'], s['discriminator/fully_connected/biases'], N, 512, K, logits)
+        logits = self._head_forward(tag, img, sn)
         return {'tag': tag, 'N': N, 'l': l, 'ab': ab, 'st': st, 'img': img, 'logits': logits, 'disc': l[5], 'P4': P4}
 
     def backward(self, ctx, dl5, dlogits, sn, need_params, need_input, accumulate, after_layer=None, stop_after=None,
@@ -397,17 +336,7 @@ class Pix2PixDiscriminator(object):
             hip.conv_wgrad(x5, dy5, gname(5, 'conv/filter'), 1, 1, accumulate=accumulate)
         rowb = None
         if dlogits is not None:
-            dimg = B.get(tag + '/gb/dimg', (N, 512))
-            K = dlogits.shape[1]
-            gw, gb_, acc = None, None, 0
-            if need_params:
-                gb_ = s.grad('discriminator/fully_connected/biases')
-                if self.sn:     # gradient w.r.t. W_bar, summed over the calls of this step
-                    gw, acc = sn['gwbar'], int(sn['n_acc'] > 0)
-                    sn['n_acc'] += 1
-                else:
-                    gw, acc = s.grad('discriminator/fully_connected/weights'), int(accumulate)
-            hip.call('ssc_fc_small_bwd', ctx['img'], sn['wbar'], dlogits, N, 512, K, dimg, gw, gb_, acc)
+            dimg = self._head_backward(ctx, sn, dlogits, need_params, accumulate)
             # the class head reads the spatial mean of layer 4: its gradient dimg / P4 is added to g4 by the norm backward
             # below while it reads g4 (no pass of its own over the tensor)
             rowb = (dimg, 1.0 / ctx['P4'], ctx['P4'])
@@ -479,9 +408,9 @@ class Pix2PixDiscriminator(object):
             dyv = View(dx)
             w = s['discriminator/layer_%d/conv/filter' % k]
             dx_next = None
-            if need_params and _DBWD_WGRAD_FIRST:
-                # round-3 order: the filter gradient of layer k in front of its data gradient (the chain's next full-size launch
-                # then follows the small launches of the norm backward directly)
+            if need_params:
+                # the filter gradient of layer k in front of its data gradient (the chain's next full-size launch then follows
+                # the small launches of the norm backward directly)
                 hip.conv_wgrad(xin, dyv, gname(k, 'conv/filter'), self.strides[k], 1, accumulate=accumulate)
                 if after_layer is not None:
                     after_layer(k)
@@ -498,26 +427,7 @@ class Pix2PixDiscriminator(object):
             elif need_input:
                 dgen = B.get(tag + '/gb/dgen', (N, l[0].shape[1], l[0].shape[2], 4))
                 hip.conv_dgrad(dyv, w, 2, 1, dgen, n_off=3, nn=3, nstore=4)
-            if need_params and not _DBWD_WGRAD_FIRST:
-                hip.conv_wgrad(xin, dyv, gname(k, 'conv/filter'), self.strides[k], 1, accumulate=accumulate)
-                if after_layer is not None:
-                    after_layer(k)
             dx = dx_next
             if stop_after == k and k > 1:
                 return {'layers': tuple(j for j in layers if j < k), 'gcur': dx, 'sums': None}
         return dgen
-
-    def finish_sn_backward(self, sn, accumulate=False):
-        """d loss / d W from the accumulated d loss / d W_bar, through sigma and the power iteration."""
-        s, B = self.s, self.b
-        if not self.sn:
-            return
-        W = s['discriminator/fully_connected/weights']
-        m, n = W.shape
-        gW = s.grad('discriminator/fully_connected/weights')
-        if sn['n_acc'] == 0:
-            if not accumulate:
-                hip.fill(gW, 0.0)
-            return
-        hip.call('ssc_sn_backward', W, sn['u'], sn['v'], sn['u_new'], sn['aux'], sn['gwbar'], m, n, gW, int(accumulate),
-                 sn['scratch'])

@@ -21,19 +21,10 @@ projection shortcut; gradients of a tensor with several consumers accumulate in 
 import torch
 
 from . import hip
-from .hip import _dev_env
 from .hip import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, View
+from .net_common import GradSlots, SnClassHead, _rows
 from .params import RESIDUAL_UNITS
 from .text_fusion import TextFusion
-
-
-import os as _os
-
-_BLOCK_OUT_FUSED = _dev_env('SSC_BLOCK_OUT_FUSED', '1') == '1'     # ssc_block_out_backward (A/B switch)
-
-
-def _rows(t):
-    return t.view(-1, t.shape[-1])
 
 
 class _Val(object):
@@ -50,10 +41,8 @@ def _view(a, b=None):
     return View(a.t, b.t, a.ab, a.act, b.ab, b.act if b.act != a.act else -1)
 
 
-class _Bottlenecks(object):
+class _Bottlenecks(GradSlots):
     """bottleneck_residual_en / de / pu (residual_util.py:81-171): forward records + backward."""
-
-    _gtag = ''
 
     def _init_blocks(self, store, bufs):
         self.s, self.b = store, bufs
@@ -148,20 +137,6 @@ class _Bottlenecks(object):
         return self._merge(tag, pre, r3, ab3, x.t, None, act, rec)
 
     # ------------------------------------------------------------------ backward pieces
-    def _gslot(self, t):
-        """Gradient buffer of tensor ``t`` for this backward pass: (buffer, accumulate?)."""
-        key = t.data_ptr()
-        if key in self._gdone:
-            return self._gdone[key], True
-        # (_gtag: two backward passes through ONE forward context that run on different streams -- BGTrainer's fake pair -- must
-        # not share these buffers: the pass names its set)
-        g = self.b.get('grad_of/%s%d' % (self._gtag, key), t.shape)
-        self._gdone[key] = g
-        return g, False
-
-    def _gget(self, t):
-        return self._gdone.get(t.data_ptr())
-
     def _sums(self, tag, pre, raw, ab, st):
         """Partial sums of this norm's backward, to be delivered by the epilogue of the launch that produces its incoming
         gradient (hip.BnBwdSums / ssc_conv_forward_bnbwd)."""
@@ -235,17 +210,11 @@ class _Bottlenecks(object):
         out = rec['out']
         dz = B.get(tag + '/gb/' + pre + '/dz', out.shape)
         acc = accumulate
-        if _BLOCK_OUT_FUSED:
-            # dz = g_out * act'(out) and, with that one dz, the norm backward of block_3 and (en / de) of the projection
-            # shortcut: one partial-sum launch, one fold, one streaming launch (ssc_block_out_backward); dz itself is only
-            # written for the identity shortcut of a pu block
-            dr3, dsc = self._block_out_backward(rec, g_out, dz if kind == 'pu' else None, need_params, acc)
-        else:
-            hip.bn_act_backward(_rows(out), None, None, _rows(g_out), act, _rows(dz))      # act'(z) from the sign of out
-            # block_3 (1x1), block_2 (3x3 SAME)
-            dr3 = self._bn_bwd(tag, pre + '/block_3/batchnorm', rec['r3'], rec['ab3'], rec['st3'], dz, ACT_NONE,
-                               need_params, acc)
-            dsc = None
+        # dz = g_out * act'(out) and, with that one dz, the norm backward of block_3 and (en / de) of the projection
+        # shortcut: one partial-sum launch, one fold, one streaming launch (ssc_block_out_backward); dz itself is only
+        # written for the identity shortcut of a pu block
+        dr3, dsc = self._block_out_backward(rec, g_out, dz if kind == 'pu' else None, need_params, acc)
+        # block_3 (1x1), block_2 (3x3 SAME)
         x3 = View(rec['r2'], None, rec['ab2'], act)
         if need_params:
             hip.conv_wgrad(x3, View(dr3), s.grad(pre + '/block_3/conv_ex/filter'), 1, 0, accumulate=acc)
@@ -265,9 +234,6 @@ class _Bottlenecks(object):
         xv = rec['xv']
         branches = [(dr1, 'block_1')]
         if kind != 'pu':
-            if dsc is None:
-                dsc = self._bn_bwd(tag, pre + '/block_add/batchnorm', rec['sc'], rec['absc'], rec['stsc'], dz, ACT_NONE,
-                                   need_params, acc)
             branches.append((dsc, 'block_add'))
         op = {'en': 'conv', 'de': 'deconv', 'pu': 'conv_ex'}[kind]
         for dy, blk in branches:
@@ -581,28 +547,16 @@ class BGDiscriminator(_Bottlenecks):
         return dgen
 
 
-class ResidualDiscriminator(_Bottlenecks):
+class ResidualDiscriminator(_Bottlenecks, SnClassHead):
     """discriminate_residual (models_collection.py:844-893): five stride-2 encoder bottlenecks on
     concat[sketch, target], a 4x4 s1 SAME patch head on layer_5 and the spectral-normed class head on the spatial
-    mean of layer_4.  Same interface as Pix2PixDiscriminator."""
+    mean of layer_4 (net_common.SnClassHead).  Same interface as Pix2PixDiscriminator."""
 
     def __init__(self, store, bufs, sn=True):
         self._init_blocks(store, bufs)
         self.sn = bool(sn)
         self.chans = [64, 128, 256, 512, 512]
         self._tape, self._gdone = [], {}
-
-    def prepare_sn(self):
-        s, B = self.s, self.b
-        W = s['discriminator/fully_connected/weights']
-        m, n = W.shape
-        if not self.sn:
-            return {'wbar': W}
-        sn = {'v': B.get('d/sn/v', (m,)), 'u_new': B.get('d/sn/u_new', (1, n)), 'wbar': B.get('d/sn/wbar', (m, n)),
-              'aux': B.get('d/sn/aux', (4,)), 'gwbar': B.get('d/sn/gwbar', (m, n)), 'n_acc': 0}
-        hip.call('ssc_sn_forward', W, s['discriminator/fully_connected/u'], m, n, sn['v'], sn['u_new'], sn['wbar'],
-                 sn['aux'])
-        return sn
 
     def forward(self, xd, sn, tag):
         """xd NHWC [N,H,W,8] = [discrim_inputs(3), discrim_targets(3), 0, 0]."""
@@ -620,9 +574,7 @@ class ResidualDiscriminator(_Bottlenecks):
         P4 = l4.shape[1] * l4.shape[2]
         img = B.get(tag + '/img', (N, 512))
         hip.call('ssc_act_mean_hw', l4, None, ACT_NONE, N, P4, 512, img)
-        K = s['discriminator/fully_connected/weights'].shape[1]
-        logits = B.get(tag + '/logits', (N, K))
-        hip.call('ssc_fc_small_fwd', img, sn['wbar'], s['discriminator/fully_connected/biases'], N, 512, K, logits)
+        logits = self._head_forward(tag, img, sn)
         return {'tag': tag, 'N': N, 'xd': xd, 'tape': self._tape, 'l4': l4, 'l5': l5, 'img': img, 'logits': logits,
                 'disc': disc, 'P4': P4}
 
@@ -638,17 +590,7 @@ class ResidualDiscriminator(_Bottlenecks):
         g5, _ = self._gslot(l5)
         hip.conv_dgrad(View(dl5), w, 1, 1, g5, k_real=1)
         if dlogits is not None:
-            dimg = B.get(tag + '/gb/dimg', (N, 512))
-            K = dlogits.shape[1]
-            gw, gb_, acc = None, None, 0
-            if need_params:
-                gb_ = s.grad('discriminator/fully_connected/biases')
-                if self.sn:
-                    gw, acc = sn['gwbar'], int(sn['n_acc'] > 0)
-                    sn['n_acc'] += 1
-                else:
-                    gw, acc = s.grad('discriminator/fully_connected/weights'), int(accumulate)
-            hip.call('ssc_fc_small_bwd', ctx['img'], sn['wbar'], dlogits, N, 512, K, dimg, gw, gb_, acc)
+            dimg = self._head_backward(ctx, sn, dlogits, need_params, accumulate)
             g4, _ = self._gslot(l4)     # first contribution: mean over the P4 positions
             hip.fill(g4, 0.0)
             hip.call('ssc_add_row_bcast', g4, dimg, 1.0 / ctx['P4'], N, ctx['P4'], 512)
@@ -667,17 +609,3 @@ class ResidualDiscriminator(_Bottlenecks):
             else:
                 self._block_backward(rec, g_out, need_params, accumulate, True)
         return dgen
-
-    def finish_sn_backward(self, sn, accumulate=False):
-        s, B = self.s, self.b
-        if not self.sn:
-            return
-        W = s['discriminator/fully_connected/weights']
-        m, n = W.shape
-        gW = s.grad('discriminator/fully_connected/weights')
-        if sn['n_acc'] == 0:
-            if not accumulate:
-                hip.fill(gW, 0.0)
-            return
-        hip.call('ssc_sn_backward', W, s['discriminator/fully_connected/u'], sn['v'], sn['u_new'], sn['aux'],
-                 sn['gwbar'], m, n, gW, int(accumulate), B.get('d/sn/scratch', (m,)))

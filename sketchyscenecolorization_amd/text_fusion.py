@@ -22,8 +22,6 @@ import torch
 from . import hip
 from .hip import _dev_env
 
-import os
-
 CELL = '/RNN/%s/multi_rnn_cell/cell_0/basic_lstm_cell/'
 FUSED_STEP = _dev_env('SSC_LSTM_FUSED', '1') != '0'     # recurrent GEMM + gate math in one launch per step
 # ... for cells of fewer rows than this.  The one-launch step has no operand reuse through LDS (64 x 32 / 64 x 64 tiles straight
@@ -35,7 +33,6 @@ FUSED_STEP = _dev_env('SSC_LSTM_FUSED', '1') != '0'     # recurrent GEMM + gate 
 # -> 12.59 / 12.65 ms; the batch-32 train steps, whose 1152-row cells run beside other chains, do not move (Pix2Pix 12.94 /
 # 12.83 / 12.80 vs 12.93 / 12.92 / 12.79 ms, MRU 185.0 / 184.4 vs 185.2 / 185.4): the threshold sits above them.
 UNFUSED_ROWS = int(_dev_env('SSC_LSTM_UNFUSED_ROWS', '2048'))
-PINNED_PREP = _dev_env('SSC_PINNED_PREP', '1') != '0'       # caption tokens to the device through pinned memory (A/B: 0)
 
 
 def check_tokens(text, vocab):
@@ -72,10 +69,9 @@ class TextFusion(object):
             # through pinned memory, not waited for: a copy from pageable memory returns when it has HAPPENED, i.e. behind
             # everything queued on the stream -- the caller of a training step would wait here for the previous step to end
             tok = B.get(tag + '/tf/tok', (S * N,), torch.int32)
-            pin = (lambda t: t.pin_memory()) if PINNED_PREP else (lambda t: t)
-            tok.copy_(pin(torch.from_numpy(tok_np)), non_blocking=PINNED_PREP)
+            tok.copy_(torch.from_numpy(tok_np).pin_memory(), non_blocking=True)
             mask = B.get(tag + '/tf/mask', (S, N), torch.int32)
-            mask.copy_(pin(torch.from_numpy((tok_np != 0).astype(np.int32)).view(S, N)), non_blocking=PINNED_PREP)
+            mask.copy_(torch.from_numpy((tok_np != 0).astype(np.int32)).view(S, N).pin_memory(), non_blocking=True)
             prep.update(tok=tok, mask=mask)
         return prep
 

@@ -4,7 +4,8 @@ per tower, its own batch and batch statistics, steps captured as graph segments,
 between them, 1/world folded into TF-Adam.  Checks, per rank:
   1. after iteration 0 every weight equals a single-process reference that computes both towers' gradients separately, averages
      them per variable (average_gradients, graph_single.py:33-68) and applies TF-Adam once;
-  2. the graph-segment trainer equals an eager world-2 trainer over three iterations (capture + replay);
+  2. the graph-segment trainer equals an eager world-2 trainer over three iterations (capture + replay), and so does a
+     world-2 trainer that runs its two discriminator passes in line (the late section sent from inside the second pass);
   3. both ranks end with bit-identical weights."""
 import os
 import socket
@@ -31,6 +32,9 @@ def worker(rank, port, out_dir):
     kw = dict(img=IMG, seed=5, max_iter_step=50)
     T = GanTrainer(use_graphs=True, process_group=dist.group.WORLD, **kw)         # segments: the default for world > 1
     E = GanTrainer(use_graphs=False, process_group=dist.group.WORLD, **kw)
+    L = GanTrainer(use_graphs=False, overlap_real=False, process_group=dist.group.WORLD, **kw)    # everything in line
+    l_red, l_reduce = [], L.reducer.reduce_async
+    L.reducer.reduce_async = lambda flat, lo, hi: (l_red.append((flat, lo, hi)), l_reduce(flat, lo, hi))[1]
     assert T.world == WORLD and T.segment_graphs and T.reducer.world == WORLD
     refs = [GanTrainer(use_graphs=False, **kw) for _ in range(WORLD)]            # one per tower, world 1
 
@@ -54,9 +58,11 @@ def worker(rank, port, out_dir):
 
     # 2. graph segments (eager, capture, replay) == eager world-2 trainer
     E.train_iteration(bd[rank], bg[rank], 0)
+    L.train_iteration(bd[rank], bg[rank], 0)
     for it in (1, 2, 3):
         T.train_iteration(bd[rank], bg[rank], it)
         E.train_iteration(bd[rank], bg[rank], it)
+        L.train_iteration(bd[rank], bg[rank], it)
     torch.cuda.synchronize()
     segs = [g for g in T._graphs.values() if isinstance(g, list)]
     assert len(segs) == 2, len(segs)
@@ -73,6 +79,11 @@ def worker(rank, port, out_dir):
     assert sum(hi - lo for lo, hi in g_red) * 4 == sum(plan['generator_sections_bytes'].values())
     w2 = max(float((T.store[n] - E.store[n]).abs().max()) for n in T.store.names())
     assert w2 == 0.0, ('segmented graphs vs eager, world 2', w2)
+    # the in-line schedule of many towers: the same sectioned exchange in each of its four steps, the same weights to the bit
+    assert not L._dbwd_concurrent and L._aux_stream is None
+    assert [(lo, hi) for flat, lo, hi in l_red if flat is L.store.discriminator.grad] == [(L._d_late, dn), (0, L._d_late)] * 4
+    w3 = max(float((L.store[n] - E.store[n]).abs().max()) for n in L.store.names())
+    assert w3 == 0.0, ('passes in line vs side by side, world 2', w3)
 
     # 3. replicas
     flat = torch.cat([T.store.generator.flat, T.store.discriminator.flat]).cpu()
