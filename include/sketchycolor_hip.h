@@ -784,6 +784,23 @@ int ssc_match_loss_grad(const float* pred, int h, int w, const uint8_t* sketch, 
 int ssc_squash_project_bwd(const float* hh, int ldh, const float* w, const float* dpred, int64_t rows, int C, float* dh, float* dw,
                            float* db, float* ws, int64_t ws_bytes, void* stream);
 
+/* --- scoring a held-out caption while the matcher trains (match_val.hip): match_validation.py; DESIGN.md section 8.9 --- */
+/* One pass over the S x S pixels from pred float [h,w]; neither up nor predicts is written.  With u = the value ssc_match_finish
+ * computes for the pixel p (the same inline function: the same bits), b = sketch[3p] (sketch uint8 [S,S,3]) and
+ * z = lut[labels[p]] != 0 (labels uint8 [S,S], lut uint8 [256]), out is five 8-byte slots:
+ *   out[0] (a double)  sum over the pixels with b <= 104 of max(u,0) - u*z + log1p(exp(-|u|)): ssc_match_loss_grad's fp32 terms,
+ *                      added in double
+ *   out[1 .. 4] (int64, stored through the same pointer)  I = #{u >= 1e-9f && b != 255 && z}, P = #{u >= 1e-9f && b != 255},
+ *                      A = #{z}, live = #{b <= 104};  the union of compute_mask_IU is P + A - I
+ * A thread owns four neighbouring pixels of a row; 4-byte loads of sketch and labels when both start on a 4-byte boundary, byte
+ * loads for any other base.  Fixed-order sums (lanes, wavefronts, then a second launch of one workgroup over the workgroups'
+ * partial rows in ws), no float atomic, a grid that depends on S alone: the same bits on every run.
+ * ws: 40 bytes per workgroup of the first launch, min(2048, ceil(S*S/4 / 256)) of them (40 bytes at S = 24, 160 at 64, 23040 at 768).
+ * The domain is ssc_match_finish's (S % 4 == 0, S*S <= 2^24, 1 <= h, w <= S): -1 outside it, for a NULL pointer and for a
+ * workspace that is too small; -3 for out or ws off an 8-byte boundary (or pred off a 4-byte one) */
+int ssc_match_score(const float* pred, int h, int w, const uint8_t* sketch, const uint8_t* labels, const uint8_t* lut, int S,
+                    double* out /* [5] */, float* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,10 @@ block to <eval_result_root>/deeplab_RMI_<split>_result.txt and writes <eval_resu
 
 trains the fusion head on the frozen backbone as Instance_Matching/matching_main.py --mode train does (sketchyscenecolorization_amd/
 match_train.py): one (scene, caption) of sentence_instance_train.json per iteration, snapshots
-<snapshot_root>/deeplab_RMI_iter_<n>.tfmodel that --mode match and --mode eval read, resumed from when <snapshot_root> holds one."""
+<snapshot_root>/deeplab_RMI_iter_<n>.tfmodel that --mode match and --mode eval read, resumed from when <snapshot_root> holds one.
+--scene_cache device keeps every scene's sketch and label map on the device, --scene_cache features the frozen backbone's output
+too (sketchyscenecolorization_amd/match_cache.py); --val_freq F scores sentence_instance_val.json every F iterations with the
+weights of the moment and appends a line to <log_root>/match_validation.jsonl (match_validation.py)."""
 import argparse
 import json
 import os
@@ -65,7 +68,12 @@ TRAIN_FLAGS = [
     ('weights', str, 'deeplab', "train: 'deeplab'"),
     ('fusion_type', str, 'RMI', "train: 'RMI'"),
     ('summary', int, 0, 'train: 0; event summaries are not written'),
+    ('scene_cache', str, 'off', "train: 'off' (every iteration reads its scene's files), 'device' (every scene's sketch and label "
+                                "map on the device, read once) or 'features' (and the frozen backbone's output of every scene)"),
+    ('val_freq', int, 0, 'train: score sentence_instance_val.json every N iterations and after the last one (0: never)'),
+    ('val_scenes', int, 0, 'train: only the first N scenes of sentence_instance_val.json are scored (0: all of them)'),
 ]
+SCENE_CACHE_MODES = ('off', 'device', 'features')
 
 
 def build_parser():
@@ -177,6 +185,15 @@ def evaluate(args, config=None, predicts_out=None):
     return totals
 
 
+def validation_scenes(args):
+    """--val_freq F > 0: the scenes of sentence_instance_val.json that a pass scores; a missing caption file or ground-truth file
+    is a ValueError.  None with F = 0: the files of the val split are not looked at.  --seg_data_dir is not read."""
+    if args.val_freq == 0:
+        return None
+    from sketchyscenecolorization_amd import match_validation
+    return match_validation.validation_scenes(args.captions_base_dir, args.data_base_dir, args.val_scenes)
+
+
 def checked_train_arguments(args):
     """--mode train: every bad argument and every missing file of the whole caption file is a ValueError here, before any weight
     is read or anything is written.  -> (config, vocab, training tuples, the snapshot to resume from or None, the backbone's
@@ -200,6 +217,10 @@ def checked_train_arguments(args):
         raise ValueError('--text_len %d: at least one word' % args.text_len)
     if args.snapshot_root == '' or args.log_root == '':
         raise ValueError('--snapshot_root or --log_root is empty')
+    if args.scene_cache not in SCENE_CACHE_MODES:
+        raise ValueError("--scene_cache %r: 'off', 'device' or 'features'" % args.scene_cache)
+    if args.val_freq < 0 or args.val_scenes < 0:
+        raise ValueError('--val_freq %d, --val_scenes %d: counts, 0 for never and for every scene' % (args.val_freq, args.val_scenes))
     config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len)
     if not os.path.isfile(args.vocab_file):
         raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
@@ -232,7 +253,39 @@ def checked_train_arguments(args):
                 raise ValueError('scene %s: the caption %r holds no word' % (image_id, caption))
             if match_eval.caption_category(caption)[0] is None:
                 raise ValueError('scene %s: the caption %r names no category to add an attribute to' % (image_id, caption))
+    validation_scenes(args)
     return config, vocab, match_train.training_tuples(scenes), resume, backbone
+
+
+def build_caches(args, cfg, model, vocab, tuples):
+    """--scene_cache and --val_freq: -> (the MatchSceneCache of the train split or None, the MatchValidation or None).  What the
+    two will hold is added up first and refused as a ValueError, before anything is allocated, when it is more than half of what
+    is free on the device now."""
+    val_scenes = validation_scenes(args)
+    if args.scene_cache == 'off' and val_scenes is None:
+        return None, None
+    import torch
+    from sketchyscenecolorization_amd import match_cache, match_validation
+    train_scenes = [(image_id, None) for image_id, _caption, _idx in tuples]
+    n_train = len(match_cache.distinct_scenes(train_scenes)[0]) if args.scene_cache != 'off' else 0
+    n_val = len(match_cache.distinct_scenes(val_scenes)[0]) if val_scenes is not None else 0
+    scene_b, feat_b = match_cache.cache_bytes(n_train, cfg.size, cfg.filters[4] if args.scene_cache == 'features' else None)
+    val_b = match_cache.cache_bytes(n_val, cfg.size)[0]
+    free = torch.cuda.mem_get_info(model.device)[0]
+    remedy = 'run with --scene_cache off' if n_train else 'score fewer scenes (--val_scenes N) or none (--val_freq 0)'
+    match_cache.check_budget(scene_b + val_b, feat_b, free, remedy_scenes=remedy)
+    cache = validation = None
+    if args.scene_cache != 'off':
+        cache = match_cache.MatchSceneCache(train_scenes, args.data_base_dir, 'train', cfg.size, model.device,
+                                            features=model if args.scene_cache == 'features' else None)
+        print('scene cache: %d scenes, %d bytes of scenes and %d of features on the device, built in %.1f s'
+              % (len(cache), cache.scene_bytes, cache.feature_bytes, cache.build_seconds))
+    if val_scenes is not None:
+        validation = match_validation.MatchValidation(model, vocab, val_scenes, args.data_base_dir,
+                                                      beside=cache.nbytes if cache is not None else 0)
+        print('validation cache: %d scenes, %d captions, %d bytes on the device' % (len(validation.cache), validation.captions,
+                                                                                 validation.nbytes))
+    return cache, validation
 
 
 def train(args, config=None):
@@ -268,12 +321,17 @@ def train(args, config=None):
     print('start_iter', start)
     os.makedirs(args.log_root, exist_ok=True)
     log_path = os.path.join(args.log_root, 'match_train.jsonl')
+    cache, validation = build_caches(args, cfg, model, vocab, tuples)          # None, None with the defaults
     loss_avg, saved = 0.0, None
     for n_iter in range(start, args.max_iteration):
         image_id, caption_thin, inst_indices = tuples[cursor.next()]
         caption = match_eval.augment_caption(caption_thin, cursor.rng)
-        gt = match_eval.load_ground_truth(args.data_base_dir, 'train', image_id, cfg.size)
-        area = np.bincount(gt['labels'].reshape(-1), minlength=256)
+        if cache is None:
+            gt = match_eval.load_ground_truth(args.data_base_dir, 'train', image_id, cfg.size)
+            area = np.bincount(gt['labels'].reshape(-1), minlength=256)
+        else:       # no file is read: views of the scene's entry, and the areas that were counted when the cache was built
+            gt = cache.entry(image_id)
+            area = cache.area[cache.index[image_id]]
         lut = match_train.caption_lut(match_eval.caption_labels(image_id, inst_indices, gt['n_inst'], area))
         indices, seq_len = matching.preprocess_sentence(caption, vocab, cfg.max_len)
         lr = match_train.polynomial_decay(trainer.step_count, args.start_lr, args.end_lr, args.lr_decay_step)
@@ -285,6 +343,8 @@ def train(args, config=None):
             with open(log_path, 'a') as f:
                 f.write(json.dumps({'iter': n_iter, 'loss_cur': loss, 'loss_avg': loss_avg, 'lr': lr, 'image_id': image_id,
                                     'caption': caption}) + '\n')
+        if validation is not None and ((n_iter + 1) % args.val_freq == 0 or (n_iter + 1) >= args.max_iteration):
+            validation.run_and_log(n_iter + 1, args.log_root)
         if (n_iter + 1) % args.save_model_freq == 0 or (n_iter + 1) >= args.max_iteration:
             saved = match_train.write_snapshot(trainer, args.snapshot_root, n_iter + 1, cursor)
             print('model saved to ' + saved)

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sketchycolor_hip.h"
+#include "match_up.h"
 
 #define CHECK_LAUNCH() ((int)hipGetLastError())
 #define MAX_PIXELS (1 << 24)
@@ -203,8 +204,8 @@ extern "C" int ssc_squash_project(const float* h, int ldh, const float* w, const
 // ---------------------------------------------------------------------------------------------------------------------------
 // tf.image.resize_bilinear(pred, [S, S]) in the legacy form (align_corners = False) and predicts = (up >= 1e-9) * stroke
 // ---------------------------------------------------------------------------------------------------------------------------
-// src = dst * (in / out); lower = floor(src), upper = min(lower + 1, in - 1), the fraction weighs them: first along x on the two
-// rows, then along y.  A thread owns four neighbouring pixels of a row: one 16-byte store of up, one 4-byte store of predicts.
+// The value of a pixel is match_up.h's match_up_value, which ssc_match_score (match_val.hip) calls too.  A thread owns four
+// neighbouring pixels of a row: one 16-byte store of up, one 4-byte store of predicts.
 __global__ __launch_bounds__(256) void match_finish_kernel(const float* __restrict__ pred, int h, int w, const u8* __restrict__ stroke,
                                                            int S, float sy, float sx, float* __restrict__ up,
                                                            u8* __restrict__ predicts) {
@@ -212,23 +213,16 @@ __global__ __launch_bounds__(256) void match_finish_kernel(const float* __restri
     const long total = (long)S * q4;
     for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
         const int y = (int)(t / q4), x0 = (int)(t - (long)y * q4) * 4;
-        const float fy = (float)y * sy;
-        const int ylo = min((int)floorf(fy), h - 1);
-        const int yhi = ylo + 1 < h ? ylo + 1 : h - 1;
-        const float wy = fy - (float)ylo;
+        int ylo, yhi;
+        float wy;
+        match_up_axis(y, sy, h, ylo, yhi, wy);
         const uchar4 st = *reinterpret_cast<const uchar4*>(stroke + (long)y * S + x0);
         const u8 sb[4] = {st.x, st.y, st.z, st.w};
         float o[4];
         u8 p[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float fx = (float)(x0 + k) * sx;
-            const int xlo = min((int)floorf(fx), w - 1);
-            const int xhi = xlo + 1 < w ? xlo + 1 : w - 1;
-            const float wx = fx - (float)xlo;
-            const float tl = pred[ylo * w + xlo], tr = pred[ylo * w + xhi], bl = pred[yhi * w + xlo], br = pred[yhi * w + xhi];
-            const float top = tl + (tr - tl) * wx, bot = bl + (br - bl) * wx;
-            o[k] = top + (bot - top) * wy;
+            o[k] = match_up_value(pred, w, ylo, yhi, wy, x0 + k, sx);
             p[k] = (o[k] >= 1e-9f && sb[k] != 0) ? (u8)1 : (u8)0;
         }
         *reinterpret_cast<float4*>(up + (long)y * S + x0) = make_float4(o[0], o[1], o[2], o[3]);

@@ -261,6 +261,7 @@ SIGNATURES = {
     'ssc_instance_label_hist': [_P, _I, _P, _L, _P, _P, _I, _P, _P],
     'ssc_match_loss_grad': [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P],
     'ssc_squash_project_bwd': [_P, _I, _P, _P, _L, _I, _P, _P, _P, _P, _L, _P],
+    'ssc_match_score': [_P, _I, _I, _P, _P, _P, _I, _P, _P, _L, _P],
 }
 
 
@@ -1443,6 +1444,35 @@ def squash_project_bwd(h, w, dpred, C=None, dh=None, dw=None, db=None, ws=None):
     check(lib().ssc_squash_project_bwd(ptr(h), ldh, ptr(w), ptr(dpred), rows, C, ptr(dh), ptr(dw), ptr(db), ptr(ws),
                                        ws.numel() * ws.element_size(), stream_ptr()), 'squash_project_bwd')
     return dh, dw, db
+
+
+# ---------------------------------------------------------------------------
+# scoring a held-out caption while the matcher trains (csrc/match_val.hip; match_validation.py)
+# ---------------------------------------------------------------------------
+def match_score_workspace_bytes(s):
+    """What ssc_match_score needs: 40 bytes per workgroup of its first launch, min(2048, ceil(S*S/4 / 256)) of them."""
+    return 40 * max(1, min(2048, -(-(int(s) * (int(s) // 4)) // 256)))
+
+
+def match_score(pred, sketch_u8, labels_u8, lut_u8, out=None, ws=None):
+    """pred float [h,w]; sketch uint8 [S,S,3], labels uint8 [S,S], lut uint8 [256] -> int64 [5] on the device, unread: slot 0
+    holds the bits of a double, the class loss summed over the pixels whose first sketch byte is <= 104 (read it with
+    ``out[:1].view(torch.float64)``); slots 1 .. 4 are I, P, A and the number of those pixels, for predicts = (up >= 1e-9) on the
+    pixels whose first sketch byte is not 255 and the target lut[labels] != 0.  ``out``: a row of an int64 [n,5] buffer."""
+    h, w = pred.shape
+    s = int(labels_u8.shape[0])
+    assert pred.dtype == torch.float32 and pred.is_contiguous()
+    assert sketch_u8.dtype == torch.uint8 and sketch_u8.is_contiguous() and tuple(sketch_u8.shape) == (s, s, 3)
+    assert labels_u8.dtype == torch.uint8 and labels_u8.is_contiguous() and tuple(labels_u8.shape) == (s, s)
+    assert lut_u8.dtype == torch.uint8 and lut_u8.is_contiguous() and lut_u8.numel() == 256
+    if out is None:
+        out = torch.empty(5, dtype=torch.int64, device=pred.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == 5
+    if ws is None:
+        ws = workspace()
+    check(lib().ssc_match_score(ptr(pred), h, w, ptr(sketch_u8), ptr(labels_u8), ptr(lut_u8), s, ptr(out), ptr(ws),
+                                ws.numel() * ws.element_size(), stream_ptr()), 'match_score')
+    return out
 
 
 METRICS_TILE = (24, 32)      # rows x columns of pixels one workgroup of ssc_image_metrics_u8 / _f32 / _bg_f32 owns (csrc/metrics.hip)

@@ -374,9 +374,18 @@ class MatchTrainer(object):
         d.copy_(torch.from_numpy(labels))
         return d
 
+    def _resident(self, t, shape, dtype, what):
+        if t.device.type != self.model.device.type or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError('%s is %s %s on %s, the step reads a contiguous %s %s on %s'
+                             % (what, t.dtype, tuple(t.shape), t.device, dtype, tuple(shape), self.model.device))
+        return t
+
     def step(self, scene, lut, tok, seq_len, lr):
         """scene: {'sketch': uint8 [S,S,3], 'labels': uint8 [S,S]} (host arrays, or a dict ``upload_scene`` has been applied to:
-        'labels_d'); lut uint8 [256]; tok the sentence's max_len indices; seq_len its real length; lr the step's learning rate.
+        'labels_d'), or its device-resident form (match_cache.MatchSceneCache.entry): {'sketch_d': uint8 [S,S,3], 'labels_d':
+        uint8 [S,S]} on the device, the loss reads them where they are, and with 'feat_d' float [1,S/8,S/8,filters[4]] -- what
+        MatchModel.features gives for that sketch -- the backbone does not run; lut uint8 [256]; tok the sentence's max_len
+        indices; seq_len its real length; lr the step's learning rate.
         One iteration.  -> the class loss of the PREVIOUS step (None at the first): the value is read one step late, the step
         itself never waits for the device.  ``last_loss`` reads the current one on demand."""
         import torch
@@ -392,9 +401,17 @@ class MatchTrainer(object):
             raise ValueError('the lut holds %d bytes, not 256' % lut.shape[0])
         prev = self._take_loss((self.step_count + 1) & 1)
         slot = self.step_count & 1
-        feat, _stroke = mdl.features(scene['sketch'])
-        sketch_d = mdl._buf('sketch', (c.size, c.size, 3), torch.uint8)
-        labels_d = scene['labels_d'] if 'labels_d' in scene else self.upload_scene(scene['labels'])
+        if 'sketch_d' in scene:
+            sketch_d, labels_d = self._resident(scene['sketch_d'], (c.size, c.size, 3), torch.uint8, 'sketch_d'), \
+                self._resident(scene['labels_d'], (c.size, c.size), torch.uint8, 'labels_d')
+            if 'feat_d' in scene:       # the frozen backbone's output is given: neither the preprocessing nor the backbone runs
+                feat = self._resident(scene['feat_d'], (1, c.feat, c.feat, c.filters[4]), torch.float32, 'feat_d')
+            else:
+                feat, _stroke = mdl.features(sketch_d)
+        else:
+            feat, _stroke = mdl.features(scene['sketch'])
+            sketch_d = mdl._buf('sketch', (c.size, c.size, 3), torch.uint8)
+            labels_d = scene['labels_d'] if 'labels_d' in scene else self.upload_scene(scene['labels'])
         tok_d = mdl._buf('tok', (c.max_len,), torch.int32)
         tok_d.copy_(torch.from_numpy(idx.astype(np.int32)))
         lut_d = mdl._buf('t_lut', (256,), torch.uint8)
