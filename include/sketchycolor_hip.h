@@ -801,6 +801,25 @@ int ssc_squash_project_bwd(const float* hh, int ldh, const float* w, const float
 int ssc_match_score(const float* pred, int h, int w, const uint8_t* sketch, const uint8_t* labels, const uint8_t* lut, int S,
                     double* out /* [5] */, float* ws, int64_t ws_bytes, void* stream);
 
+/* --- the backward of the matcher's backbone (match_backbone_train.hip).  Its norms are frozen
+ * (deeplab_model.py:176-231), so relu(a*r + b) goes backward without statistics.  NHWC floats, C a multiple of 4, every pointer
+ * on a 16-byte boundary (-3), at most 2^33 - 4 floats per tensor; -1 for any other bad argument, nothing is launched then.  At an
+ * activation of exactly 0 the mask is 0.  No atomics: the same bits on every run. */
+/* dr[p, c] = g[p, c] * a[c] * (a[c]*r[p, c] + b[c] > 0), ab = [a | b] of 2C floats, M pixels.  dr may be g, never r. */
+int ssc_frozen_act_bwd(const float* g, const float* r, const float* ab, int64_t M, int C, float* dr, void* stream);
+/* the backward of ssc_residual_merge(r3, ab3, x2, ab_add, relu) from its output: m = out > 0, dr3 = g*m*a3, and
+ * d2 = g*m*a_add (ab_add given: the gradient of the projection shortcut's raw output) or g*m (ab_add NULL: the gradient of the
+ * identity shortcut).  The four tensors are distinct. */
+int ssc_unit_merge_bwd(const float* g, const float* out, const float* ab3, const float* ab_add, int64_t M, int C, float* dr3,
+                       float* d2, void* stream);
+/* the data gradient of a 1x1 SAME conv of stride 2 from that of the stride-1 conv on its lattice: src [N, h, w, C] ->
+ * out [N, H, W, C], h = ceil(H/2), w = ceil(W/2): out[n, 2y, 2x] = src[n, y, x], zero wherever a coordinate is odd */
+int ssc_zero_stuff2(const float* src, int N, int h, int w, int C, int H, int W, float* out, void* stream);
+/* the backward of ssc_max_pool3s2(r0, ab): g [N, ceil(H/2), ceil(W/2), C] -> dr0 [N, H, W, C].  Gather form: every input pixel
+ * looks at the up-to-four windows that hold it; a window's gradient goes to the first of its taps in row-major order that attains
+ * its maximum of relu(a*r0 + b), taps in the padding never take part; dr0 = (sum over those windows of g) * a * (a*r0 + b > 0) */
+int ssc_max_pool3s2_bwd(const float* g, const float* r0, const float* ab, int N, int H, int W, int C, float* dr0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,14 @@ match_train.py): one (scene, caption) of sentence_instanc
 <snapshot_root>/deeplab_RMI_iter_<n>.tfmodel that --mode match and --mode eval read, resumed from when <snapshot_root> holds one.
 --scene_cache device keeps every scene's sketch and label map on the device, --scene_cache features the frozen backbone's output
 too (sketchyscenecolorization_amd/match_cache.py); --val_freq F scores sentence_instance_val.json every F iterations with the
-weights of the moment and appends a line to <log_root>/match_validation.jsonl (match_validation.py)."""
+weights of the moment and appends a line to <log_root>/match_validation.jsonl (match_validation.py).
+
+    python match_main.py --mode train --train_backbone 1 --backbone_snapshot models/SketchyScene_DeepLabv2 \
+        --data_base_dir ../data --captions_base_dir data
+
+trains the backbone's ResNet/*/DW filters beside the head, through its frozen norms, as RMI_model.py does with
+train_fusion_var_only=False (sketchyscenecolorization_amd/match_backbone_train.py).  Its snapshots also
+hold the filters' Adam slots; --scene_cache off and device work, features does not (they would be the initial backbone's)."""
 import argparse
 import json
 import os
@@ -57,9 +64,11 @@ TRAIN_FLAGS = [
     ('start_lr', float, 2.5e-4, 'train: the learning rate at step 0'),
     ('end_lr', float, 1e-5, 'train: the learning rate from --lr_decay_step on'),
     ('lr_decay_step', int, 75000, 'train: steps of the polynomial decay (power 0.9)'),
-    ('weight_decay', float, 5e-4, 'train: the rate of the l2 regulariser on the two DW'),
+    ('weight_decay', float, 5e-4, 'train: the rate of the l2 regulariser on every trained DW'),
     ('log_root', str, 'outputs/log', 'train: where match_train.jsonl goes'),
-    ('train_fusion_var_only', int, 1, 'train: 1; training the backbone is not built'),
+    ('train_fusion_var_only', int, 1, 'train: 1; the backbone is trained with --train_backbone 1'),
+    ('train_backbone', int, 0, 'train: 1 to differentiate the backbone as well and update its ResNet/*/DW filters through the frozen '
+                               'norms (0: the fusion head alone)'),
     ('training_ignore_bg', int, 1, 'train: 1; the loss over every pixel is not built'),
     ('batch_size', int, 1, 'train: 1'),
     ('gpus', int, 1, 'train: 1'),
@@ -199,7 +208,7 @@ def checked_train_arguments(args):
     is read or anything is written.  -> (config, vocab, training tuples, the snapshot to resume from or None, the backbone's
     checkpoint prefix or None)."""
     from sketchyscenecolorization_amd import match_eval, match_train, matching
-    for name, want, why in (('train_fusion_var_only', 1, 'training the backbone is not built'),
+    for name, want, why in (('train_fusion_var_only', 1, 'the backbone is trained with --train_backbone 1'),
                             ('training_ignore_bg', 1, 'the loss over every pixel is not built'),
                             ('batch_size', 1, 'the reference trains one tuple per iteration'), ('gpus', 1, 'one device'),
                             ('graph', 0, 'the step is not captured'), ('keep_prob', 1.0, 'dropout is not built'),
@@ -219,6 +228,11 @@ def checked_train_arguments(args):
         raise ValueError('--snapshot_root or --log_root is empty')
     if args.scene_cache not in SCENE_CACHE_MODES:
         raise ValueError("--scene_cache %r: 'off', 'device' or 'features'" % args.scene_cache)
+    if args.train_backbone not in (0, 1):
+        raise ValueError('--train_backbone %d: 0 (the fusion head alone) or 1 (and the backbone)' % args.train_backbone)
+    if args.train_backbone and args.scene_cache == 'features':
+        raise ValueError('--train_backbone 1 --scene_cache features: cached features are those of the initial backbone; '
+                         'use --scene_cache device')
     if args.val_freq < 0 or args.val_scenes < 0:
         raise ValueError('--val_freq %d, --val_scenes %d: counts, 0 for never and for every scene' % (args.val_freq, args.val_scenes))
     config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len)
@@ -301,10 +315,24 @@ def train(args, config=None):
     model = matching.MatchModel(cfg)
     cursor = match_train.TupleCursor(len(tuples), random.Random(args.seed))
     start = 0
+
+    def make_trainer():
+        """--train_backbone 1: what the backward will keep is added up first, printed, and refused as a ValueError when it is more
+        than half of what is free on the device; then it is all allocated, so that the caches are budgeted beside it."""
+        if not args.train_backbone:
+            return match_train.MatchTrainer(model, args.weight_decay)
+        import torch
+        from sketchyscenecolorization_amd import match_backbone_train
+        act, scratch, slots = match_backbone_train.check_budget(cfg, torch.cuda.mem_get_info(model.device)[0])
+        print('backbone training: %d bytes of kept activations, %d of gradient scratch, %d of gradient and Adam slots on the device'
+              % (act, scratch, slots))
+        t = match_backbone_train.BackboneMatchTrainer(model, args.weight_decay)
+        t.reserve()
+        return t
     if resume is not None:
         tensors = tf_checkpoint.read_checkpoint(resume)
         model.load_dict(tensors)
-        trainer = match_train.MatchTrainer(model, args.weight_decay)
+        trainer = make_trainer()
         start = match_train.snapshot_iteration(resume)
         trainer.load_slots(tensors, start)
         with open(resume + '.train_state.json') as f:
@@ -315,7 +343,7 @@ def train(args, config=None):
         variables = {k: v for k, v in have.items() if k.startswith('ResNet/')}
         variables.update(match_train.init_head(cfg, args.seed))
         model.load_dict(variables)
-        trainer = match_train.MatchTrainer(model, args.weight_decay)
+        trainer = make_trainer()
         print('firstly train, loaded', backbone)
     print('%d tuples of data.' % len(tuples))
     print('start_iter', start)

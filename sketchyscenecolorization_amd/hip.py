@@ -262,6 +262,10 @@ SIGNATURES = {
     'ssc_match_loss_grad': [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P],
     'ssc_squash_project_bwd': [_P, _I, _P, _P, _L, _I, _P, _P, _P, _P, _L, _P],
     'ssc_match_score': [_P, _I, _I, _P, _P, _P, _I, _P, _P, _L, _P],
+    'ssc_frozen_act_bwd': [_P, _P, _P, _L, _I, _P, _P],
+    'ssc_unit_merge_bwd': [_P, _P, _P, _P, _L, _I, _P, _P, _P],
+    'ssc_zero_stuff2': [_P, _I, _I, _I, _I, _I, _I, _P, _P],
+    'ssc_max_pool3s2_bwd': [_P, _P, _P, _I, _I, _I, _I, _P, _P],
 }
 
 
@@ -1304,6 +1308,52 @@ def batch_to_space(x, r, out=None):
         out = torch.empty((n, h * r, w * r, c), dtype=torch.float32, device=x.device)
     assert out.is_contiguous() and tuple(out.shape) == (n, h * r, w * r, c), tuple(out.shape)
     check(lib().ssc_batch_to_space(ptr(x), n, h * r, w * r, c, r, ptr(out), stream_ptr()), 'batch_to_space')
+    return out
+
+
+def _f32c(*ts):
+    return all(t.dtype == torch.float32 and t.is_contiguous() for t in ts)
+
+
+def frozen_act_bwd(g, r, ab, out=None):
+    """The backward of relu(a*r + b) with a frozen [a | b]: g, r float [..., C] -> dr = g * a * (a*r + b > 0).  ``out`` may be g."""
+    c = r.shape[-1]
+    if out is None:
+        out = torch.empty_like(r)
+    assert _f32c(g, r, ab, out) and g.shape == r.shape == out.shape and ab.numel() == 2 * c, (tuple(g.shape), tuple(r.shape))
+    check(lib().ssc_frozen_act_bwd(ptr(g), ptr(r), ptr(ab), r.numel() // c, c, ptr(out), stream_ptr()), 'frozen_act_bwd')
+    return out
+
+
+def unit_merge_bwd(g, out, ab3, ab_add=None, dr3=None, d2=None):
+    """The backward of a bottleneck unit's closing relu(a3*r3 + b3 + shortcut) from its output ``out``: -> (dr3 = g*m*a3,
+    d2 = g*m*a_add with ab_add -- the projection shortcut's raw output -- or g*m without: the identity shortcut), m = out > 0."""
+    c = out.shape[-1]
+    dr3 = torch.empty_like(out) if dr3 is None else dr3
+    d2 = torch.empty_like(out) if d2 is None else d2
+    assert _f32c(g, out, ab3, dr3, d2) and g.shape == out.shape == dr3.shape == d2.shape and ab3.numel() == 2 * c
+    assert ab_add is None or (_f32c(ab_add) and ab_add.numel() == 2 * c)
+    check(lib().ssc_unit_merge_bwd(ptr(g), ptr(out), ptr(ab3), ptr(ab_add), out.numel() // c, c, ptr(dr3), ptr(d2), stream_ptr()),
+          'unit_merge_bwd')
+    return dr3, d2
+
+
+def zero_stuff2(src, out):
+    """src float [N,h,w,C] -> out [N,H,W,C] with h = ceil(H/2), w = ceil(W/2): out[:, ::2, ::2] = src, zero elsewhere."""
+    n, h, w, c = src.shape
+    assert _f32c(src, out) and out.dim() == 4 and out.shape[0] == n and out.shape[3] == c, (tuple(src.shape), tuple(out.shape))
+    check(lib().ssc_zero_stuff2(ptr(src), n, h, w, c, out.shape[1], out.shape[2], ptr(out), stream_ptr()), 'zero_stuff2')
+    return out
+
+
+def max_pool3s2_bwd(g, r0, ab, out=None):
+    """The backward of max_pool3s2(r0, ab): g float [N, ceil(H/2), ceil(W/2), C] -> d r0 [N,H,W,C]."""
+    n, h, w, c = r0.shape
+    if out is None:
+        out = torch.empty_like(r0)
+    assert _f32c(g, r0, ab, out) and tuple(g.shape) == (n, (h + 1) // 2, (w + 1) // 2, c) and out.shape == r0.shape, tuple(g.shape)
+    assert ab.numel() == 2 * c
+    check(lib().ssc_max_pool3s2_bwd(ptr(g), ptr(r0), ptr(ab), n, h, w, c, ptr(out), stream_ptr()), 'max_pool3s2_bwd')
     return out
 
 

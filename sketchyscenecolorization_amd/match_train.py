@@ -12,8 +12,10 @@ The trained parameters are the head's entries of MatchModel.flat, in the device 
 by gate blocks); the gradient and the two Adam slots are buffers of that layout.  A padded entry has a zero gradient by
 construction and Adam leaves a zero with zero moments at zero.
 
-Not here: training the backbone, training_ignore_bg = False, the other backbones, attention, dropout, summaries, batches, several
-devices, a captured step."""
+Training the backbone's filters as well: match_backbone_train.py, a subclass of the trainer here.
+
+Not here: training_ignore_bg = False, the other backbones, attention, dropout, summaries, batches, several devices, a captured
+step."""
 import json
 import os
 import random
@@ -258,8 +260,9 @@ class MatchTrainer(object):
         return pred.view(fh, fw)
 
     # ------------------------------------------------------------------ backward
-    def backward(self, dpred):
-        """dpred float [h,w]: the gradient on ``head_train``'s pred.  Fills the gradient of every trained tensor (device layout);
+    def backward(self, dpred, dfeat=None):
+        """dpred float [h,w]: the gradient on ``head_train``'s pred.  Fills the gradient of every trained tensor (device layout).
+        dfeat float [1,h,w,filters[4]]: receives the gradient on ``head_train``'s feat (match_backbone_train.py); without it
         nothing goes into the backbone."""
         import torch
         from . import hip
@@ -337,6 +340,8 @@ class MatchTrainer(object):
         hip.conv_wgrad(View(x['feat']), View(dvp.view(1, x['fh'], x['fw'], c.v_emb)), g['vproj/w'], 1, 0)
         hip.join_wgrad()
         hip.call('ssc_group_rowsum', dvp, c.v_emb, 1, R, c.v_emb, g['vproj/b'], 0)
+        if dfeat is not None:       # d feat = dvp . DW^T
+            hip.matmul_nt(dvp, d['vproj/w'].view(c.filters[4], c.v_emb), dfeat.view(R, c.filters[4]))
 
     # ------------------------------------------------------------------ loss, optimiser
     def loss_and_grad(self, pred, sketch_d, labels_d, lut_d, slot=0):
@@ -407,9 +412,9 @@ class MatchTrainer(object):
             if 'feat_d' in scene:       # the frozen backbone's output is given: neither the preprocessing nor the backbone runs
                 feat = self._resident(scene['feat_d'], (1, c.feat, c.feat, c.filters[4]), torch.float32, 'feat_d')
             else:
-                feat, _stroke = mdl.features(sketch_d)
+                feat = self._features(sketch_d)
         else:
-            feat, _stroke = mdl.features(scene['sketch'])
+            feat = self._features(scene['sketch'])
             sketch_d = mdl._buf('sketch', (c.size, c.size, 3), torch.uint8)
             labels_d = scene['labels_d'] if 'labels_d' in scene else self.upload_scene(scene['labels'])
         tok_d = mdl._buf('tok', (c.max_len,), torch.int32)
@@ -427,6 +432,11 @@ class MatchTrainer(object):
         self.backward(dpred)
         self.apply(lr)
         return prev
+
+    def _features(self, sketch):
+        """The visual feature of a sketch for ``step``: the frozen backbone's (match_backbone_train.py keeps what its backward
+        needs instead)."""
+        return self.model.features(sketch)[0]
 
     def _take_loss(self, slot):
         ev = self._loss_event[slot]
