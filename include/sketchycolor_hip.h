@@ -820,6 +820,23 @@ int ssc_zero_stuff2(const float* src, int N, int h, int w, int C, int H, int W, 
  * its maximum of relu(a*r0 + b), taps in the padding never take part; dr0 = (sum over those windows of g) * a * (a*r0 + b > 0) */
 int ssc_max_pool3s2_bwd(const float* g, const float* r0, const float* ab, int N, int H, int W, int C, float* dr0, void* stream);
 
+/* --- the matcher's word attention (match_attn.hip): RMI_model.py:202-217 with use_attn; DESIGN.md section 8.11 --- */
+/* attn[t] = softmax over t < T of (t < L ? sum_c hs[t*ld+c]*w[c] : 0) + b[0].  The rows >= L of hs are not read.  One workgroup,
+ * fixed summation order.  -1 for L < 1, L > T, T > 64, ld < C */
+int ssc_attn_scores_fwd(const float* hs, int ld, const float* w, const float* b, int C, int L, int T, float* attn, void* stream);
+/* y[i] = fmaf(s[k], x[i], overwrite ? 0 : y[i]) for i < n: ssc_axpy with the scale read from device memory (s holds ns floats;
+ * -1 for k outside of them) */
+int ssc_dev_scaled_add(float* y, const float* x, const float* s, int ns, int k, int64_t n, int overwrite, void* stream);
+/* dattn[t] = sum_i dacc[i]*H[t*stride+i] for t < L (<= 64), i < n: float64 partial sums in two stages of a fixed order through
+ * ws (8-byte aligned, L * min(512, ceil(n / 4096)) doubles), rounded to float once; no atomics */
+int ssc_attn_plane_dots(const float* dacc, const float* H, int64_t stride, int64_t n, int L, float* dattn, float* ws,
+                        int64_t ws_bytes, void* stream);
+/* The backward of ssc_attn_scores_fwd: dlogit[t] = attn[t]*((t < L ? dattn[t] : 0) - sum_{s<L} attn[s]*dattn[s]) for t < T;
+ * dw[c] = sum_{t<L} dlogit[t]*hs[t*ld+c]; db[0] = sum_{t<T} dlogit[t] in index order; dhs[t*ldd+c] += dlogit[t]*w[c] for t < L,
+ * c < C.  One workgroup; the rows >= L of hs, dattn and dhs are not touched */
+int ssc_attn_scores_bwd(const float* attn, const float* dattn, const float* hs, int ld, const float* w, int C, int L, int T,
+                        float* dlogit, float* dw, float* db, float* dhs, int ldd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

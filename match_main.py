@@ -29,7 +29,11 @@ weights of the moment and appends a line to <log_root>/match_validation.jsonl (m
 
 trains the backbone's ResNet/*/DW filters beside the head, through its frozen norms, as RMI_model.py does with
 train_fusion_var_only=False (sketchyscenecolorization_amd/match_backbone_train.py).  Its snapshots also
-hold the filters' Adam slots; --scene_cache off and device work, features does not (they would be the initial backbone's)."""
+hold the filters' Adam slots; --scene_cache off and device work, features does not (they would be the initial backbone's).
+
+--use_attn 1, in every mode, is the model class's use_attn (RMI_model.py:202-217): a softmax over the word
+LSTM's outputs weighs the multimodal LSTM's outputs of every word.  --mode train then also trains attn_fc/DW and attn_fc/biases,
+--mode match writes the weights into match.json as "attention"; a snapshot is read with the flag it was trained with."""
 import argparse
 import json
 import os
@@ -44,6 +48,8 @@ FLAGS = [
     ('image_id', str, None, 'the scene'),
     ('instruction', str, '', "e.g. 'the bus on the left is yellow'"),
     ('results_dir', str, 'outputs/match_results', 'where <id>/match.json and <id>/<id>_match.png go'),
+    ('use_attn', int, 0, "1: the head with the model class's word attention (use_attn of RMI_model.py), for a checkpoint trained "
+                         'with it, and to train one; match.json then holds the weights as "attention"'),
 ]
 EVAL_FLAGS = [
     ('data_base_dir', str, '../data', 'eval: the SketchyScene data, with <split>/INSTANCE_GT and <split>/DRAWING_GT'),
@@ -75,7 +81,7 @@ TRAIN_FLAGS = [
     ('graph', int, 0, 'train: 0; the step is not captured'),
     ('keep_prob', float, 1.0, 'train: 1; dropout is not built'),
     ('weights', str, 'deeplab', "train: 'deeplab'"),
-    ('fusion_type', str, 'RMI', "train: 'RMI'"),
+    ('fusion_type', str, 'RMI', "train: 'RMI'; 'RecurAttn' is not built (the attention that is built is --use_attn 1)"),
     ('summary', int, 0, 'train: 0; event summaries are not written'),
     ('scene_cache', str, 'off', "train: 'off' (every iteration reads its scene's files), 'device' (every scene's sketch and label "
                                 "map on the device, read once) or 'features' (and the frozen backbone's output of every scene)"),
@@ -83,6 +89,30 @@ TRAIN_FLAGS = [
     ('val_scenes', int, 0, 'train: only the first N scenes of sentence_instance_val.json are scored (0: all of them)'),
 ]
 SCENE_CACHE_MODES = ('off', 'device', 'features')
+
+
+def checked_use_attn(args):
+    """--use_attn: 0 or 1, anything else is a ValueError."""
+    if args.use_attn not in (0, 1):
+        raise ValueError('--use_attn %d: 0 (the last state feeds the projection) or 1 (the attention-weighted sum of every '
+                         "word's state)" % args.use_attn)
+    return bool(args.use_attn)
+
+
+def checked_snapshot_attention(prefix, use_attn):
+    """The snapshot's variable names against --use_attn, read from its index alone: MatchModel.load_dict's refusal, before
+    anything is allocated."""
+    from sketchyscenecolorization_amd import matching, tf_checkpoint
+    matching.check_attention_variables({name for name, _shape, _dtype in tf_checkpoint.list_variables(prefix)}, use_attn)
+
+
+def agreed_config(config, cfg):
+    """A ``config`` handed to ``main`` must be what the flags say: -> config.  ValueError otherwise."""
+    if (config.size, config.vocab_size, config.max_len) != (cfg.size, cfg.vocab_size, cfg.max_len):
+        raise ValueError('the given configuration and --scene_size / --vocab_size / --text_len disagree')
+    if bool(getattr(config, 'use_attn', False)) != cfg.use_attn:
+        raise ValueError('the given configuration has use_attn %r, --use_attn is %d' % (config.use_attn, int(cfg.use_attn)))
+    return config
 
 
 def build_parser():
@@ -102,9 +132,10 @@ def checked_arguments(args):
         raise ValueError('--snapshot <directory or checkpoint prefix> is needed: the matcher has no weights of its own')
     if args.image_id is None or args.image_id == '' or args.instruction == '':
         raise ValueError("--image_id <id> and --instruction '<text>' are needed")
+    use_attn = checked_use_attn(args)
     if args.text_len < 1:
         raise ValueError('--text_len %d: at least one word' % args.text_len)
-    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len)
+    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn)
     if not matching.sentence_tokens(args.instruction):
         raise ValueError('--instruction %r holds no word' % args.instruction)
     if not os.path.isfile(args.vocab_file):
@@ -114,6 +145,7 @@ def checked_arguments(args):
         raise ValueError('--vocab_file %r holds %d words, --vocab_size is %d; <unk> and <pad> must be among them'
                          % (args.vocab_file, len(vocab), args.vocab_size))
     prefix = matching.resolve_snapshot(args.snapshot)
+    checked_snapshot_attention(prefix, use_attn)
     for sub, name in (('sketches', args.image_id + '.png'), ('inner_masks', args.image_id + '.mat'),
                       ('seg_data', args.image_id + '_datas.npz')):
         if not os.path.isfile(os.path.join(args.scene_dir, sub, name)):
@@ -131,13 +163,14 @@ def checked_eval_arguments(args):
         raise ValueError("--dataset %r: 'val' or 'test'" % args.dataset)
     if args.mask_ap not in (0, 1):
         raise ValueError('--mask_ap %d: 0 or 1' % args.mask_ap)
+    use_attn = checked_use_attn(args)
     if args.max_scenes < 0:
         raise ValueError('--max_scenes %d: a count, 0 for every scene' % args.max_scenes)
     if args.text_len < 1:
         raise ValueError('--text_len %d: at least one word' % args.text_len)
     if args.eval_result_root == '':
         raise ValueError('--eval_result_root is empty')
-    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len)
+    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn)
     if not os.path.isfile(args.vocab_file):
         raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
     vocab = matching.load_vocab(args.vocab_file)
@@ -145,6 +178,7 @@ def checked_eval_arguments(args):
         raise ValueError('--vocab_file %r holds %d words, --vocab_size is %d; <unk> and <pad> must be among them'
                          % (args.vocab_file, len(vocab), args.vocab_size))
     prefix = matching.resolve_snapshot(args.snapshot)
+    checked_snapshot_attention(prefix, use_attn)
     scenes = match_eval.read_captions(args.captions_base_dir, args.dataset)
     if args.max_scenes:
         scenes = scenes[:args.max_scenes]
@@ -167,9 +201,7 @@ def evaluate(args, config=None, predicts_out=None):
     """--mode eval.  ``predicts_out``: a path that receives every caption's predicts, uint8 [captions, S, S], as .npy."""
     cfg, prefix, vocab, scenes = checked_eval_arguments(args)
     if config is not None:
-        if (config.size, config.vocab_size, config.max_len) != (cfg.size, cfg.vocab_size, cfg.max_len):
-            raise ValueError('the given configuration and --scene_size / --vocab_size / --text_len disagree')
-        cfg = config
+        cfg = agreed_config(config, cfg)
     import random
     import numpy as np
     from sketchyscenecolorization_amd import match_eval, matching
@@ -213,7 +245,7 @@ def checked_train_arguments(args):
                             ('batch_size', 1, 'the reference trains one tuple per iteration'), ('gpus', 1, 'one device'),
                             ('graph', 0, 'the step is not captured'), ('keep_prob', 1.0, 'dropout is not built'),
                             ('weights', 'deeplab', 'the other backbones are not built'),
-                            ('fusion_type', 'RMI', 'attention is not built'), ('summary', 0, 'event summaries are not written')):
+                            ('fusion_type', 'RMI', "'RecurAttn' is not built; the attention that is built is --use_attn 1"), ('summary', 0, 'event summaries are not written')):
         if getattr(args, name) != want:
             raise ValueError('--%s %r: only %r (%s)' % (name, getattr(args, name), want, why))
     if args.max_iteration < 1 or args.save_model_freq < 1 or args.log_freq < 1:
@@ -235,7 +267,8 @@ def checked_train_arguments(args):
                          'use --scene_cache device')
     if args.val_freq < 0 or args.val_scenes < 0:
         raise ValueError('--val_freq %d, --val_scenes %d: counts, 0 for never and for every scene' % (args.val_freq, args.val_scenes))
-    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len)
+    use_attn = checked_use_attn(args)
+    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn)
     if not os.path.isfile(args.vocab_file):
         raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
     vocab = matching.load_vocab(args.vocab_file)
@@ -251,6 +284,7 @@ def checked_train_arguments(args):
         match_train.snapshot_iteration(resume)
         if not os.path.isfile(resume + '.train_state.json'):
             raise ValueError('%s.train_state.json: no such file; the snapshot cannot be resumed from' % resume)
+        checked_snapshot_attention(resume, use_attn)        # a resume goes on with the head the snapshot was trained with
     else:
         if args.backbone_snapshot == '':
             raise ValueError('--backbone_snapshot <directory or checkpoint prefix> is needed: a fresh run takes ResNet/* from it')
@@ -306,9 +340,7 @@ def train(args, config=None):
     """--mode train."""
     cfg, vocab, tuples, resume, backbone = checked_train_arguments(args)
     if config is not None:
-        if (config.size, config.vocab_size, config.max_len) != (cfg.size, cfg.vocab_size, cfg.max_len):
-            raise ValueError('the given configuration and --scene_size / --vocab_size / --text_len disagree')
-        cfg = config
+        cfg = agreed_config(config, cfg)
     import random
     import numpy as np
     from sketchyscenecolorization_amd import match_eval, match_train, matching, tf_checkpoint
@@ -392,9 +424,7 @@ def main(argv=None, config=None, predicts_out=None):
         raise ValueError("--mode %r: 'match', 'eval' or 'train'" % args.mode)
     cfg, prefix, vocab = checked_arguments(args)
     if config is not None:
-        if (config.size, config.vocab_size, config.max_len) != (cfg.size, cfg.vocab_size, cfg.max_len):
-            raise ValueError('the given configuration and --scene_size / --vocab_size / --text_len disagree')
-        cfg = config
+        cfg = agreed_config(config, cfg)
     import numpy as np
     from PIL import Image
     from sketchyscenecolorization_amd import fg_scene, matching
@@ -410,6 +440,8 @@ def main(argv=None, config=None, predicts_out=None):
               'matched_inst_indices': matched,
               'occupancy': [None if s != s else float(s) for s in scores.tolist()],
               'class_ids': [int(c) for c in np.asarray(scene['class_ids']).reshape(-1)], 'snapshot': prefix}
+    if cfg.use_attn:        # the weights of all --text_len positions, the padded ones included
+        record['attention'] = [float(a) for a in info['attention']]
     with open(os.path.join(out_dir, 'match.json'), 'w') as f:
         json.dump(record, f, indent=1)
     Image.fromarray((info['predicts'] != 0).astype(np.uint8) * 255).save(os.path.join(out_dir, '%s_match.png' % args.image_id))

@@ -266,6 +266,10 @@ SIGNATURES = {
     'ssc_unit_merge_bwd': [_P, _P, _P, _P, _L, _I, _P, _P, _P],
     'ssc_zero_stuff2': [_P, _I, _I, _I, _I, _I, _I, _P, _P],
     'ssc_max_pool3s2_bwd': [_P, _P, _P, _I, _I, _I, _I, _P, _P],
+    'ssc_attn_scores_fwd': [_P, _I, _P, _P, _I, _I, _I, _P, _P],
+    'ssc_dev_scaled_add': [_P, _P, _P, _I, _I, _L, _I, _P],
+    'ssc_attn_plane_dots': [_P, _P, _L, _L, _I, _P, _P, _L, _P],
+    'ssc_attn_scores_bwd': [_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
 }
 
 
@@ -1494,6 +1498,86 @@ def squash_project_bwd(h, w, dpred, C=None, dh=None, dw=None, db=None, ws=None):
     check(lib().ssc_squash_project_bwd(ptr(h), ldh, ptr(w), ptr(dpred), rows, C, ptr(dh), ptr(dw), ptr(db), ptr(ws),
                                        ws.numel() * ws.element_size(), stream_ptr()), 'squash_project_bwd')
     return dh, dw, db
+
+
+# ---------------------------------------------------------------------------
+# the matcher's word attention (csrc/match_attn.hip; matching.py, match_train.py)
+# ---------------------------------------------------------------------------
+ATTN_MAX_T = 64         # words a sentence may have for the attention kernels (csrc/match_attn.hip)
+
+
+def _refused(rc, what, why):
+    """An argument check of an entry point (-1) is the caller's mistake: a ValueError; anything else goes through ``check``."""
+    if rc == -1:
+        raise ValueError('%s refused its arguments: %s' % (what, why))
+    check(rc, what)
+
+
+def attn_scores_fwd(hs, w, b, C, L, out=None):
+    """hs float [>= L, ld]: the word LSTM's outputs, of which only the first L rows are read; w float [>= C], b float [1] ->
+    attn float [T] = softmax over all T positions of (t < L ? <hs[t, :C], w> : 0) + b.  T = out.numel() (hs.shape[0] without
+    ``out``).  ValueError for L < 1, L > T or T > ATTN_MAX_T."""
+    ld = int(hs.shape[1])
+    assert hs.dtype == torch.float32 and hs.is_contiguous() and w.is_contiguous() and w.numel() >= C and b.numel() >= 1
+    if out is None:
+        out = torch.empty(hs.shape[0], dtype=torch.float32, device=hs.device)
+    T = out.numel()
+    assert out.is_contiguous() and hs.shape[0] >= min(int(L), T)
+    _refused(lib().ssc_attn_scores_fwd(ptr(hs), ld, ptr(w), ptr(b), int(C), int(L), T, ptr(out), stream_ptr()), 'attn_scores_fwd',
+             'L = %d of T = %d words (at most %d), C = %d of ld = %d' % (L, T, ATTN_MAX_T, C, ld))
+    return out
+
+
+def dev_scaled_add(y, x, s, k, overwrite=False):
+    """y = (0 if overwrite else y) + s[k] * x, one fmaf per element; s stays on the device, nothing waits for it.  ValueError
+    for a k outside s."""
+    n = x.numel()
+    assert y.dtype == x.dtype == s.dtype == torch.float32 and y.is_contiguous() and x.is_contiguous() and s.is_contiguous()
+    assert y.numel() == n
+    _refused(lib().ssc_dev_scaled_add(ptr(y), ptr(x), ptr(s), s.numel(), int(k), n, int(bool(overwrite)), stream_ptr()),
+             'dev_scaled_add', 'scale %d of %d, %d elements' % (k, s.numel(), n))
+    return y
+
+
+def attn_plane_dots_workspace_bytes(n, L):
+    """What ssc_attn_plane_dots needs: a double per plane and workgroup of its first stage, min(512, ceil(n / 4096)) per plane."""
+    return 8 * int(L) * max(1, min(512, -(-int(n) // 4096)))
+
+
+def attn_plane_dots(dacc, planes, L, out=None, ws=None):
+    """dacc float [n] (any shape), planes float [>= L, n] (any shape behind the first axis) -> dattn float [L] =
+    <dacc, planes[t]>, summed in float64 in a fixed order: the same bits on every run.  ValueError for L < 1 or L > ATTN_MAX_T."""
+    n = dacc.numel()
+    assert dacc.dtype == planes.dtype == torch.float32 and dacc.is_contiguous() and planes.is_contiguous()
+    assert planes.shape[0] >= min(int(L), ATTN_MAX_T) and planes[0].numel() == n
+    if out is None:
+        out = torch.empty(max(int(L), 1), dtype=torch.float32, device=dacc.device)
+    assert out.is_contiguous() and out.numel() >= L
+    if ws is None:
+        ws = workspace()
+    _refused(lib().ssc_attn_plane_dots(ptr(dacc), ptr(planes), n, n, int(L), ptr(out), ptr(ws), ws.numel() * ws.element_size(),
+                                       stream_ptr()), 'attn_plane_dots', 'L = %d planes (at most %d) of %d' % (L, ATTN_MAX_T, n))
+    return out
+
+
+def attn_scores_bwd(attn, dattn, hs, w, C, L, dhs, dw=None, db=None, dlogit=None):
+    """The backward of attn_scores_fwd: attn float [T], dattn float [>= L] -> (dlogit [T], dw [C] written into the first C entries
+    of ``dw``, db [1]); dhs float [>= L, ldd] receives += dlogit[t] * w on its first L rows and C columns.  ValueError for
+    L < 1, L > T or T > ATTN_MAX_T."""
+    T, ld, ldd = attn.numel(), int(hs.shape[1]), int(dhs.shape[1])
+    assert attn.is_contiguous() and dattn.is_contiguous() and dattn.numel() >= min(int(L), T) and hs.is_contiguous() and dhs.is_contiguous()
+    assert w.is_contiguous() and w.numel() >= C and hs.shape[0] >= min(int(L), T) and dhs.shape[0] >= min(int(L), T)
+    if dw is None:
+        dw = torch.empty(C, dtype=torch.float32, device=attn.device)
+    if db is None:
+        db = torch.empty(1, dtype=torch.float32, device=attn.device)
+    if dlogit is None:
+        dlogit = torch.empty(T, dtype=torch.float32, device=attn.device)
+    assert dw.is_contiguous() and dw.numel() >= C and db.numel() >= 1 and dlogit.is_contiguous() and dlogit.numel() >= T
+    _refused(lib().ssc_attn_scores_bwd(ptr(attn), ptr(dattn), ptr(hs), ld, ptr(w), int(C), int(L), T, ptr(dlogit), ptr(dw), ptr(db),
+                                       ptr(dhs), ldd, stream_ptr()), 'attn_scores_bwd',
+             'L = %d of T = %d words (at most %d), C = %d of ld = %d / %d' % (L, T, ATTN_MAX_T, C, ld, ldd))
+    return dlogit, dw, db
 
 
 # ---------------------------------------------------------------------------

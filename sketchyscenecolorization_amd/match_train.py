@@ -14,8 +14,14 @@ construction and Adam leaves a zero with zero moments at zero.
 
 Training the backbone's filters as well: match_backbone_train.py, a subclass of the trainer here.
 
-Not here: training_ignore_bg = False, the other backbones, attention, dropout, summaries, batches, several devices, a captured
-step."""
+MatchConfig(use_attn=True): attn_fc/DW and attn_fc/biases are trained too.  head_train accumulates the
+weighted sum of the multimodal outputs as MatchModel.head does; backward sends the projection's gradient into that sum, injects
+attn[t] times it into every step of the multimodal cell's BPTT (ssc_dev_scaled_add), takes the weights' gradient as L dots over
+the kept outputs (ssc_attn_plane_dots) and goes through the softmax into the two variables and the word cell's incoming gradient
+(ssc_attn_scores_bwd).  The bias shifts every logit alike: it is a free parameter, its exact gradient is 0.
+
+Not here: training_ignore_bg = False, the other backbones, fusion_type 'RecurAttn', dropout, summaries, batches, several devices,
+a captured step."""
 import json
 import os
 import random
@@ -62,15 +68,18 @@ def adam_step_size(lr, t):
 
 def init_head(config, seed=0):
     """{checkpoint name: float32 array} of a fresh head, the reference's initialisers drawn from numpy.random.RandomState(seed):
-    Xavier-uniform for the two DW, uniform +-0.08 for the embedding, Glorot-uniform for the LSTM kernels, zero biases.  (TF's
-    own random streams are not reproduced.)"""
+    Xavier-uniform for the two DW, uniform +-0.08 for the embedding, Glorot-uniform for the LSTM kernels, zero biases; with
+    use_attn uniform_unit_scaling_initializer(factor=1.0), +-sqrt(3 / w_rnn), for attn_fc/DW, drawn last.  (TF's own random
+    streams are not reproduced.)"""
     rng = np.random.RandomState(seed)
     out = {}
     shapes = config.variable_shapes()
     for name in head_variable_names(config):
         shape = shapes[name]
         leaf = name.rsplit('/', 1)[1]
-        if leaf == 'DW':
+        if leaf == 'DW' and len(shape) == 2:
+            v = rng.uniform(-1, 1, shape) * np.sqrt(3.0 / shape[0])
+        elif leaf == 'DW':
             v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[2] + shape[3]))
         elif leaf == 'kernel':
             v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[0] + shape[1]))
@@ -103,6 +112,9 @@ def pack_head(config, host):
     dev['m/Kl'], dev['m/Ks'] = matching.pad_rows(kx[o:o + c.w_rnn], cw), kx[o + c.w_rnn:]
     dev['proj/w'] = matching.pad_rows(np.asarray(host[HEAD + 'm_lstm_output_projection/DW']).reshape(-1), cm)
     dev['proj/b'] = host[HEAD + 'm_lstm_output_projection/biases']
+    if c.use_attn:
+        dev['attn/w'] = matching.pad_rows(np.asarray(host[HEAD + 'attn_fc/DW']).reshape(-1), cw)
+        dev['attn/b'] = host[HEAD + 'attn_fc/biases']
     return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in dev.items()}
 
 
@@ -122,6 +134,9 @@ def unpack_head(config, dev):
     out[HEAD + 'mLSTM/lstm_cell/bias'] = unpad_gate_columns(d['m/b'], c.m_rnn, cm)
     out[HEAD + 'm_lstm_output_projection/DW'] = d['proj/w'][:c.m_rnn].reshape(1, 1, c.m_rnn, 1)
     out[HEAD + 'm_lstm_output_projection/biases'] = d['proj/b'].reshape(1)
+    if c.use_attn:
+        out[HEAD + 'attn_fc/DW'] = d['attn/w'][:c.w_rnn].reshape(c.w_rnn, 1)
+        out[HEAD + 'attn_fc/biases'] = d['attn/b'].reshape(1)
     return {k: np.array(v, dtype=np.float32, order='C', copy=True) for k, v in out.items()}
 
 
@@ -134,6 +149,17 @@ DEVICE_TO_VARIABLE = {
     'proj/w': 'm_lstm_output_projection/DW', 'proj/b': 'm_lstm_output_projection/biases',
 }
 HEAD_DEVICE_NAMES = tuple(DEVICE_TO_VARIABLE)
+ATTN_DEVICE_TO_VARIABLE = {'attn/w': 'attn_fc/DW', 'attn/b': 'attn_fc/biases'}      # use_attn: behind proj/b
+
+
+def device_to_variable(config):
+    """DEVICE_TO_VARIABLE of a configuration: with use_attn the attention's two tensors behind the others."""
+    return dict(DEVICE_TO_VARIABLE, **ATTN_DEVICE_TO_VARIABLE) if config.use_attn else dict(DEVICE_TO_VARIABLE)
+
+
+def head_device_names(config):
+    """HEAD_DEVICE_NAMES of a configuration, in the flat buffer's order."""
+    return tuple(device_to_variable(config))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -192,17 +218,19 @@ class MatchTrainer(object):
         self.model, self.cfg = model, model.cfg
         self.weight_decay = float(weight_decay)
         lay = model._layout
-        assert [n for n in lay if n in DEVICE_TO_VARIABLE] == list(HEAD_DEVICE_NAMES), list(lay)
-        self.lo, self.hi = lay[HEAD_DEVICE_NAMES[0]][0], lay['spatial'][0]
+        self.dev_to_var = device_to_variable(self.cfg)
+        self.names = names = head_device_names(self.cfg)
+        assert [n for n in lay if n in self.dev_to_var] == list(names), list(lay)
+        self.lo, self.hi = lay[names[0]][0], lay['spatial'][0]
         # the head is one stretch of the flat buffer: every trained tensor in it, nothing else
         inside = [n for n, (o, _s) in lay.items() if self.lo <= o < self.hi]
-        assert inside == list(HEAD_DEVICE_NAMES), inside
+        assert inside == list(names), inside
         self.params = model.flat[self.lo:self.hi]
         self.grad, self.adam_m, self.adam_v = (torch.zeros(self.hi - self.lo, dtype=torch.float32, device=model.device) for _ in range(3))
         self.spans = {}
-        for k, name in enumerate(HEAD_DEVICE_NAMES):
+        for k, name in enumerate(names):
             o, shape = lay[name]
-            end = lay[HEAD_DEVICE_NAMES[k + 1]][0] if k + 1 < len(HEAD_DEVICE_NAMES) else self.hi
+            end = lay[names[k + 1]][0] if k + 1 < len(names) else self.hi
             self.spans[name] = (o - self.lo, int(np.prod(shape)), end - o, shape)          # offset, real size, padded size
         self.g, self.m, self.v = ({n: buf[o:o + size].view(shape) for n, (o, size, _p, shape) in self.spans.items()}
                                   for buf in (self.grad, self.adam_m, self.adam_v))
@@ -242,6 +270,10 @@ class MatchTrainer(object):
             hip.lstm_step_fwd(hs[t], d['w/Kh'], 4 * cw, ew[t:t + 1], None, 1, one, 1, cs[t], 1, cw, t > 0, cs[t + 1], hs[t + 1],
                               acts_w[t:t + 1], hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1],
                               hp_out=None if hp is None else hp[t & 1])
+        attn = acc = None
+        if c.use_attn:
+            attn = hip.attn_scores_fwd(hs[1:], d['attn/w'], d['attn/b'], c.w_rnn, L, out=buf('t_attn', (c.max_len,)))
+            acc = buf('t_attn_acc', (R, cm))
         lang, lang_ss = buf('lang', (c.max_len, cw)), buf('lang_ss', (c.max_len,))
         hip.call('ssc_row_l2norm_fwd', hs[1:], cw, None, L, cw, lang, lang_ss)
         gt = buf('g_t', (c.max_len, 4 * cm))
@@ -254,9 +286,11 @@ class MatchTrainer(object):
         for t in range(L):
             hip.lstm_step_fwd(ha[t], d['m/Kh'], 4 * cm, gs, gt[t:t + 1], R, one, R, ca[t], R, cm, t > 0, ca[t + 1], ha[t + 1], acts_m[t],
                               hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
-        pred = hip.squash_project(ha[L], d['proj/w'], d['proj/b'], C=c.m_rnn, out=buf('t_pred', (R,)))
+            if acc is not None:
+                hip.dev_scaled_add(acc, ha[t + 1], attn, t, overwrite=t == 0)
+        pred = hip.squash_project(ha[L] if acc is None else acc, d['proj/w'], d['proj/b'], C=c.m_rnn, out=buf('t_pred', (R,)))
         self._ctx = dict(feat=feat, tok=tok, L=L, R=R, fh=fh, fw=fw, vis=vis, vis_ss=vis_ss, emb=emb, cs=cs, hs=hs, acts_w=acts_w,
-                         lang=lang, lang_ss=lang_ss, ca=ca, ha=ha, acts_m=acts_m)
+                         lang=lang, lang_ss=lang_ss, ca=ca, ha=ha, acts_m=acts_m, attn=attn, acc=acc)
         return pred.view(fh, fw)
 
     # ------------------------------------------------------------------ backward
@@ -279,13 +313,22 @@ class MatchTrainer(object):
         # 1. the projection and the squash
         dh, dh2 = buf('b_dh0', (R, cm)), buf('b_dh1', (R, cm))
         dc, dc2 = buf('b_dc0', (R, cm)), buf('b_dc1', (R, cm))
-        hip.squash_project_bwd(ha[L], d['proj/w'], dpred.reshape(-1), C=c.m_rnn, dh=dh, dw=g['proj/w'], db=g['proj/b'], ws=ws)
+        attn, dacc, dattn = x['attn'], None, None
+        if attn is None:
+            hip.squash_project_bwd(ha[L], d['proj/w'], dpred.reshape(-1), C=c.m_rnn, dh=dh, dw=g['proj/w'], db=g['proj/b'], ws=ws)
+        else:       # the projection read the weighted sum: its gradient reaches every step's output through that step's weight,
+            #         and the weights through the L dots <dacc, m_out[t]> (taken now: ws is free again before the next user)
+            dacc = buf('b_dacc', (R, cm))
+            hip.squash_project_bwd(x['acc'], d['proj/w'], dpred.reshape(-1), C=c.m_rnn, dh=dacc, dw=g['proj/w'], db=g['proj/b'], ws=ws)
+            dattn = hip.attn_plane_dots(dacc, ha[1:], L, out=buf('b_dattn', (c.max_len,)), ws=ws)
         # 2. the multimodal cell back through its steps: the gate gradients of every step are kept, their sum is the gradient of
         #    the step-invariant share of the gates
         dg_all, dgs = buf('b_dg_all', (c.max_len, R, G4)), buf('b_dgs', (R, G4))
         hip.fill(dc, 0.0)
         hip.fill(dgs, 0.0)
         for t in range(L - 1, -1, -1):
+            if attn is not None:    # dh = (what step t + 1 sent back) + attn[t] * dacc
+                hip.dev_scaled_add(dh, dacc, attn, t, overwrite=t == L - 1)
             hip.call('ssc_lstm_pointwise_bwd', dh, dc, acts_m[t], ca[t], ca[t + 1], one, R, R, cm, dg_all[t], dc2, dh2, dgs)
             if t > 0:       # h_0 = 0: nothing upstream of it
                 hip.matmul_nt(dg_all[t], d['m/Kh'], dh2, accumulate=True)
@@ -310,6 +353,9 @@ class MatchTrainer(object):
         hip.matmul_nt(dr[:L], d['m/Kl'], dlang[:L])
         dhw = buf('b_dhw', (c.max_len, cw))
         hip.call('ssc_row_l2norm_bwd', lang, x['lang_ss'], dlang, L, cw, dhw, 0)
+        if attn is not None:    # through the softmax: the two variables, and dlogit[t] * w onto the word outputs' gradient
+            hip.attn_scores_bwd(attn, dattn, x['hs'][1:], d['attn/w'], c.w_rnn, L, dhs=dhw, dw=g['attn/w'], db=g['attn/b'],
+                                dlogit=buf('b_dlogit', (c.max_len,)))
         # 5. the word cell back through its steps, then the embedding
         cs, hs, acts_w = x['cs'], x['hs'], x['acts_w']
         dew = buf('b_dew', (c.max_len, 4 * cw))
@@ -361,11 +407,11 @@ class MatchTrainer(object):
         self.step_count += 1
         lr_t = adam_step_size(lr, self.step_count)
         for name, (o, size, padded, _shape) in self.spans.items():
-            if is_regularized(DEVICE_TO_VARIABLE[name]) and self.weight_decay != 0.0:
+            if is_regularized(self.dev_to_var[name]) and self.weight_decay != 0.0:
                 hip.call('ssc_l2_reg', self.params[o:o + size], size, self.weight_decay, None, self.grad[o:o + size])
         for name, (o, _size, padded, _shape) in self.spans.items():
             hip.call('ssc_adam_tf', self.params[o:o + padded], self.grad[o:o + padded], self.adam_m[o:o + padded],
-                     self.adam_v[o:o + padded], padded, lr_t, None, BETA1, BETA2, EPSILON, grad_scale(DEVICE_TO_VARIABLE[name]))
+                     self.adam_v[o:o + padded], padded, lr_t, None, BETA1, BETA2, EPSILON, grad_scale(self.dev_to_var[name]))
         hip.refresh_splits(self.params)
 
     def upload_scene(self, labels_u8):
@@ -451,7 +497,7 @@ class MatchTrainer(object):
 
     # ------------------------------------------------------------------ weights in and out
     def _export(self, views):
-        return unpack_head(self.cfg, {n: views[n].detach().cpu().numpy() for n in HEAD_DEVICE_NAMES})
+        return unpack_head(self.cfg, {n: views[n].detach().cpu().numpy() for n in self.names})
 
     def export_variables(self):
         """{checkpoint name: array}: the head out of the device layout, and the backbone's arrays as they were loaded.

@@ -1,7 +1,8 @@
 """The instance matcher of the scene pipeline, inference only, batch 1 (Pipeline_utils/fg_matching_utils.py::
 build_instance_matching): RMI_model.py in eval mode (fusion_type 'RMI', no attention) on the DeepLab-ResNet backbone of
 deeplab_model.py (is_intermediate, frozen norms), then get_pred_instance_mask's choice of the instances the prediction covers.
-DESIGN.md section 8.6.
+DESIGN.md section 8.6.  MatchConfig(use_attn=True): the model class's word attention (RMI_model.py:202-217) -- a softmax over the
+word LSTM's outputs weighs the multimodal LSTM's outputs of every word, their sum feeds the projection; DESIGN.md section 8.11.
 
     sketch uint8 [S,S,3] --ssc_match_preprocess_u8--> x [1,S,S,4], stroke [S,S]
     backbone: 7x7 s2 conv, max-pool (ssc_max_pool3s2), bottleneck units [3,4,23,3] -- hip.conv_forward with the producer's frozen
@@ -10,12 +11,14 @@ DESIGN.md section 8.6.
               front of either group, ssc_batch_to_space(2) twice behind the last unit.
     head:     1x1 projection + l2 norm, word LSTM, multimodal LSTM per location (hip.lstm_step_fwd on gate blocks padded to a
               multiple of 32), ssc_squash_project, ssc_match_finish -> up [S,S], predicts [S,S]
+              use_attn: ssc_attn_scores_fwd behind the word LSTM, ssc_dev_scaled_add behind every multimodal step, and
+              ssc_squash_project on the weighted sum instead of the last state
     choice:   ssc_instance_occupancy -> int64 counts; the quotient and the comparison with 0.5 in float64 on the host
 
 ``features`` and ``predict`` are the pass in two halves -- the backbone once per scene, the head once per caption -- for the
 evaluation on a split (match_eval.py).
 
-Not here: training (match_train.py), the other backbones, attention,
+Not here: training (match_train.py), the other backbones, fusion_type 'RecurAttn',
 post_processing_mask_with_segmentation."""
 import os
 import re
@@ -27,6 +30,8 @@ OCCUPIED_THRESH = 0.5
 UNK, PAD = '<unk>', '<pad>'
 _SPLIT = re.compile(r'(\W+)')
 NORM_PARTS = ('beta', 'gamma', 'factor', 'mean', 'variance')
+ATTN_MAX_LEN = 64           # hip.ATTN_MAX_T: the words the attention kernels hold
+ATTN_VARIABLES = ('text_sketchyscene/attn_fc/DW', 'text_sketchyscene/attn_fc/biases')
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -113,7 +118,10 @@ class MatchConfig(object):
     """The sizes of the matcher.  The defaults are the released model; the tests run small ones through the same code."""
 
     def __init__(self, size=768, units=(3, 4, 23, 3), filters=(64, 256, 512, 1024, 2048), v_emb=1000, w_emb=1000, w_rnn=1000,
-                 m_rnn=500, vocab_size=76, max_len=15):
+                 m_rnn=500, vocab_size=76, max_len=15, use_attn=False):
+        if use_attn not in (False, True, 0, 1):
+            raise ValueError('use_attn %r: False or True' % (use_attn,))
+        self.use_attn = bool(use_attn)
         self.size, self.units, self.filters = int(size), tuple(int(u) for u in units), tuple(int(f) for f in filters)
         self.v_emb, self.w_emb, self.w_rnn, self.m_rnn = int(v_emb), int(w_emb), int(w_rnn), int(m_rnn)
         self.vocab_size, self.max_len = int(vocab_size), int(max_len)
@@ -129,6 +137,8 @@ class MatchConfig(object):
             raise ValueError('filters %r: every channel count must be a multiple of 4' % (self.filters,))
         if self.vocab_size < 2 or self.max_len < 1:
             raise ValueError('vocab_size %d, max_len %d' % (self.vocab_size, self.max_len))
+        if self.use_attn and self.max_len > ATTN_MAX_LEN:
+            raise ValueError('max_len %d with use_attn: the attention kernels hold %d words' % (self.max_len, ATTN_MAX_LEN))
 
     @property
     def feat(self):
@@ -167,7 +177,23 @@ class MatchConfig(object):
         s[h + 'mLSTM/lstm_cell/bias'] = (4 * self.m_rnn,)
         s[h + 'm_lstm_output_projection/DW'] = (1, 1, self.m_rnn, 1)
         s[h + 'm_lstm_output_projection/biases'] = (1,)
+        if self.use_attn:
+            s[h + 'attn_fc/DW'] = (self.w_rnn, 1)
+            s[h + 'attn_fc/biases'] = (1,)
         return s
+
+
+def check_attention_variables(names, use_attn):
+    """names: the variable names of a checkpoint (any container).  ValueError when the attention's variables are missing with
+    use_attn, or there without it: a head trained to be read through its attention gives nothing meaningful through its last
+    state.  A checkpoint without a head at all (a backbone's) passes with the flag off."""
+    for name in ATTN_VARIABLES:
+        if use_attn and name not in names:
+            raise ValueError('the checkpoint has no variable %s: it was not trained with use_attn (--use_attn 1); read it with '
+                             'use_attn off (--use_attn 0)' % name)
+        if not use_attn and name in names:
+            raise ValueError('the checkpoint holds %s: its head was trained with use_attn (--use_attn 1) and is read through its '
+                             'attention; set use_attn (--use_attn 1)' % name)
 
 
 OLD_CELL_NAMES = {'/lstm_cell/kernel': '/lstm_cell/weights', '/lstm_cell/bias': '/lstm_cell/biases'}
@@ -183,6 +209,8 @@ def random_variables(config, seed=0):
         n = int(np.prod(shape))
         if leaf == 'DW' and name.startswith('ResNet/'):
             v = rng.randn(*shape) * np.sqrt(2.0 / (shape[0] * shape[1] * shape[3]))
+        elif leaf == 'DW' and len(shape) == 2:      # attn_fc: uniform_unit_scaling_initializer(factor=1.0)
+            v = rng.uniform(-1, 1, shape) * np.sqrt(3.0 / shape[0])
         elif leaf == 'DW':
             v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[2] + shape[3]))
         elif leaf == 'kernel':
@@ -257,6 +285,8 @@ class MatchModel(object):
         s['m/Kv'], s['m/Kw'], s['m/Kl'], s['m/Ks'] = (c.v_emb, 4 * cm), (c.w_emb, 4 * cm), (cw, 4 * cm), (8, 4 * cm)
         s['m/Kh'], s['m/b'] = (cm, 4 * cm), (4 * cm,)
         s['proj/w'], s['proj/b'] = (cm,), (1,)
+        if c.use_attn:
+            s['attn/w'], s['attn/b'] = (cw,), (1,)
         s['spatial'] = (c.feat * c.feat, 8)
         return s
 
@@ -264,9 +294,11 @@ class MatchModel(object):
     def load_dict(self, variables):
         """Take {checkpoint name: array}: every variable of MatchConfig.variable_shapes (the LSTM cells also under their older
         names weights / biases); anything else -- optimizer slots, global_step -- is ignored.  ValueError names a variable that
-        is missing or has another shape."""
+        is missing or has another shape.  The attention's two variables must be there with use_attn and must not without it:
+        a head trained to be read through its attention gives nothing meaningful through its last state."""
         import torch
         c, host = self.cfg, {}
+        check_attention_variables(variables, c.use_attn)
         for name, shape in c.variable_shapes().items():
             src = name
             if src not in variables:
@@ -299,6 +331,9 @@ class MatchModel(object):
         dev['m/Kl'], dev['m/Ks'] = pad_rows(kx[o:o + c.w_rnn], self.cw), kx[o + c.w_rnn:]
         dev['proj/w'] = pad_rows(host[h + 'm_lstm_output_projection/DW'].reshape(-1), self.cm)
         dev['proj/b'] = host[h + 'm_lstm_output_projection/biases']
+        if c.use_attn:
+            dev['attn/w'] = pad_rows(host[h + 'attn_fc/DW'].reshape(-1), self.cw)
+            dev['attn/b'] = host[h + 'attn_fc/biases']
         dev['spatial'] = spatial_features(c.feat, c.feat).reshape(-1, 8)
         assert set(dev) == set(self.d), set(dev) ^ set(self.d)
         for name, v in dev.items():
@@ -426,6 +461,10 @@ class MatchModel(object):
         for t in range(L):
             hip.lstm_step_fwd(hs[t], d['w/Kh'], 4 * cw, ew[t:t + 1], None, 1, one, 1, cs[t], 1, cw, t > 0, cs[t + 1], hs[t + 1], acts_w,
                               hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
+        attn = acc = None
+        if c.use_attn:      # the weights of the T positions: rows L .. of hs hold an earlier, longer sentence and are not read
+            attn = hip.attn_scores_fwd(hs[1:], d['attn/w'], d['attn/b'], c.w_rnn, L, out=self._buf('attn', (c.max_len,)))
+            acc = self._buf('attn_acc', (R, cm))
         lang, lang_ss = self._buf('lang', (c.max_len, cw)), self._buf('lang_ss', (c.max_len,))
         hip.call('ssc_row_l2norm_fwd', hs[1:], cw, None, L, cw, lang, lang_ss)
         gt = self._buf('g_t', (c.max_len, 4 * cm))
@@ -441,7 +480,9 @@ class MatchModel(object):
             a, b = t & 1, (t + 1) & 1
             hip.lstm_step_fwd(ha[a], d['m/Kh'], 4 * cm, gs, gt[t:t + 1], R, one, R, ca[a], R, cm, t > 0, ca[b], ha[b], acts_m,
                               hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
-        pred = hip.squash_project(ha[L & 1], d['proj/w'], d['proj/b'], C=c.m_rnn, out=self._buf('pred', (R,)))
+            if acc is not None:     # acc (+)= attn[t] * m_out[t]; the outputs past L are zero and add nothing
+                hip.dev_scaled_add(acc, ha[b], attn, t, overwrite=t == 0)
+        pred = hip.squash_project(ha[L & 1] if acc is None else acc, d['proj/w'], d['proj/b'], C=c.m_rnn, out=self._buf('pred', (R,)))
         return pred.view(fh, fw)
 
     # ------------------------------------------------------------------ the whole pass
@@ -583,6 +624,8 @@ def match_instances(model, scene, text, vocab):
     matched, scores = select_instances(counts)
     info = {'tokens': sentence_tokens(text)[:T], 'indices': list(indices), 'seq_len': seq_len, 'counts': counts,
             'up': up.cpu().numpy(), 'predicts': predicts.cpu().numpy()}
+    if model.cfg.use_attn:      # the T weights of the pass, the padded positions' included: they sum to 1
+        info['attention'] = model._buf('attn', (T,)).cpu().numpy()
     return matched, scores, info
 
 
