@@ -3,8 +3,8 @@ train_fusion_var_only=False, RMI_model.py:320-330): every ResNet/*/DW filter of 
 as they were loaded -- beta, gamma, factor, mean and variance are trainable=False and bn=False reads the stored moments
 (deeplab_model.py:176-231).  DESIGN.md section 8.10.
 
-    forward   backbone_train: the launches of MatchModel.backbone on the same operands (the feature map has its bits), every
-              unit's raw conv outputs r1, r2, r3, sc and its merged output in buffers of their own
+    forward   backbone_train: MatchModel.backbone with keep (the feature map has inference's bits): every unit's raw conv
+              outputs r1, r2, r3, sc and its merged output in buffers of their own
     backward  MatchTrainer.backward with dfeat = dvp . DW^T -> ssc_space_to_batch(2) per doubling of the rate (the backward of
               the final ungroup) -> per unit, last to first: ssc_unit_merge_bwd (the closing relu, both branches), conv_wgrad /
               conv_dgrad through block_3, block_2, block_1 with ssc_frozen_act_bwd between them (the consumer-side views are the
@@ -19,7 +19,7 @@ initial backbone)."""
 import numpy as np
 
 from . import match_train, matching
-from .match_train import BETA1, BETA2, EPSILON, MatchTrainer
+from .match_train import MatchTrainer
 
 
 def backbone_variable_names(config):
@@ -127,23 +127,15 @@ class BackboneMatchTrainer(MatchTrainer):
     views into the backbone's gradient buffer and Adam slot buffers by checkpoint name."""
 
     def __init__(self, model, weight_decay=5e-4):
-        import torch
         MatchTrainer.__init__(self, model, weight_decay)
         lay = model._layout
         self.b_names = backbone_variable_names(self.cfg)
         self.b_hi = self.lo             # the backbone is the stretch of the flat buffer in front of the head
         inside = [n for n, (o, _s) in lay.items() if o < self.b_hi]
         assert all(n.startswith('ResNet/') for n in inside) and [n for n in inside if n.endswith('/DW')] == self.b_names, inside
-        self.b_params = model.flat[:self.b_hi]
-        self.b_grad, self.b_adam_m, self.b_adam_v = (torch.zeros(self.b_hi, dtype=torch.float32, device=model.device) for _ in range(3))
-        order = list(lay)
-        self.b_spans = {}
-        for name in self.b_names:
-            o, shape = lay[name]
-            self.b_spans[name] = (o, int(np.prod(shape)), lay[order[order.index(name) + 1]][0] - o, shape)
-        self.bg, self.bm, self.bv = ({n: buf[o:o + size].view(shape) for n, (o, size, _p, shape) in self.b_spans.items()}
-                                     for buf in (self.b_grad, self.b_adam_m, self.b_adam_v))
-        self._units = None
+        self.b_params, (self.b_grad, self.b_adam_m, self.b_adam_v), self.b_spans, (self.bg, self.bm, self.bv) = \
+            match_train.trained_stretch(model, self.b_names, 0, self.b_hi)
+        self._kept = None           # what MatchModel.backbone kept of the latest pass: units, x4, r0
         self.on_part = None         # a callable(name), called behind each part of backbone_backward (scripts/match_backbone_train_rate.py)
 
     # ------------------------------------------------------------------ forward
@@ -156,77 +148,20 @@ class BackboneMatchTrainer(MatchTrainer):
             for tag, shape in shapes.items():
                 self._bbuf(tag, shape)
 
-    def unit_train(self, x, scope, stride):
-        """MatchModel.unit with every output in a buffer of the unit's own.  -> the record ``backward`` reads."""
-        from . import hip
-        from .hip import ACT_RELU, View
-        d = self.model.d
-        n, h, w, cin = x.shape
-        oh, ow = -(-h // stride), -(-w // stride)
-        w1, w2, w3 = (d['%s/block_%d/conv/DW' % (scope, k)] for k in (1, 2, 3))
-        c4, cout = w1.shape[3], w3.shape[3]
-        t = 'bt/%s/' % scope
-        r1 = self._bbuf(t + 'r1', (n, oh, ow, c4))
-        hip.conv_forward(View(x), w1, stride, 0, r1, same=True)
-        r2 = self._bbuf(t + 'r2', (n, oh, ow, c4))
-        hip.conv_forward(View(r1, None, d[scope + '/block_1/bn'], ACT_RELU), w2, 1, 0, r2, same=True)
-        r3 = self._bbuf(t + 'r3', (n, oh, ow, cout))
-        hip.conv_forward(View(r2, None, d[scope + '/block_2/bn'], ACT_RELU), w3, 1, 0, r3, same=True)
-        out = self._bbuf(t + 'out', (n, oh, ow, cout))
-        wadd = d.get(scope + '/block_add/conv/DW')
-        sc = None
-        if wadd is not None:
-            sc = self._bbuf(t + 'sc', (n, oh, ow, cout))
-            hip.conv_forward(View(x), wadd, stride, 0, sc, same=True)
-            hip.call('ssc_residual_merge', r3, d[scope + '/block_3/bn'], sc, d[scope + '/block_add/bn'], ACT_RELU, out,
-                     n * oh * ow, cout)
-        else:
-            assert cin == cout and stride == 1, (scope, cin, cout, stride)
-            hip.call('ssc_residual_merge', r3, d[scope + '/block_3/bn'], x, None, ACT_RELU, out, n * oh * ow, cout)
-        return dict(scope=scope, stride=stride, x=x, r1=r1, r2=r2, r3=r3, sc=sc, out=out, regroups=0)
-
     def backbone_train(self, x4):
-        """x4 float [1,S,S,4] -> the visual feature [1,S/8,S/8,filters[4]], with the bits of MatchModel.backbone."""
-        from . import hip
-        from .hip import View
-        c, d = self.cfg, self.model.d
-        s = c.size
-        r0 = self._bbuf('bt/conv1', (1, s // 2, s // 2, c.filters[0]))
-        hip.conv_forward(View(x4), d['ResNet/group_1/conv1/DW'], 2, 0, r0, same=True)
-        x = hip.max_pool3s2(r0, d['ResNet/group_1/bn_conv1'], out=self._bbuf('bt/pool', (1, s // 4, s // 4, c.filters[0])))
-        cur, units = 1, []
-        for scope, _cin, _cout, stride, rate in c.unit_list():
-            regroups = 0
-            while cur < rate:
-                n, h, w, ch = x.shape
-                cur *= 2
-                x = hip.space_to_batch(x, 2, out=self._bbuf('bt/s2b%d' % cur, (n * 4, h // 2, w // 2, ch)))
-                regroups += 1
-            rec = self.unit_train(x, scope, stride)
-            rec['regroups'] = regroups          # how many space_to_batch(2) ran in front of this unit
-            units.append(rec)
-            x = rec['out']
-        while cur > 1:
-            nb, h, w, ch = x.shape
-            cur //= 2
-            x = hip.batch_to_space(x, 2, out=self._bbuf('bt/b2s%d' % cur, (nb // 4, h * 2, w * 2, ch)))
-        self._units, self._x4, self._r0 = units, x4, r0
-        return x
+        """MatchModel.backbone on x4 float [1,S,S,4] with every output kept for ``backbone_backward`` (the buffers of
+        ``forward_buffer_shapes``): the same pass, so the feature map has its bits."""
+        kept = {}
+        feat = self.model.backbone(x4, keep=kept)
+        self._kept = kept
+        return feat
 
     def _features(self, sketch):
-        """MatchModel.features with ``backbone_train`` in the place of ``backbone``."""
-        import torch
-        from . import hip
-        mdl, c = self.model, self.cfg
-        sk = sketch if isinstance(sketch, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sketch))
-        if sk.dtype != torch.uint8 or tuple(sk.shape) != (c.size, c.size, 3):
-            raise ValueError('the sketch is %s %s, the matcher reads uint8 [%d, %d, 3]' % (sk.dtype, tuple(sk.shape), c.size, c.size))
-        skd = mdl._buf('sketch', (c.size, c.size, 3), torch.uint8)
-        if skd.data_ptr() != sk.data_ptr():
-            skd.copy_(sk)
-        x4, _ = hip.match_preprocess_u8(skd, out=mdl._buf('x4', (1, c.size, c.size, 4)),
-                                        stroke=mdl._buf('stroke_kept', (c.size, c.size), torch.uint8))
-        return self.backbone_train(x4)
+        """MatchModel.features with the backbone's outputs kept; the feature map stays where the pass left it."""
+        kept = {}
+        feat = self.model.features(sketch, keep=kept)[0]
+        self._kept = kept
+        return feat
 
     def step(self, scene, lut, tok, seq_len, lr):
         if 'feat_d' in scene:
@@ -238,7 +173,7 @@ class BackboneMatchTrainer(MatchTrainer):
         """The head's backward, then the backbone's from the gradient on the feature map: fills the gradient of every trained
         tensor of both."""
         c = self.cfg
-        if self._units is None:
+        if self._kept is None:
             raise RuntimeError('backward without a backbone_train before it')
         if dfeat is None:
             dfeat = self._bbuf('bb/dfeat', (1, c.feat, c.feat, c.filters[4]))
@@ -253,7 +188,7 @@ class BackboneMatchTrainer(MatchTrainer):
         from . import hip
         from .hip import ACT_RELU, View
         c, d, bg = self.cfg, self.model.d, self.bg
-        units = self._units
+        units = self._kept['units']
         # the scratch buffers are reused from unit to unit: every launch, the filter gradients included, is on this one stream
         assert hip.WGRAD_STREAM is None
         # the final ungroup backwards: into the layout of the last unit
@@ -304,55 +239,41 @@ class BackboneMatchTrainer(MatchTrainer):
             if self.on_part is not None and scope.endswith('_0'):
                 self.on_part(scope.rsplit('/', 1)[1][:-2])         # 'group_5' .. 'group_2': the group's units are behind us
         # the pool with conv1's relu, then conv1's filter: 3 real channels of the 4-channel input, SAME pad (2, 3)
-        r0 = self._r0
+        r0 = self._kept['r0']
         dr0 = hip.max_pool3s2_bwd(g, r0, d['ResNet/group_1/bn_conv1'], out=self._bbuf('bb/dr0', r0.shape))
-        hip.conv_wgrad(View(self._x4), View(dr0), bg['ResNet/group_1/conv1/DW'], 2, hip.same_pad_before(c.size, 7, 2))
+        hip.conv_wgrad(View(self._kept['x4']), View(dr0), bg['ResNet/group_1/conv1/DW'], 2, hip.same_pad_before(c.size, 7, 2))
         hip.join_wgrad()
         if self.on_part is not None:
             self.on_part('pool and conv1')
 
     # ------------------------------------------------------------------ optimiser
     def apply(self, lr):
-        """MatchTrainer.apply on the head, then the same on the backbone's filters: the regulariser on every DW, TF's Adam with
-        the head's step size and scale 1, the bf16 planes of what changed."""
-        from . import hip
+        """MatchTrainer.apply on the head, then the same on the backbone's filters with the head's step size: every DW is
+        regularised and none is a 'biases'."""
         MatchTrainer.apply(self, lr)
-        lr_t = match_train.adam_step_size(lr, self.step_count)
-        if self.weight_decay != 0.0:
-            for _name, (o, size, _padded, _shape) in self.b_spans.items():
-                hip.call('ssc_l2_reg', self.b_params[o:o + size], size, self.weight_decay, None, self.b_grad[o:o + size])
-        for _name, (o, _size, padded, _shape) in self.b_spans.items():
-            hip.call('ssc_adam_tf', self.b_params[o:o + padded], self.b_grad[o:o + padded], self.b_adam_m[o:o + padded],
-                     self.b_adam_v[o:o + padded], padded, lr_t, None, BETA1, BETA2, EPSILON, 1.0)
-        hip.refresh_splits(self.b_params)
+        match_train.apply_adam(self.b_params, self.b_grad, self.b_adam_m, self.b_adam_v, self.b_spans, {n: n for n in self.b_names},
+                               match_train.adam_step_size(lr, self.step_count), self.weight_decay)
 
     # ------------------------------------------------------------------ weights in and out
     def export_variables(self):
         """{checkpoint name: array}: the head and the backbone's filters from the device, the norms as they were loaded."""
         out = MatchTrainer.export_variables(self)
-        for name in self.b_names:
-            out[name] = self.model.d[name].detach().cpu().numpy().copy()
+        out.update(self._export_backbone(self.model.d))
         return out
 
+    def _export_backbone(self, views):
+        return {n: views[n].detach().cpu().numpy().copy() for n in self.b_names}
+
     def export_backbone_gradients(self):
-        return {n: self.bg[n].detach().cpu().numpy().copy() for n in self.b_names}
+        return self._export_backbone(self.bg)
 
     def snapshot_tensors(self):
         out = MatchTrainer.snapshot_tensors(self)
-        for suffix, views in (('/Adam', self.bm), ('/Adam_1', self.bv)):
-            for name in self.b_names:
-                out[name + suffix] = views[name].detach().cpu().numpy().copy()
+        match_train.slots_to_snapshot(out, self.bm, self.bv, self._export_backbone)
         return out
 
     def load_slots(self, tensors, step):
-        import torch
-        for suffix, views in (('/Adam', self.bm), ('/Adam_1', self.bv)):
-            for name in self.b_names:
-                if name + suffix not in tensors:
-                    raise ValueError('the snapshot has no %s: it was written by a run with --train_backbone 0 (or not by training); '
-                                     'resume it with --train_backbone 0' % (name + suffix))
-                a = np.ascontiguousarray(tensors[name + suffix], dtype=np.float32)
-                if a.shape != tuple(views[name].shape):
-                    raise ValueError('%s is %s, the model needs %s' % (name + suffix, a.shape, tuple(views[name].shape)))
-                views[name].copy_(torch.from_numpy(a))
+        match_train.slots_from_snapshot(tensors, self.bm, self.bv, self.b_names, dict,
+                                        'it was written by a run with --train_backbone 0 (or not by training); resume it with '
+                                        '--train_backbone 0')
         MatchTrainer.load_slots(self, tensors, step)

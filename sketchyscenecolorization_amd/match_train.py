@@ -2,7 +2,7 @@
 train_fusion_var_only, utils/loss.py): the DeepLab backbone stays frozen, the text_sketchyscene/* head -- the visual projection,
 the embedding, the word LSTM, the multimodal LSTM and the output projection -- learns.  DESIGN.md section 8.8.
 
-    per iteration  MatchModel.features (frozen backbone) -> head_train (the arithmetic of MatchModel.head, every step's state kept)
+    per iteration  MatchModel.features (frozen backbone) -> head_train (MatchModel.head with keep: every step's state kept)
                    -> ssc_match_loss_grad (summed sigmoid cross entropy of the up-sampled logits over the stroke pixels, its
                    gradient on the 1/8 map) -> backward (ssc_squash_project_bwd, BPTT of both cells on the caption branch's
                    kernels) -> ssc_l2_reg on the two DW -> ssc_adam_tf per tensor (gradient x 2 on the two biases) ->
@@ -14,8 +14,8 @@ construction and Adam leaves a zero with zero moments at zero.
 
 Training the backbone's filters as well: match_backbone_train.py, a subclass of the trainer here.
 
-MatchConfig(use_attn=True): attn_fc/DW and attn_fc/biases are trained too.  head_train accumulates the
-weighted sum of the multimodal outputs as MatchModel.head does; backward sends the projection's gradient into that sum, injects
+MatchConfig(use_attn=True): attn_fc/DW and attn_fc/biases are trained too.  MatchModel.head accumulates
+the weighted sum of the multimodal outputs; backward sends the projection's gradient into that sum, injects
 attn[t] times it into every step of the multimodal cell's BPTT (ssc_dev_scaled_add), takes the weights' gradient as L dots over
 the kept outputs (ssc_attn_plane_dots) and goes through the softmax into the two variables and the word cell's incoming gradient
 (ssc_attn_scores_bwd).  The bias shifts every logit alike: it is a free parameter, its exact gradient is 0.
@@ -29,8 +29,8 @@ import random
 import numpy as np
 
 from . import matching
+from .matching import HEAD, pack_head, unpack_head, unpad_gate_columns  # noqa: F401 (the head's packing lives beside pad_lstm)
 
-HEAD = 'text_sketchyscene/'
 BETA1, BETA2, EPSILON = 0.9, 0.999, 1e-8
 MODEL_NAME = 'deeplab_RMI'
 LIVE_MAX_BYTE = 104         # im[..., 0] < 0 with mu_0 = 104.00698793
@@ -75,69 +75,9 @@ def init_head(config, seed=0):
     out = {}
     shapes = config.variable_shapes()
     for name in head_variable_names(config):
-        shape = shapes[name]
-        leaf = name.rsplit('/', 1)[1]
-        if leaf == 'DW' and len(shape) == 2:
-            v = rng.uniform(-1, 1, shape) * np.sqrt(3.0 / shape[0])
-        elif leaf == 'DW':
-            v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[2] + shape[3]))
-        elif leaf == 'kernel':
-            v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[0] + shape[1]))
-        elif leaf == 'embedding':
-            v = rng.uniform(-0.08, 0.08, shape)
-        else:
-            v = np.zeros(shape)
-        out[name] = np.ascontiguousarray(v, dtype=np.float32)
+        v = matching.draw_head_weight(rng, name.rsplit('/', 1)[1], shapes[name])
+        out[name] = np.ascontiguousarray(np.zeros(shapes[name]) if v is None else v, dtype=np.float32)
     return out
-
-
-def unpad_gate_columns(k, c, cp):
-    """The inverse of matching.pad_gate_columns: [..., 4cp] -> [..., 4c]."""
-    k = np.asarray(k)
-    return np.concatenate([k[..., g * cp:g * cp + c] for g in range(4)], axis=-1)
-
-
-def pack_head(config, host):
-    """{checkpoint name: array} of the head -> {device name: float32 array}, as MatchModel.load_dict lays them out."""
-    c = config
-    cw, cm = matching.pad32(c.w_rnn), matching.pad32(c.m_rnn)
-    dev = {'vproj/w': host[HEAD + 'visual_feat_projection/DW'], 'vproj/b': host[HEAD + 'visual_feat_projection/biases'],
-           'embedding': host[HEAD + 'embedding']}
-    dev['w/Kx'], dev['w/Kh'], dev['w/b'] = matching.pad_lstm(host[HEAD + 'wLSTM/lstm_cell/kernel'], host[HEAD + 'wLSTM/lstm_cell/bias'],
-                                                           c.w_emb, c.w_rnn)
-    kx, dev['m/Kh'], dev['m/b'] = matching.pad_lstm(host[HEAD + 'mLSTM/lstm_cell/kernel'], host[HEAD + 'mLSTM/lstm_cell/bias'],
-                                                  c.v_emb + c.w_emb + c.w_rnn + 8, c.m_rnn)
-    o = c.v_emb + c.w_emb
-    dev['m/Kv'], dev['m/Kw'] = kx[:c.v_emb], kx[c.v_emb:o]
-    dev['m/Kl'], dev['m/Ks'] = matching.pad_rows(kx[o:o + c.w_rnn], cw), kx[o + c.w_rnn:]
-    dev['proj/w'] = matching.pad_rows(np.asarray(host[HEAD + 'm_lstm_output_projection/DW']).reshape(-1), cm)
-    dev['proj/b'] = host[HEAD + 'm_lstm_output_projection/biases']
-    if c.use_attn:
-        dev['attn/w'] = matching.pad_rows(np.asarray(host[HEAD + 'attn_fc/DW']).reshape(-1), cw)
-        dev['attn/b'] = host[HEAD + 'attn_fc/biases']
-    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in dev.items()}
-
-
-def unpack_head(config, dev):
-    """The inverse of ``pack_head``: pad_lstm, pad_rows and the cut of the multimodal kernel's rows undone."""
-    c = config
-    cw, cm = matching.pad32(c.w_rnn), matching.pad32(c.m_rnn)
-    d = {k: np.asarray(v, dtype=np.float32) for k, v in dev.items()}
-    out = {HEAD + 'visual_feat_projection/DW': d['vproj/w'].reshape(1, 1, c.filters[4], c.v_emb),
-           HEAD + 'visual_feat_projection/biases': d['vproj/b'].reshape(c.v_emb),
-           HEAD + 'embedding': d['embedding'].reshape(c.vocab_size, c.w_emb)}
-    out[HEAD + 'wLSTM/lstm_cell/kernel'] = np.concatenate(
-        [unpad_gate_columns(d['w/Kx'], c.w_rnn, cw), unpad_gate_columns(d['w/Kh'][:c.w_rnn], c.w_rnn, cw)], axis=0)
-    out[HEAD + 'wLSTM/lstm_cell/bias'] = unpad_gate_columns(d['w/b'], c.w_rnn, cw)
-    out[HEAD + 'mLSTM/lstm_cell/kernel'] = np.concatenate(
-        [unpad_gate_columns(k, c.m_rnn, cm) for k in (d['m/Kv'], d['m/Kw'], d['m/Kl'][:c.w_rnn], d['m/Ks'], d['m/Kh'][:c.m_rnn])], axis=0)
-    out[HEAD + 'mLSTM/lstm_cell/bias'] = unpad_gate_columns(d['m/b'], c.m_rnn, cm)
-    out[HEAD + 'm_lstm_output_projection/DW'] = d['proj/w'][:c.m_rnn].reshape(1, 1, c.m_rnn, 1)
-    out[HEAD + 'm_lstm_output_projection/biases'] = d['proj/b'].reshape(1)
-    if c.use_attn:
-        out[HEAD + 'attn_fc/DW'] = d['attn/w'][:c.w_rnn].reshape(c.w_rnn, 1)
-        out[HEAD + 'attn_fc/biases'] = d['attn/b'].reshape(1)
-    return {k: np.array(v, dtype=np.float32, order='C', copy=True) for k, v in out.items()}
 
 
 # device name -> the checkpoint variable whose name decides its regulariser and its gradient scale
@@ -205,6 +145,63 @@ def caption_lut(labels_of_caption):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# a trained stretch of MatchModel.flat: its buffers, its update, its Adam slots in a snapshot
+# ---------------------------------------------------------------------------------------------------------------------------
+def trained_stretch(model, names, lo, hi):
+    """flat[lo:hi] holds the tensors ``names`` (layout names, in the layout's order) -> (the stretch, its gradient buffer and its
+    two Adam slot buffers, {name: (offset in the stretch, real size, size up to the next tensor of the layout, shape)}, the
+    three buffers' views by name)."""
+    import torch
+    lay, order = model._layout, list(model._layout)
+    bufs = [torch.zeros(hi - lo, dtype=torch.float32, device=model.device) for _ in range(3)]
+    spans = {}
+    for name in names:
+        o, shape = lay[name]
+        spans[name] = (o - lo, int(np.prod(shape)), lay[order[order.index(name) + 1]][0] - o, shape)
+    views = [{n: buf[o:o + size].view(shape) for n, (o, size, _p, shape) in spans.items()} for buf in bufs]
+    return model.flat[lo:hi], bufs, spans, views
+
+
+def apply_adam(params, grad, adam_m, adam_v, spans, variable_of, lr_t, weight_decay):
+    """One update of a stretch: the regulariser's gradient on the real entries of every span whose variable is_regularized, TF's
+    Adam on every span (padding included: a zero with zero moments stays zero) with the gradient times its variable's
+    grad_scale, then the bf16 planes of the changed filters."""
+    from . import hip
+    for name, (o, size, _padded, _shape) in spans.items():
+        if is_regularized(variable_of[name]) and weight_decay != 0.0:
+            hip.call('ssc_l2_reg', params[o:o + size], size, weight_decay, None, grad[o:o + size])
+    for name, (o, _size, padded, _shape) in spans.items():
+        hip.call('ssc_adam_tf', params[o:o + padded], grad[o:o + padded], adam_m[o:o + padded], adam_v[o:o + padded], padded, lr_t,
+                 None, BETA1, BETA2, EPSILON, grad_scale(variable_of[name]))
+    hip.refresh_splits(params)
+
+
+def slots_to_snapshot(out, m, v, to_checkpoint):
+    """The two Adam slots of a stretch into ``out`` as <name>/Adam and <name>/Adam_1; to_checkpoint: views by layout name ->
+    {checkpoint name: array}."""
+    for suffix, views in (('/Adam', m), ('/Adam_1', v)):
+        for name, a in to_checkpoint(views).items():
+            out[name + suffix] = a
+
+
+def slots_from_snapshot(tensors, m, v, names, from_checkpoint, hint):
+    """The way back: the slots of the checkpoint variables ``names`` out of a snapshot's tensors; from_checkpoint: {checkpoint
+    name: array} -> {layout name: array}.  ValueError with ``hint`` for a snapshot without them."""
+    import torch
+    for suffix, views in (('/Adam', m), ('/Adam_1', v)):
+        host = {}
+        for name in names:
+            if name + suffix not in tensors:
+                raise ValueError('the snapshot has no %s: %s' % (name + suffix, hint))
+            host[name] = tensors[name + suffix]
+        for n, a in from_checkpoint(host).items():
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != tuple(views[n].shape):
+                raise ValueError('%s is %s, the model needs %s' % (n + suffix, a.shape, tuple(views[n].shape)))
+            views[n].copy_(torch.from_numpy(a))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # the trainer on the device
 # ---------------------------------------------------------------------------------------------------------------------------
 class MatchTrainer(object):
@@ -225,15 +222,8 @@ class MatchTrainer(object):
         # the head is one stretch of the flat buffer: every trained tensor in it, nothing else
         inside = [n for n, (o, _s) in lay.items() if self.lo <= o < self.hi]
         assert inside == list(names), inside
-        self.params = model.flat[self.lo:self.hi]
-        self.grad, self.adam_m, self.adam_v = (torch.zeros(self.hi - self.lo, dtype=torch.float32, device=model.device) for _ in range(3))
-        self.spans = {}
-        for k, name in enumerate(names):
-            o, shape = lay[name]
-            end = lay[names[k + 1]][0] if k + 1 < len(names) else self.hi
-            self.spans[name] = (o - self.lo, int(np.prod(shape)), end - o, shape)          # offset, real size, padded size
-        self.g, self.m, self.v = ({n: buf[o:o + size].view(shape) for n, (o, size, _p, shape) in self.spans.items()}
-                                  for buf in (self.grad, self.adam_m, self.adam_v))
+        self.params, (self.grad, self.adam_m, self.adam_v), self.spans, (self.g, self.m, self.v) = \
+            trained_stretch(model, names, self.lo, self.hi)
         self.step_count = 0
         self._loss = torch.zeros(2, dtype=torch.float64, device=model.device)
         self._live = torch.zeros(2, dtype=torch.int64, device=model.device)
@@ -242,56 +232,12 @@ class MatchTrainer(object):
 
     # ------------------------------------------------------------------ forward
     def head_train(self, feat, tok, seq_len):
-        """The arithmetic of MatchModel.head -- the same launches on the same operands, so ``pred`` has its bits -- with the cell
-        state, the output and the activated gates of every step of both cells kept for ``backward``."""
-        from . import hip
-        from .hip import View
-        mdl, c, d = self.model, self.cfg, self.model.d
-        buf = mdl._buf
-        _, fh, fw, _ = feat.shape
-        R, L, cw, cm = fh * fw, int(seq_len), mdl.cw, mdl.cm
-        assert 1 <= L <= c.max_len and (fh, fw) == (c.feat, c.feat)
-        one = mdl.one
-        vp = buf('vproj', (1, fh, fw, c.v_emb))
-        hip.conv_forward(View(feat), d['vproj/w'], 1, 0, vp, bias=d['vproj/b'], same=True)
-        vis, vis_ss = buf('vis', (R, c.v_emb)), buf('vis_ss', (R,))
-        hip.call('ssc_row_l2norm_fwd', vp, c.v_emb, None, R, c.v_emb, vis, vis_ss)
-        gs = buf('g_static', (R, 4 * cm))
-        hip.matmul(vis, d['m/Kv'], gs)
-        hip.matmul(d['spatial'], d['m/Ks'], gs, accumulate=True)
-        emb = buf('emb', (c.max_len, c.w_emb))
-        hip.call('ssc_embedding_gather', d['embedding'], tok, L, c.w_emb, emb)
-        ew = buf('ew', (c.max_len, 4 * cw))
-        hip.matmul(emb[:L], d['w/Kx'], ew[:L], bias=d['w/b'])
-        cs, hs = buf('cw', (c.max_len + 1, cw), zero=True), buf('hw', (c.max_len + 1, cw), zero=True)
-        acts_w = buf('t_acts_w', (c.max_len, 4 * cw))
-        hp = mdl._lstm_planes('hpw', 1, cw)
-        for t in range(L):
-            hip.lstm_step_fwd(hs[t], d['w/Kh'], 4 * cw, ew[t:t + 1], None, 1, one, 1, cs[t], 1, cw, t > 0, cs[t + 1], hs[t + 1],
-                              acts_w[t:t + 1], hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1],
-                              hp_out=None if hp is None else hp[t & 1])
-        attn = acc = None
-        if c.use_attn:
-            attn = hip.attn_scores_fwd(hs[1:], d['attn/w'], d['attn/b'], c.w_rnn, L, out=buf('t_attn', (c.max_len,)))
-            acc = buf('t_attn_acc', (R, cm))
-        lang, lang_ss = buf('lang', (c.max_len, cw)), buf('lang_ss', (c.max_len,))
-        hip.call('ssc_row_l2norm_fwd', hs[1:], cw, None, L, cw, lang, lang_ss)
-        gt = buf('g_t', (c.max_len, 4 * cm))
-        hip.matmul(emb[:L], d['m/Kw'], gt[:L], bias=d['m/b'])
-        hip.matmul(lang[:L], d['m/Kl'], gt[:L], accumulate=True)
-        # state 0 of the multimodal cell is zero and nobody writes it: the steps store the states 1 .. L
-        ca, ha = buf('t_ca', (c.max_len + 1, R, cm), zero=True), buf('t_ha', (c.max_len + 1, R, cm), zero=True)
-        acts_m = buf('t_acts_m', (c.max_len, R, 4 * cm))
-        hp = mdl._lstm_planes('hpm', R, cm)
-        for t in range(L):
-            hip.lstm_step_fwd(ha[t], d['m/Kh'], 4 * cm, gs, gt[t:t + 1], R, one, R, ca[t], R, cm, t > 0, ca[t + 1], ha[t + 1], acts_m[t],
-                              hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
-            if acc is not None:
-                hip.dev_scaled_add(acc, ha[t + 1], attn, t, overwrite=t == 0)
-        pred = hip.squash_project(ha[L] if acc is None else acc, d['proj/w'], d['proj/b'], C=c.m_rnn, out=buf('t_pred', (R,)))
-        self._ctx = dict(feat=feat, tok=tok, L=L, R=R, fh=fh, fw=fw, vis=vis, vis_ss=vis_ss, emb=emb, cs=cs, hs=hs, acts_w=acts_w,
-                         lang=lang, lang_ss=lang_ss, ca=ca, ha=ha, acts_m=acts_m, attn=attn, acc=acc)
-        return pred.view(fh, fw)
+        """MatchModel.head with the cell state, the output and the activated gates of every step of both cells kept for
+        ``backward``: the same pass, so ``pred`` has its bits."""
+        ctx = {}
+        pred = self.model.head(feat, tok, seq_len, keep=ctx)
+        self._ctx = ctx
+        return pred
 
     # ------------------------------------------------------------------ backward
     def backward(self, dpred, dfeat=None):
@@ -364,7 +310,7 @@ class MatchTrainer(object):
         hip.fill(wc, 0.0)
         for t in range(L - 1, -1, -1):
             hip.call('ssc_axpy', wh, dhw[t:t + 1], 1.0, cw)
-            hip.call('ssc_lstm_pointwise_bwd', wh, wc, acts_w[t:t + 1], cs[t:t + 1], cs[t + 1:t + 2], one, 1, 1, cw, dew[t:t + 1], wc2,
+            hip.call('ssc_lstm_pointwise_bwd', wh, wc, acts_w[t], cs[t:t + 1], cs[t + 1:t + 2], one, 1, 1, cw, dew[t:t + 1], wc2,
                      wh2, None)
             if t > 0:
                 hip.matmul_nt(dew[t:t + 1], d['w/Kh'], wh2, accumulate=True)
@@ -403,16 +349,9 @@ class MatchTrainer(object):
     def apply(self, lr):
         """The regulariser's gradient on the two DW, then TF's Adam on every trained tensor with the gradient of the two biases
         doubled, then the bf16 planes of the changed filters."""
-        from . import hip
         self.step_count += 1
-        lr_t = adam_step_size(lr, self.step_count)
-        for name, (o, size, padded, _shape) in self.spans.items():
-            if is_regularized(self.dev_to_var[name]) and self.weight_decay != 0.0:
-                hip.call('ssc_l2_reg', self.params[o:o + size], size, self.weight_decay, None, self.grad[o:o + size])
-        for name, (o, _size, padded, _shape) in self.spans.items():
-            hip.call('ssc_adam_tf', self.params[o:o + padded], self.grad[o:o + padded], self.adam_m[o:o + padded],
-                     self.adam_v[o:o + padded], padded, lr_t, None, BETA1, BETA2, EPSILON, grad_scale(self.dev_to_var[name]))
-        hip.refresh_splits(self.params)
+        apply_adam(self.params, self.grad, self.adam_m, self.adam_v, self.spans, self.dev_to_var, adam_step_size(lr, self.step_count),
+                   self.weight_decay)
 
     def upload_scene(self, labels_u8):
         """The scene's label map uint8 [S,S] into its device buffer (once per scene)."""
@@ -441,12 +380,7 @@ class MatchTrainer(object):
         itself never waits for the device.  ``last_loss`` reads the current one on demand."""
         import torch
         c, mdl = self.cfg, self.model
-        idx = np.asarray(tok, dtype=np.int64).reshape(-1)
-        seq_len = int(seq_len)
-        if idx.shape[0] != c.max_len or not 1 <= seq_len <= c.max_len:
-            raise ValueError('%d indices with %d real ones: the matcher reads %d, at least one real' % (idx.shape[0], seq_len, c.max_len))
-        if idx.min() < 0 or idx.max() >= c.vocab_size:
-            raise ValueError('a word index outside the vocabulary of %d' % c.vocab_size)
+        tok, seq_len = mdl.check_sentence(tok, seq_len)
         lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1)
         if lut.shape[0] != 256:
             raise ValueError('the lut holds %d bytes, not 256' % lut.shape[0])
@@ -463,8 +397,7 @@ class MatchTrainer(object):
             feat = self._features(scene['sketch'])
             sketch_d = mdl._buf('sketch', (c.size, c.size, 3), torch.uint8)
             labels_d = scene['labels_d'] if 'labels_d' in scene else self.upload_scene(scene['labels'])
-        tok_d = mdl._buf('tok', (c.max_len,), torch.int32)
-        tok_d.copy_(torch.from_numpy(idx.astype(np.int32)))
+        tok_d = mdl.put_sentence(tok)
         lut_d = mdl._buf('t_lut', (256,), torch.uint8)
         lut_d.copy_(torch.from_numpy(lut))
         pred = self.head_train(feat, tok_d, seq_len)
@@ -513,9 +446,7 @@ class MatchTrainer(object):
         """What a snapshot holds: every variable, the Adam slots of the trained ones as <name>/Adam and <name>/Adam_1,
         beta1_power, beta2_power and the step as Variable."""
         out = self.export_variables()
-        for suffix, views in (('/Adam', self.m), ('/Adam_1', self.v)):
-            for name, a in self._export(views).items():
-                out[name + suffix] = a
+        slots_to_snapshot(out, self.m, self.v, self._export)
         out['beta1_power'] = np.float32(BETA1 ** (self.step_count + 1))
         out['beta2_power'] = np.float32(BETA2 ** (self.step_count + 1))
         out['Variable'] = np.int32(self.step_count)
@@ -523,15 +454,8 @@ class MatchTrainer(object):
 
     def load_slots(self, tensors, step):
         """The Adam slots and the step out of a snapshot's tensors."""
-        import torch
-        for suffix, views in (('/Adam', self.m), ('/Adam_1', self.v)):
-            host = {}
-            for name in head_variable_names(self.cfg):
-                if name + suffix not in tensors:
-                    raise ValueError('the snapshot has no %s: it was not written by training' % (name + suffix))
-                host[name] = tensors[name + suffix]
-            for n, a in pack_head(self.cfg, host).items():
-                views[n].copy_(torch.from_numpy(a).view(views[n].shape))
+        slots_from_snapshot(tensors, self.m, self.v, head_variable_names(self.cfg), lambda host: pack_head(self.cfg, host),
+                            'it was not written by training')
         self.step_count = int(step)
 
 

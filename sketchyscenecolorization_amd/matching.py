@@ -18,7 +18,10 @@ word LSTM's outputs weighs the multimodal LSTM's outputs of every word, their su
 ``features`` and ``predict`` are the pass in two halves -- the backbone once per scene, the head once per caption -- for the
 evaluation on a split (match_eval.py).
 
-Not here: training (match_train.py), the other backbones, fusion_type 'RecurAttn',
+``head``, ``unit``, ``backbone`` and ``features`` are also the forward pass of training: with ``keep`` they leave what a backward
+pass reads in buffers of its own (match_train.py, match_backbone_train.py; DESIGN.md sections 8.8 and 8.10).
+
+Not here: the backward pass and the optimiser (match_train.py), the other backbones, fusion_type 'RecurAttn',
 post_processing_mask_with_segmentation."""
 import os
 import re
@@ -31,7 +34,8 @@ UNK, PAD = '<unk>', '<pad>'
 _SPLIT = re.compile(r'(\W+)')
 NORM_PARTS = ('beta', 'gamma', 'factor', 'mean', 'variance')
 ATTN_MAX_LEN = 64           # hip.ATTN_MAX_T: the words the attention kernels hold
-ATTN_VARIABLES = ('text_sketchyscene/attn_fc/DW', 'text_sketchyscene/attn_fc/biases')
+HEAD = 'text_sketchyscene/'          # the scope of the fusion head's variables
+ATTN_VARIABLES = (HEAD + 'attn_fc/DW', HEAD + 'attn_fc/biases')
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -114,6 +118,55 @@ def pad_lstm(kernel, bias, n_in, c):
             pad_gate_columns(bias, c, cp))
 
 
+def unpad_gate_columns(k, c, cp):
+    """The inverse of pad_gate_columns: [..., 4cp] -> [..., 4c]."""
+    k = np.asarray(k)
+    return np.concatenate([k[..., g * cp:g * cp + c] for g in range(4)], axis=-1)
+
+
+def pack_head(config, host):
+    """{checkpoint name: array} of the head -> {device name: float32 array}, as the kernels read them: the LSTM kernels cut by
+    input rows and padded by gate blocks, the two projections' vectors padded."""
+    c, h = config, HEAD
+    cw, cm = pad32(c.w_rnn), pad32(c.m_rnn)
+    dev = {'vproj/w': host[h + 'visual_feat_projection/DW'], 'vproj/b': host[h + 'visual_feat_projection/biases'],
+           'embedding': host[h + 'embedding']}
+    dev['w/Kx'], dev['w/Kh'], dev['w/b'] = pad_lstm(host[h + 'wLSTM/lstm_cell/kernel'], host[h + 'wLSTM/lstm_cell/bias'], c.w_emb, c.w_rnn)
+    kx, dev['m/Kh'], dev['m/b'] = pad_lstm(host[h + 'mLSTM/lstm_cell/kernel'], host[h + 'mLSTM/lstm_cell/bias'],
+                                           c.v_emb + c.w_emb + c.w_rnn + 8, c.m_rnn)
+    o = c.v_emb + c.w_emb
+    dev['m/Kv'], dev['m/Kw'] = kx[:c.v_emb], kx[c.v_emb:o]
+    dev['m/Kl'], dev['m/Ks'] = pad_rows(kx[o:o + c.w_rnn], cw), kx[o + c.w_rnn:]
+    dev['proj/w'] = pad_rows(np.asarray(host[h + 'm_lstm_output_projection/DW']).reshape(-1), cm)
+    dev['proj/b'] = host[h + 'm_lstm_output_projection/biases']
+    if c.use_attn:
+        dev['attn/w'] = pad_rows(np.asarray(host[h + 'attn_fc/DW']).reshape(-1), cw)
+        dev['attn/b'] = host[h + 'attn_fc/biases']
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in dev.items()}
+
+
+def unpack_head(config, dev):
+    """The inverse of ``pack_head``: pad_lstm, pad_rows and the cut of the multimodal kernel's rows undone."""
+    c, h = config, HEAD
+    cw, cm = pad32(c.w_rnn), pad32(c.m_rnn)
+    d = {k: np.asarray(v, dtype=np.float32) for k, v in dev.items()}
+    out = {h + 'visual_feat_projection/DW': d['vproj/w'].reshape(1, 1, c.filters[4], c.v_emb),
+           h + 'visual_feat_projection/biases': d['vproj/b'].reshape(c.v_emb),
+           h + 'embedding': d['embedding'].reshape(c.vocab_size, c.w_emb)}
+    out[h + 'wLSTM/lstm_cell/kernel'] = np.concatenate(
+        [unpad_gate_columns(d['w/Kx'], c.w_rnn, cw), unpad_gate_columns(d['w/Kh'][:c.w_rnn], c.w_rnn, cw)], axis=0)
+    out[h + 'wLSTM/lstm_cell/bias'] = unpad_gate_columns(d['w/b'], c.w_rnn, cw)
+    out[h + 'mLSTM/lstm_cell/kernel'] = np.concatenate(
+        [unpad_gate_columns(k, c.m_rnn, cm) for k in (d['m/Kv'], d['m/Kw'], d['m/Kl'][:c.w_rnn], d['m/Ks'], d['m/Kh'][:c.m_rnn])], axis=0)
+    out[h + 'mLSTM/lstm_cell/bias'] = unpad_gate_columns(d['m/b'], c.m_rnn, cm)
+    out[h + 'm_lstm_output_projection/DW'] = d['proj/w'][:c.m_rnn].reshape(1, 1, c.m_rnn, 1)
+    out[h + 'm_lstm_output_projection/biases'] = d['proj/b'].reshape(1)
+    if c.use_attn:
+        out[h + 'attn_fc/DW'] = d['attn/w'][:c.w_rnn].reshape(c.w_rnn, 1)
+        out[h + 'attn_fc/biases'] = d['attn/b'].reshape(1)
+    return {k: np.array(v, dtype=np.float32, order='C', copy=True) for k, v in out.items()}
+
+
 class MatchConfig(object):
     """The sizes of the matcher.  The defaults are the released model; the tests run small ones through the same code."""
 
@@ -167,7 +220,7 @@ class MatchConfig(object):
                     ((('block_add', (1, 1, cin, cout)),) if cin != cout else ()):
                 s['%s/%s/conv/DW' % (scope, blk)] = shape
                 norm('%s/%s/bn' % (scope, blk), shape[3])
-        h = 'text_sketchyscene/'
+        h = HEAD
         s[h + 'visual_feat_projection/DW'] = (1, 1, f[4], self.v_emb)
         s[h + 'visual_feat_projection/biases'] = (self.v_emb,)
         s[h + 'embedding'] = (self.vocab_size, self.w_emb)
@@ -199,6 +252,21 @@ def check_attention_variables(names, use_attn):
 OLD_CELL_NAMES = {'/lstm_cell/kernel': '/lstm_cell/weights', '/lstm_cell/bias': '/lstm_cell/biases'}
 
 
+def draw_head_weight(rng, leaf, shape):
+    """The reference's initialiser of one of the head's weights, drawn from ``rng``: Xavier-uniform for a 1x1 filter DW,
+    uniform_unit_scaling_initializer(factor=1.0) for attn_fc's 2-d DW, Glorot-uniform for an LSTM kernel, uniform +-0.08 for the
+    embedding.  -> float64, or None for a leaf that is none of them (a bias)."""
+    if leaf == 'DW' and len(shape) == 2:
+        return rng.uniform(-1, 1, shape) * np.sqrt(3.0 / shape[0])
+    if leaf == 'DW':
+        return rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[2] + shape[3]))
+    if leaf == 'kernel':
+        return rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[0] + shape[1]))
+    if leaf == 'embedding':
+        return rng.uniform(-0.08, 0.08, shape)
+    return None
+
+
 def random_variables(config, seed=0):
     """Float32 variables under the checkpoint names: the reference's initialisers for the weights, and norms that are not the
     identity (so that a wrong fold shows)."""
@@ -209,14 +277,8 @@ def random_variables(config, seed=0):
         n = int(np.prod(shape))
         if leaf == 'DW' and name.startswith('ResNet/'):
             v = rng.randn(*shape) * np.sqrt(2.0 / (shape[0] * shape[1] * shape[3]))
-        elif leaf == 'DW' and len(shape) == 2:      # attn_fc: uniform_unit_scaling_initializer(factor=1.0)
-            v = rng.uniform(-1, 1, shape) * np.sqrt(3.0 / shape[0])
-        elif leaf == 'DW':
-            v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[2] + shape[3]))
-        elif leaf == 'kernel':
-            v = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / (shape[0] + shape[1]))
-        elif leaf == 'embedding':
-            v = rng.uniform(-0.08, 0.08, shape)
+        elif leaf in ('DW', 'kernel', 'embedding'):
+            v = draw_head_weight(rng, leaf, shape)
         elif leaf in ('gamma', 'variance'):
             v = rng.uniform(0.5, 1.5, shape)
         elif leaf == 'factor':
@@ -319,21 +381,7 @@ class MatchModel(object):
                     dev[name] = v
                 elif leaf == 'gamma':
                     dev[scope] = fold_norm(*[host[scope + '/' + p] for p in NORM_PARTS])
-        h = 'text_sketchyscene/'
-        dev['vproj/w'], dev['vproj/b'] = host[h + 'visual_feat_projection/DW'], host[h + 'visual_feat_projection/biases']
-        dev['embedding'] = host[h + 'embedding']
-        dev['w/Kx'], dev['w/Kh'], dev['w/b'] = pad_lstm(host[h + 'wLSTM/lstm_cell/kernel'], host[h + 'wLSTM/lstm_cell/bias'],
-                                                        c.w_emb, c.w_rnn)
-        kx, dev['m/Kh'], dev['m/b'] = pad_lstm(host[h + 'mLSTM/lstm_cell/kernel'], host[h + 'mLSTM/lstm_cell/bias'],
-                                               c.v_emb + c.w_emb + c.w_rnn + 8, c.m_rnn)
-        o = c.v_emb + c.w_emb
-        dev['m/Kv'], dev['m/Kw'] = kx[:c.v_emb], kx[c.v_emb:o]
-        dev['m/Kl'], dev['m/Ks'] = pad_rows(kx[o:o + c.w_rnn], self.cw), kx[o + c.w_rnn:]
-        dev['proj/w'] = pad_rows(host[h + 'm_lstm_output_projection/DW'].reshape(-1), self.cm)
-        dev['proj/b'] = host[h + 'm_lstm_output_projection/biases']
-        if c.use_attn:
-            dev['attn/w'] = pad_rows(host[h + 'attn_fc/DW'].reshape(-1), self.cw)
-            dev['attn/b'] = host[h + 'attn_fc/biases']
+        dev.update(pack_head(c, host))
         dev['spatial'] = spatial_features(c.feat, c.feat).reshape(-1, 8)
         assert set(dev) == set(self.d), set(dev) ^ set(self.d)
         for name, v in dev.items():
@@ -360,9 +408,14 @@ class MatchModel(object):
         return b
 
     # ------------------------------------------------------------------ backbone
-    def unit(self, x, scope, stride, slot=0):
+    # Every pass below takes ``keep``.  None: inference -- the intermediate buffers are shared from unit to unit and from step to
+    # step, nothing beyond the result outlives the pass.  A dict: training -- every output the backward reads goes to a buffer of
+    # its own (t_* in the head, bt/* in the backbone), and the dict is filled with the record the backward reads
+    # (match_train.py, match_backbone_train.py).  The launches and their operands' values are the same either way.
+    def unit(self, x, scope, stride, slot=0, keep=None):
         """One bottleneck unit on x float [N,H,W,cin] (materialised) -> relu(norm(block_3) + shortcut) [N,H/stride,W/stride,cout].
-        Each raw conv output is read by its consumer through the producer's folded norm and relu."""
+        Each raw conv output is read by its consumer through the producer's folded norm and relu.  keep: x, r1, r2, r3, sc (None
+        for the identity shortcut) and out, in buffers bt/<scope>/*."""
         from . import hip
         from .hip import ACT_RELU, View
         d = self.d
@@ -370,59 +423,74 @@ class MatchModel(object):
         oh, ow = -(-h // stride), -(-w // stride)
         w1, w2, w3 = (d['%s/block_%d/conv/DW' % (scope, k)] for k in (1, 2, 3))
         c4, cout = w1.shape[3], w3.shape[3]
-        r1 = self._buf('r1', (n, oh, ow, c4))
+        # inference: the units share r1, r2, r3 and sc, and alternate between two outputs (a unit reads its predecessor's)
+        own, out_tag = ('', 'out%d' % slot) if keep is None else ('bt/%s/' % scope, 'bt/%s/out' % scope)
+        r1 = self._buf(own + 'r1', (n, oh, ow, c4))
         hip.conv_forward(View(x), w1, stride, 0, r1, same=True)
-        r2 = self._buf('r2', (n, oh, ow, c4))
+        r2 = self._buf(own + 'r2', (n, oh, ow, c4))
         hip.conv_forward(View(r1, None, d[scope + '/block_1/bn'], ACT_RELU), w2, 1, 0, r2, same=True)
-        r3 = self._buf('r3', (n, oh, ow, cout))
+        r3 = self._buf(own + 'r3', (n, oh, ow, cout))
         hip.conv_forward(View(r2, None, d[scope + '/block_2/bn'], ACT_RELU), w3, 1, 0, r3, same=True)
-        out = self._buf('out%d' % slot, (n, oh, ow, cout))
+        out = self._buf(out_tag, (n, oh, ow, cout))
         assert out.data_ptr() != x.data_ptr()
         wadd = d.get(scope + '/block_add/conv/DW')
+        sc = None
         if wadd is not None:
-            sc = self._buf('sc', (n, oh, ow, cout))
+            sc = self._buf(own + 'sc', (n, oh, ow, cout))
             hip.conv_forward(View(x), wadd, stride, 0, sc, same=True)
-            hip.call('ssc_residual_merge', r3, d[scope + '/block_3/bn'], sc, d[scope + '/block_add/bn'], ACT_RELU, out,
-                     n * oh * ow, cout)
         else:
             assert cin == cout and stride == 1, (scope, cin, cout, stride)
-            hip.call('ssc_residual_merge', r3, d[scope + '/block_3/bn'], x, None, ACT_RELU, out, n * oh * ow, cout)
+        hip.call('ssc_residual_merge', r3, d[scope + '/block_3/bn'], x if sc is None else sc, d.get(scope + '/block_add/bn'), ACT_RELU,
+                 out, n * oh * ow, cout)
+        if keep is not None:
+            keep.update(scope=scope, stride=stride, x=x, r1=r1, r2=r2, r3=r3, sc=sc, out=out)
         return out
 
-    def regroup(self, x, rate_from, rate_to):
-        """x in the space-to-batch layout of rate_from (1: the image itself) -> the layout of rate_to (2 or 4): one
-        ssc_space_to_batch(2).  Applied to the rate-2 layout it leaves sub-image (n*4 + i1*2 + j1)*4 + i2*2 + j2 with the pixels
-        y % 4 == 2*i2 + i1, x % 4 == 2*j2 + j1: every sub-image is one residue class mod 4, which is all a rate-4 conv asks."""
+    def regroup(self, x, rate_from, rate_to, tag='s2b'):
+        """x in the space-to-batch layout of rate_from (1: the image itself) -> the layout of rate_to (2 or 4), in the buffer
+        ``tag``: one ssc_space_to_batch(2).  Applied to the rate-2 layout it leaves sub-image (n*4 + i1*2 + j1)*4 + i2*2 + j2 with
+        the pixels y % 4 == 2*i2 + i1, x % 4 == 2*j2 + j1: every sub-image is one residue class mod 4, which is all a rate-4 conv
+        asks."""
         from . import hip
         assert rate_to == 2 * rate_from, (rate_from, rate_to)
         n, h, w, c = x.shape
-        return hip.space_to_batch(x, 2, out=self._buf('s2b', (n * 4, h // 2, w // 2, c)))
+        return hip.space_to_batch(x, 2, out=self._buf(tag, (n * 4, h // 2, w // 2, c)))
 
-    def ungroup(self, x, rate):
-        """The way back from ``regroup``: one ssc_batch_to_space(2) per halving of the rate."""
+    def ungroup(self, x, rate, tag='b2s'):
+        """The way back from ``regroup``: one ssc_batch_to_space(2) per halving of the rate, into the buffer ``tag`` formatted
+        with the rate it arrives at."""
         from . import hip
         while rate > 1:
             nb, h, w, c = x.shape
-            x = hip.batch_to_space(x, 2, out=self._buf('b2s', (nb // 4, h * 2, w * 2, c)))
             rate //= 2
+            x = hip.batch_to_space(x, 2, out=self._buf(tag.format(rate), (nb // 4, h * 2, w * 2, c)))
         return x
 
-    def backbone(self, x4):
-        """x4 float [1,S,S,4] (ssc_match_preprocess_u8) -> the visual feature [1,S/8,S/8,filters[4]]."""
+    def backbone(self, x4, keep=None):
+        """x4 float [1,S,S,4] (ssc_match_preprocess_u8) -> the visual feature [1,S/8,S/8,filters[4]].  keep: x4, r0 (conv1's raw
+        output) and units, the list of every unit's record with ``regroups``, the space_to_batch(2) moves in front of it; the
+        buffers are those of match_backbone_train.forward_buffer_shapes."""
         from . import hip
         from .hip import View
         c, d = self.cfg, self.d
         s = c.size
-        r0 = self._buf('conv1', (1, s // 2, s // 2, c.filters[0]))
+        own = '' if keep is None else 'bt/'
+        r0 = self._buf(own + 'conv1', (1, s // 2, s // 2, c.filters[0]))
         hip.conv_forward(View(x4), d['ResNet/group_1/conv1/DW'], 2, 0, r0, same=True)
-        x = hip.max_pool3s2(r0, d['ResNet/group_1/bn_conv1'], out=self._buf('pool', (1, s // 4, s // 4, c.filters[0])))
-        cur = 1
+        x = hip.max_pool3s2(r0, d['ResNet/group_1/bn_conv1'], out=self._buf(own + 'pool', (1, s // 4, s // 4, c.filters[0])))
+        cur, units = 1, []
         for k, (scope, _cin, _cout, stride, rate) in enumerate(c.unit_list()):
+            rec = None if keep is None else {'regroups': 0}
             while cur < rate:
-                x = self.regroup(x, cur, cur * 2)
+                x = self.regroup(x, cur, cur * 2, 's2b' if keep is None else 'bt/s2b%d' % (cur * 2))
                 cur *= 2
-            x = self.unit(x, scope, stride, k & 1)
-        return self.ungroup(x, cur)     # group_last's relu: the last unit's output is one already
+                if rec is not None:
+                    rec['regroups'] += 1
+            x = self.unit(x, scope, stride, k & 1, keep=rec)
+            units.append(rec)
+        if keep is not None:
+            keep.update(units=units, x4=x4, r0=r0)
+        return self.ungroup(x, cur, 'b2s' if keep is None else 'bt/b2s{}')     # group_last's relu: the last unit's output is one already
 
     # ------------------------------------------------------------------ head
     def _lstm_planes(self, tag, rows, C):
@@ -432,16 +500,37 @@ class MatchModel(object):
             return None
         return self._buf(tag, (2, hip.lstm_hplanes_floats(rows, C)), zero=True)
 
-    def head(self, feat, tok, seq_len):
-        """feat float [1,h,w,filters[4]], tok int32 [T] on the device, seq_len on the host -> pred float [h,w]."""
-        import torch
+    def _cell(self, keep, name, Kh, C, rows, gates_in, c_st, h_st, L, each=None):
+        """L steps of an LSTM cell on ``rows`` rows: state t is plane t % P of c_st / h_st [P, rows, C] (state 0 filled by the
+        caller), gates_in(t) -> (g1, g2) are the step's two shares of the gates from outside, each(t, h) runs behind step t.
+        -> the activated gates [planes, rows, 4C], step t in plane t % planes.  Inference reads no step's gates again: one
+        plane, and None where the bf16 step form leaves the store out.  keep: a plane per step, on the bf16 step form too."""
+        from . import hip
+        if keep is not None:
+            acts = self._buf('t_acts_' + name, (self.cfg.max_len, rows, 4 * C))
+        else:
+            acts = None if hip.lstm_bf(C, 4 * C) else self._buf('acts_' + name, (1, rows, 4 * C))
+        hp, P = self._lstm_planes('hp' + name, rows, C), len(c_st)
+        for t in range(L):
+            a, b = t % P, (t + 1) % P
+            g1, g2 = gates_in(t)
+            # the step mask ``one``: every row is live (t < seq_len is decided here, on the host)
+            hip.lstm_step_fwd(h_st[a], Kh, 4 * C, g1, g2, rows, self.one, rows, c_st[a], rows, C, t > 0, c_st[b], h_st[b],
+                              None if acts is None else acts[t % len(acts)],
+                              hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
+            if each is not None:
+                each(t, h_st[b])
+        return acts
+
+    def head(self, feat, tok, seq_len, keep=None):
+        """feat float [1,h,w,filters[4]], tok int32 [T] on the device, seq_len on the host -> pred float [h,w].  keep: the cell
+        state, the output and the activated gates of every step of both cells stay (MatchTrainer.backward reads them from it)."""
         from . import hip
         from .hip import View
         c, d = self.cfg, self.d
         _, fh, fw, _ = feat.shape
         R, L, cw, cm = fh * fw, int(seq_len), self.cw, self.cm
         assert 1 <= L <= c.max_len and (fh, fw) == (c.feat, c.feat)
-        one = self.one      # the step mask: every row is live (t < seq_len is decided here, on the host)
         # visual: projection, l2 norm, and its share (with the spatial table's) of the multimodal gates
         vp = self._buf('vproj', (1, fh, fw, c.v_emb))
         hip.conv_forward(View(feat), d['vproj/w'], 1, 0, vp, bias=d['vproj/b'], same=True)
@@ -456,45 +545,39 @@ class MatchModel(object):
         ew = self._buf('ew', (c.max_len, 4 * cw))
         hip.matmul(emb[:L], d['w/Kx'], ew[:L], bias=d['w/b'])
         cs, hs = self._buf('cw', (c.max_len + 1, cw), zero=True), self._buf('hw', (c.max_len + 1, cw), zero=True)
-        acts_w = None if hip.lstm_bf(cw, 4 * cw) else self._buf('acts_w', (1, 4 * cw))
-        hp = self._lstm_planes('hpw', 1, cw)
-        for t in range(L):
-            hip.lstm_step_fwd(hs[t], d['w/Kh'], 4 * cw, ew[t:t + 1], None, 1, one, 1, cs[t], 1, cw, t > 0, cs[t + 1], hs[t + 1], acts_w,
-                              hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
+        own = '' if keep is None else 't_'
+        acts_w = self._cell(keep, 'w', d['w/Kh'], cw, 1, lambda t: (ew[t:t + 1], None), cs, hs, L)
         attn = acc = None
         if c.use_attn:      # the weights of the T positions: rows L .. of hs hold an earlier, longer sentence and are not read
-            attn = hip.attn_scores_fwd(hs[1:], d['attn/w'], d['attn/b'], c.w_rnn, L, out=self._buf('attn', (c.max_len,)))
-            acc = self._buf('attn_acc', (R, cm))
+            attn = hip.attn_scores_fwd(hs[1:], d['attn/w'], d['attn/b'], c.w_rnn, L, out=self._buf(own + 'attn', (c.max_len,)))
+            acc = self._buf(own + 'attn_acc', (R, cm))
         lang, lang_ss = self._buf('lang', (c.max_len, cw)), self._buf('lang_ss', (c.max_len,))
         hip.call('ssc_row_l2norm_fwd', hs[1:], cw, None, L, cw, lang, lang_ss)
         gt = self._buf('g_t', (c.max_len, 4 * cm))
         hip.matmul(emb[:L], d['m/Kw'], gt[:L], bias=d['m/b'])
         hip.matmul(lang[:L], d['m/Kl'], gt[:L], accumulate=True)
-        # multimodal LSTM: every location a row, the word's share of the gates the same for all of them
-        ca, ha = self._buf('ca', (2, R, cm)), self._buf('ha', (2, R, cm))
-        hip.fill(ca[0], 0.0)
-        hip.fill(ha[0], 0.0)
-        acts_m = None if hip.lstm_bf(cm, 4 * cm) else self._buf('acts_m', (R, 4 * cm))
-        hp = self._lstm_planes('hpm', R, cm)
-        for t in range(L):
-            a, b = t & 1, (t + 1) & 1
-            hip.lstm_step_fwd(ha[a], d['m/Kh'], 4 * cm, gs, gt[t:t + 1], R, one, R, ca[a], R, cm, t > 0, ca[b], ha[b], acts_m,
-                              hp_in=None if hp is None or t == 0 else hp[(t - 1) & 1], hp_out=None if hp is None else hp[t & 1])
-            if acc is not None:     # acc (+)= attn[t] * m_out[t]; the outputs past L are zero and add nothing
-                hip.dev_scaled_add(acc, ha[b], attn, t, overwrite=t == 0)
-        pred = hip.squash_project(ha[L & 1] if acc is None else acc, d['proj/w'], d['proj/b'], C=c.m_rnn, out=self._buf('pred', (R,)))
+        # multimodal LSTM: every location a row, the word's share of the gates the same for all of them.  Inference alternates its
+        # states between two planes: step 2 overwrites plane 0, so every pass zeroes it.  keep: a plane per state; state 0 is a
+        # zero nobody writes (the steps store 1 .. L)
+        P = 2 if keep is None else c.max_len + 1
+        ca, ha = (self._buf(own + tag, (P, R, cm), zero=keep is not None) for tag in ('ca', 'ha'))
+        if keep is None:
+            hip.fill(ca[0], 0.0)
+            hip.fill(ha[0], 0.0)
+        # acc (+)= attn[t] * m_out[t]; the outputs past L are zero and add nothing
+        weigh = None if acc is None else lambda t, h: hip.dev_scaled_add(acc, h, attn, t, overwrite=t == 0)
+        acts_m = self._cell(keep, 'm', d['m/Kh'], cm, R, lambda t: (gs, gt[t:t + 1]), ca, ha, L, each=weigh)
+        pred = hip.squash_project(ha[L % P] if acc is None else acc, d['proj/w'], d['proj/b'], C=c.m_rnn, out=self._buf(own + 'pred', (R,)))
+        if keep is not None:
+            keep.update(feat=feat, tok=tok, L=L, R=R, fh=fh, fw=fw, vis=vis, vis_ss=vis_ss, emb=emb, cs=cs, hs=hs, acts_w=acts_w,
+                        lang=lang, lang_ss=lang_ss, ca=ca, ha=ha, acts_m=acts_m, attn=attn, acc=acc)
         return pred.view(fh, fw)
 
     # ------------------------------------------------------------------ the whole pass
-    def upload(self, sketch_u8, indices, seq_len):
-        """The inputs into their device buffers; -> (sketch uint8 [S,S,3], tok int32 [T], seq_len)."""
-        import torch
+    def check_sentence(self, indices, seq_len):
+        """The sentence's T indices and its real length -> (int32 [T] on the host, seq_len).  ValueError for another count of
+        indices, a length outside 1 .. T or an index outside the vocabulary (ssc_embedding_gather does not clamp)."""
         c = self.cfg
-        if not self.loaded:
-            raise RuntimeError('the matcher has no weights: load_tf_checkpoint or init_random first')
-        sk = sketch_u8 if isinstance(sketch_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sketch_u8))
-        if sk.dtype != torch.uint8 or tuple(sk.shape) != (c.size, c.size, 3):
-            raise ValueError('the sketch is %s %s, the matcher reads uint8 [%d, %d, 3]' % (sk.dtype, tuple(sk.shape), c.size, c.size))
         idx = np.asarray(indices, dtype=np.int64).reshape(-1)
         seq_len = int(seq_len)
         if idx.shape[0] != c.max_len or not 1 <= seq_len <= c.max_len:
@@ -502,11 +585,36 @@ class MatchModel(object):
         if idx.min() < 0 or idx.max() >= c.vocab_size:
             raise ValueError('word index %d outside the vocabulary of %d' % (int(idx.max() if idx.max() >= c.vocab_size else idx.min()),
                                                                              c.vocab_size))
+        return idx.astype(np.int32), seq_len
+
+    def put_sentence(self, tok):
+        """``check_sentence``'s indices into the ``tok`` buffer."""
+        import torch
+        tok_d = self._buf('tok', (self.cfg.max_len,), torch.int32)
+        tok_d.copy_(torch.from_numpy(tok))
+        return tok_d
+
+    def put_sketch(self, sketch_u8, check_only=False):
+        """sketch uint8 [S,S,3], host or device, into the ``sketch`` buffer (a sketch that already is that buffer stays where it
+        is).  RuntimeError without weights, ValueError for another type or shape; check_only: nothing is copied."""
+        import torch
+        c = self.cfg
+        if not self.loaded:
+            raise RuntimeError('the matcher has no weights: load_tf_checkpoint or init_random first')
+        sk = sketch_u8 if isinstance(sketch_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sketch_u8))
+        if sk.dtype != torch.uint8 or tuple(sk.shape) != (c.size, c.size, 3):
+            raise ValueError('the sketch is %s %s, the matcher reads uint8 [%d, %d, 3]' % (sk.dtype, tuple(sk.shape), c.size, c.size))
         skd = self._buf('sketch', (c.size, c.size, 3), torch.uint8)
-        skd.copy_(sk)
-        tok = self._buf('tok', (c.max_len,), torch.int32)
-        tok.copy_(torch.from_numpy(idx.astype(np.int32)))
-        return skd, tok, seq_len
+        if not check_only and skd.data_ptr() != sk.data_ptr():
+            skd.copy_(sk)
+        return skd
+
+    def upload(self, sketch_u8, indices, seq_len):
+        """The inputs into their device buffers; -> (sketch uint8 [S,S,3], tok int32 [T], seq_len).  Both are checked before
+        either is copied."""
+        self.put_sketch(sketch_u8, check_only=True)
+        tok, seq_len = self.check_sentence(indices, seq_len)
+        return self.put_sketch(sketch_u8), self.put_sentence(tok), seq_len
 
     def forward(self, sketch_u8, indices, seq_len):
         """sketch uint8 [S,S,3] (host or device), the sentence's T indices and its real length ->
@@ -522,26 +630,22 @@ class MatchModel(object):
                                 predicts=self._buf('predicts', (c.size, c.size), torch.uint8))
 
     # ------------------------------------------------------------------ the pass in two halves (match_eval.py)
-    def features(self, sketch_u8):
+    def features(self, sketch_u8, keep=None):
         """The half of ``forward`` that does not read the sentence: sketch uint8 [S,S,3] (host or device) -> (feat float
         [1,S/8,S/8,filters[4]], stroke uint8 [S,S]), both in buffers of their own that only the next ``features`` overwrites --
-        no ``head``, ``predict`` or ``forward`` call touches them."""
+        no ``head``, ``predict`` or ``forward`` call touches them.  keep: ``backbone``'s."""
         import torch
         from . import hip
         c = self.cfg
-        if not self.loaded:
-            raise RuntimeError('the matcher has no weights: load_tf_checkpoint or init_random first')
-        sk = sketch_u8 if isinstance(sketch_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sketch_u8))
-        if sk.dtype != torch.uint8 or tuple(sk.shape) != (c.size, c.size, 3):
-            raise ValueError('the sketch is %s %s, the matcher reads uint8 [%d, %d, 3]' % (sk.dtype, tuple(sk.shape), c.size, c.size))
-        skd = self._buf('sketch', (c.size, c.size, 3), torch.uint8)
-        skd.copy_(sk)
-        x4, _ = hip.match_preprocess_u8(skd, out=self._buf('x4', (1, c.size, c.size, 4)),
-                                        stroke=self._buf('stroke_kept', (c.size, c.size), torch.uint8))
-        feat = self.backbone(x4)
-        kept = self._buf('feat_kept', tuple(feat.shape))
-        kept.copy_(feat)
-        return kept, self._buf('stroke_kept', (c.size, c.size), torch.uint8)
+        skd = self.put_sketch(sketch_u8)
+        x4, stroke = hip.match_preprocess_u8(skd, out=self._buf('x4', (1, c.size, c.size, 4)),
+                                             stroke=self._buf('stroke_kept', (c.size, c.size), torch.uint8))
+        feat = self.backbone(x4, keep)
+        if keep is None:    # the map lies in a buffer the next backbone pass reuses (b2s); a kept pass gave it one of its own
+            kept = self._buf('feat_kept', tuple(feat.shape))
+            kept.copy_(feat)
+            feat = kept
+        return feat, stroke
 
     def predict(self, feat, stroke, indices, seq_len):
         """The other half: what ``features`` returned, the sentence's T indices and its real length -> (up float [S,S],
@@ -549,16 +653,8 @@ class MatchModel(object):
         import torch
         from . import hip
         c = self.cfg
-        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
-        seq_len = int(seq_len)
-        if idx.shape[0] != c.max_len or not 1 <= seq_len <= c.max_len:
-            raise ValueError('%d indices with %d real ones: the matcher reads %d, at least one real' % (idx.shape[0], seq_len, c.max_len))
-        if idx.min() < 0 or idx.max() >= c.vocab_size:
-            raise ValueError('word index %d outside the vocabulary of %d' % (int(idx.max() if idx.max() >= c.vocab_size else idx.min()),
-                                                                             c.vocab_size))
-        tok = self._buf('tok', (c.max_len,), torch.int32)
-        tok.copy_(torch.from_numpy(idx.astype(np.int32)))
-        pred = self.head(feat, tok, seq_len)
+        tok, seq_len = self.check_sentence(indices, seq_len)
+        pred = self.head(feat, self.put_sentence(tok), seq_len)
         return hip.match_finish(pred, stroke, up=self._buf('up', (c.size, c.size)),
                                 predicts=self._buf('predicts', (c.size, c.size), torch.uint8))
 

@@ -277,6 +277,27 @@ def test_head_train_has_the_bits_of_head(key, seq_len):
     assert torch.equal(model.head(feat, tok, seq_len), want)            # and head still gives them after a training pass
 
 
+@pytest.mark.parametrize('widths,use_attn', [('narrow', 0), ('narrow', 1), ('bf', 0), ('bf', 1)])
+def test_one_forward_gives_the_parents_bits(widths, use_attn):
+    """profiles/match_forward_once.txt keeps the digests scripts/match_forward_digest.py printed on the parent commit's tree, where
+    the head and the backbone were written out once for inference and once for training: head at L = 15, 3, 1, forward, features,
+    predict, three steps of the head trainer (one from a device-resident scene with its feature map) and two of the backbone
+    trainer on units (2, 1, 2, 2), their snapshots' bytes, a resumed step, and the names that went through hip.call in order.
+    This tree's are the same, every line."""
+    sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+    try:
+        import match_forward_digest as D
+    finally:
+        sys.path.pop(0)
+    tag = D.case_name(widths, use_attn) + ' '
+    want = {k: v for k, v in D.recorded(os.path.join(ROOT, 'profiles', 'match_forward_once.txt')).items() if k.startswith(tag)}
+    got = dict(D.digests(widths, use_attn))
+    assert len(want) == 35 and set(got) == set(want), set(got) ^ set(want)
+    for what, sha in got.items():
+        print('%s: %s' % (what, sha))
+        assert sha == want[what], what
+
+
 def _real_entries(trainer):
     """1 where the flat head buffer holds an entry of a variable, 0 on the padding."""
     ones = {n: np.ones(s, np.float32) for n, s in trainer.cfg.variable_shapes().items() if n.startswith(TO.P)}

@@ -456,6 +456,8 @@ def test_whole_small_model(which, small_model_64, small_model_96):
         sure = np.abs(up64 - 1e-9) > bound
         assert (~sure).mean() <= 0.005
         up, pr = model.forward(sk, idx, n)
+        # inference keeps nothing for a backward pass: no buffer of the training passes (t_*, bt/*, bb/*) is allocated
+        assert model._bufs and not [k for k in model._bufs if str(k[0]).startswith(('t_', 'bt/', 'bb/'))]
         up, pr = up.cpu().numpy().astype(np.float64), pr.cpu().numpy()
         err = np.abs(up - up64).max()
         print('whole model size %d seq_len %d: device %.3e, float32 oracle %.3e (relative to max|up| = %.3e: %.3e and %.3e), bound %.3e'

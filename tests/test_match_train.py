@@ -4,6 +4,7 @@ tests/match_train_oracle.py against tests/matching_oracle.py."""
 import json
 import os
 import random
+import sys
 
 import numpy as np
 import pytest
@@ -46,6 +47,22 @@ def test_export_inverts_load_bit_for_bit(widths):
     assert trainer.hi == model._layout['spatial'][0] and trainer.params.numel() == trainer.grad.numel() == trainer.hi - trainer.lo
     assert sum(p for _o, _s, p, _sh in trainer.spans.values()) == trainer.hi - trainer.lo
     model.close()
+
+
+def test_initial_variables_have_the_parents_bits():
+    """profiles/match_forward_once.txt keeps the digests scripts/match_forward_digest.py printed on the parent commit's tree; its
+    ``host`` lines are random_variables(cfg, 41) and init_head(cfg, 5) of both head widths with the attention off and on, which
+    every recorded digest and parity file rests on.  This tree's are the same."""
+    sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+    try:
+        import match_forward_digest as D
+    finally:
+        sys.path.pop(0)
+    want = {k: v for k, v in D.recorded(os.path.join(ROOT, 'profiles', 'match_forward_once.txt')).items() if ' host ' in k}
+    got = dict(line for case in D.CASES for line in D.host_digests(*case))
+    assert len(want) == 8 and set(got) == set(want), set(got) ^ set(want)
+    for what, sha in got.items():
+        assert sha == want[what], what
 
 
 def test_init_head_follows_the_reference_initialisers():
