@@ -837,6 +837,17 @@ int ssc_attn_plane_dots(const float* dacc, const float* H, int64_t stride, int64
 int ssc_attn_scores_bwd(const float* attn, const float* dattn, const float* hs, int ld, const float* w, int C, int L, int T,
                         float* dlogit, float* dw, float* db, float* dhs, int ldd, void* stream);
 
+/* --- the matcher's SegNet backbone (match_segnet.hip): Instance_Matching/segnet_model.py with is_intermediate; DESIGN.md
+ *     section 8.12.  NHWC floats, C a multiple of 4, float pointers on a 16-byte boundary and code on a 4-byte one (-3); -1 for any
+ *     other bad argument, nothing is launched then.  No atomics: the same bits on every run.  Each is the other's backward. --- */
+/* tf.nn.max_pool_with_argmax(2x2, stride 2) of relu(ab[c]*x + ab[C+c]) (ab == NULL: of x itself, no relu): x [N,H,W,C], H and W
+ * even -> out [N,H/2,W/2,C] and code uint8 of that shape = 2*dy + dx of the first tap in row-major order that attains the maximum
+ * (TF's choice; the tie rule of ssc_max_pool3s2_bwd).  TF's flat index of the element is ((2y+dy)*W + 2x+dx)*C + c. */
+int ssc_max_pool2_argmax(const float* x, const float* ab, int N, int H, int W, int C, float* out, uint8_t* code, void* stream);
+/* segnet_model.py::_unpool_2d: x, code [N,h,w,C] -> out [N,2h,2w,C]; out[n,2y+dy,2x+dx,c] = x[n,y,x,c] where
+ * (code[n,y,x,c] & 3) == 2*dy + dx and 0 at the window's three other positions.  Every element of out is written. */
+int ssc_unpool2(const float* x, const uint8_t* code, int N, int h, int w, int C, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,12 @@ hold the filters' Adam slots; --scene_cache off and device work, features does n
 
 --use_attn 1, in every mode, is the model class's use_attn (RMI_model.py:202-217): a softmax over the word
 LSTM's outputs weighs the multimodal LSTM's outputs of every word.  --mode train then also trains attn_fc/DW and attn_fc/biases,
---mode match writes the weights into match.json as "attention"; a snapshot is read with the flag it was trained with."""
+--mode match writes the weights into match.json as "attention"; a snapshot is read with the flag it was trained with.
+
+--weights segnet, in every mode, is the reference's --model segnet (segnet_model.py with is_intermediate):
+the SegNet backbone, whose norms take the statistics of the one image, in place of the DeepLab-ResNet.  --mode train then takes
+SegNet/* from --backbone_snapshot, trains the head on the frozen backbone (--train_backbone 1 is refused) and writes
+segnet_RMI_iter_<n>.tfmodel; --mode eval writes segnet_RMI_<split>_result.txt; a snapshot is read with the --weights it holds."""
 import argparse
 import json
 import os
@@ -50,6 +55,8 @@ FLAGS = [
     ('results_dir', str, 'outputs/match_results', 'where <id>/match.json and <id>/<id>_match.png go'),
     ('use_attn', int, 0, "1: the head with the model class's word attention (use_attn of RMI_model.py), for a checkpoint trained "
                          'with it, and to train one; match.json then holds the weights as "attention"'),
+    ('weights', str, 'deeplab', "the backbone, in every mode: 'deeplab' (the DeepLab-ResNet) or 'segnet' (SegNet with the norms of "
+                                "the one image); the reference's --model.  'fcn_8s' and 'deeplab_v3plus' are not built"),
 ]
 EVAL_FLAGS = [
     ('data_base_dir', str, '../data', 'eval: the SketchyScene data, with <split>/INSTANCE_GT and <split>/DRAWING_GT'),
@@ -80,7 +87,6 @@ TRAIN_FLAGS = [
     ('gpus', int, 1, 'train: 1'),
     ('graph', int, 0, 'train: 0; the step is not captured'),
     ('keep_prob', float, 1.0, 'train: 1; dropout is not built'),
-    ('weights', str, 'deeplab', "train: 'deeplab'"),
     ('fusion_type', str, 'RMI', "train: 'RMI'; 'RecurAttn' is not built (the attention that is built is --use_attn 1)"),
     ('summary', int, 0, 'train: 0; event summaries are not written'),
     ('scene_cache', str, 'off', "train: 'off' (every iteration reads its scene's files), 'device' (every scene's sketch and label "
@@ -99,11 +105,33 @@ def checked_use_attn(args):
     return bool(args.use_attn)
 
 
-def checked_snapshot_attention(prefix, use_attn):
-    """The snapshot's variable names against --use_attn, read from its index alone: MatchModel.load_dict's refusal, before
-    anything is allocated."""
+def checked_weights(args):
+    """--weights: -> 'deeplab' or 'segnet', anything else is a ValueError."""
+    from sketchyscenecolorization_amd import matching
+    if args.weights not in matching.BACKBONES:
+        raise ValueError('--weights %r: only %s (the other backbones are not built)'
+                         % (args.weights, ' or '.join(repr(b) for b in matching.BACKBONES)))
+    return args.weights
+
+
+def checked_snapshot_attention(prefix, use_attn, backbone='deeplab'):
+    """The snapshot's variable names against --use_attn and --weights, read from its index alone: MatchModel.load_dict's
+    refusals, before anything is allocated."""
     from sketchyscenecolorization_amd import matching, tf_checkpoint
-    matching.check_attention_variables({name for name, _shape, _dtype in tf_checkpoint.list_variables(prefix)}, use_attn)
+    names = {name for name, _shape, _dtype in tf_checkpoint.list_variables(prefix)}
+    matching.check_backbone_variables(names, backbone)
+    matching.check_attention_variables(names, use_attn)
+
+
+def reserved_model(cfg):
+    """The MatchModel of a configuration.  With the SegNet backbone the scratch memory of its pass is added up first, printed, and
+    refused as a ValueError when it is more than half of what is free on the device."""
+    from sketchyscenecolorization_amd import matching
+    if cfg.backbone == 'segnet':
+        import torch
+        print('segnet backbone: %d bytes of scratch memory on the device'
+              % matching.check_segnet_scratch(cfg, torch.cuda.mem_get_info()[0]))
+    return matching.MatchModel(cfg)
 
 
 def agreed_config(config, cfg):
@@ -112,6 +140,8 @@ def agreed_config(config, cfg):
         raise ValueError('the given configuration and --scene_size / --vocab_size / --text_len disagree')
     if bool(getattr(config, 'use_attn', False)) != cfg.use_attn:
         raise ValueError('the given configuration has use_attn %r, --use_attn is %d' % (config.use_attn, int(cfg.use_attn)))
+    if getattr(config, 'backbone', 'deeplab') != cfg.backbone:
+        raise ValueError('the given configuration has the backbone %r, --weights is %r' % (config.backbone, cfg.backbone))
     return config
 
 
@@ -132,10 +162,11 @@ def checked_arguments(args):
         raise ValueError('--snapshot <directory or checkpoint prefix> is needed: the matcher has no weights of its own')
     if args.image_id is None or args.image_id == '' or args.instruction == '':
         raise ValueError("--image_id <id> and --instruction '<text>' are needed")
-    use_attn = checked_use_attn(args)
+    use_attn, weights = checked_use_attn(args), checked_weights(args)
     if args.text_len < 1:
         raise ValueError('--text_len %d: at least one word' % args.text_len)
-    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn)
+    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn,
+                                  backbone=weights)
     if not matching.sentence_tokens(args.instruction):
         raise ValueError('--instruction %r holds no word' % args.instruction)
     if not os.path.isfile(args.vocab_file):
@@ -145,7 +176,7 @@ def checked_arguments(args):
         raise ValueError('--vocab_file %r holds %d words, --vocab_size is %d; <unk> and <pad> must be among them'
                          % (args.vocab_file, len(vocab), args.vocab_size))
     prefix = matching.resolve_snapshot(args.snapshot)
-    checked_snapshot_attention(prefix, use_attn)
+    checked_snapshot_attention(prefix, use_attn, weights)
     for sub, name in (('sketches', args.image_id + '.png'), ('inner_masks', args.image_id + '.mat'),
                       ('seg_data', args.image_id + '_datas.npz')):
         if not os.path.isfile(os.path.join(args.scene_dir, sub, name)):
@@ -163,14 +194,15 @@ def checked_eval_arguments(args):
         raise ValueError("--dataset %r: 'val' or 'test'" % args.dataset)
     if args.mask_ap not in (0, 1):
         raise ValueError('--mask_ap %d: 0 or 1' % args.mask_ap)
-    use_attn = checked_use_attn(args)
+    use_attn, weights = checked_use_attn(args), checked_weights(args)
     if args.max_scenes < 0:
         raise ValueError('--max_scenes %d: a count, 0 for every scene' % args.max_scenes)
     if args.text_len < 1:
         raise ValueError('--text_len %d: at least one word' % args.text_len)
     if args.eval_result_root == '':
         raise ValueError('--eval_result_root is empty')
-    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn)
+    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn,
+                                  backbone=weights)
     if not os.path.isfile(args.vocab_file):
         raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
     vocab = matching.load_vocab(args.vocab_file)
@@ -178,7 +210,7 @@ def checked_eval_arguments(args):
         raise ValueError('--vocab_file %r holds %d words, --vocab_size is %d; <unk> and <pad> must be among them'
                          % (args.vocab_file, len(vocab), args.vocab_size))
     prefix = matching.resolve_snapshot(args.snapshot)
-    checked_snapshot_attention(prefix, use_attn)
+    checked_snapshot_attention(prefix, use_attn, weights)
     scenes = match_eval.read_captions(args.captions_base_dir, args.dataset)
     if args.max_scenes:
         scenes = scenes[:args.max_scenes]
@@ -204,8 +236,8 @@ def evaluate(args, config=None, predicts_out=None):
         cfg = agreed_config(config, cfg)
     import random
     import numpy as np
-    from sketchyscenecolorization_amd import match_eval, matching
-    model = matching.MatchModel(cfg)
+    from sketchyscenecolorization_amd import match_eval, match_train, matching
+    model = reserved_model(cfg)
     model.load_tf_checkpoint(prefix)
     rng = None if args.augment_seed is None else random.Random(args.augment_seed)
     kept = [] if predicts_out is not None else None
@@ -215,7 +247,7 @@ def evaluate(args, config=None, predicts_out=None):
     block = totals.block(prefix)
     print(block)
     os.makedirs(args.eval_result_root, exist_ok=True)
-    with open(os.path.join(args.eval_result_root, 'deeplab_RMI_%s_result.txt' % args.dataset), 'a') as f:
+    with open(os.path.join(args.eval_result_root, '%s_%s_result.txt' % (match_train.model_name(cfg.backbone), args.dataset)), 'a') as f:
         f.write(block)
     record = dict(totals.record(), split=args.dataset, snapshot=prefix, scenes=len(scenes), augment_seed=args.augment_seed,
                   per_caption=records)
@@ -239,15 +271,15 @@ def checked_train_arguments(args):
     """--mode train: every bad argument and every missing file of the whole caption file is a ValueError here, before any weight
     is read or anything is written.  -> (config, vocab, training tuples, the snapshot to resume from or None, the backbone's
     checkpoint prefix or None)."""
-    from sketchyscenecolorization_amd import match_eval, match_train, matching
+    from sketchyscenecolorization_amd import match_eval, match_train, matching, tf_checkpoint
     for name, want, why in (('train_fusion_var_only', 1, 'the backbone is trained with --train_backbone 1'),
                             ('training_ignore_bg', 1, 'the loss over every pixel is not built'),
                             ('batch_size', 1, 'the reference trains one tuple per iteration'), ('gpus', 1, 'one device'),
                             ('graph', 0, 'the step is not captured'), ('keep_prob', 1.0, 'dropout is not built'),
-                            ('weights', 'deeplab', 'the other backbones are not built'),
                             ('fusion_type', 'RMI', "'RecurAttn' is not built; the attention that is built is --use_attn 1"), ('summary', 0, 'event summaries are not written')):
         if getattr(args, name) != want:
             raise ValueError('--%s %r: only %r (%s)' % (name, getattr(args, name), want, why))
+    weights = checked_weights(args)
     if args.max_iteration < 1 or args.save_model_freq < 1 or args.log_freq < 1:
         raise ValueError('--max_iteration %d, --save_model_freq %d, --log_freq %d: each at least 1'
                          % (args.max_iteration, args.save_model_freq, args.log_freq))
@@ -262,13 +294,17 @@ def checked_train_arguments(args):
         raise ValueError("--scene_cache %r: 'off', 'device' or 'features'" % args.scene_cache)
     if args.train_backbone not in (0, 1):
         raise ValueError('--train_backbone %d: 0 (the fusion head alone) or 1 (and the backbone)' % args.train_backbone)
+    if args.train_backbone and weights == 'segnet':
+        raise ValueError('--train_backbone 1 --weights segnet: the SegNet backward is not built; its backbone is run frozen '
+                         '(--train_backbone 0)')
     if args.train_backbone and args.scene_cache == 'features':
         raise ValueError('--train_backbone 1 --scene_cache features: cached features are those of the initial backbone; '
                          'use --scene_cache device')
     if args.val_freq < 0 or args.val_scenes < 0:
         raise ValueError('--val_freq %d, --val_scenes %d: counts, 0 for never and for every scene' % (args.val_freq, args.val_scenes))
     use_attn = checked_use_attn(args)
-    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn)
+    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn,
+                                  backbone=weights)
     if not os.path.isfile(args.vocab_file):
         raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
     vocab = matching.load_vocab(args.vocab_file)
@@ -284,11 +320,14 @@ def checked_train_arguments(args):
         match_train.snapshot_iteration(resume)
         if not os.path.isfile(resume + '.train_state.json'):
             raise ValueError('%s.train_state.json: no such file; the snapshot cannot be resumed from' % resume)
-        checked_snapshot_attention(resume, use_attn)        # a resume goes on with the head the snapshot was trained with
+        checked_snapshot_attention(resume, use_attn, weights)       # a resume goes on with the head the snapshot was trained with
     else:
         if args.backbone_snapshot == '':
-            raise ValueError('--backbone_snapshot <directory or checkpoint prefix> is needed: a fresh run takes ResNet/* from it')
+            raise ValueError('--backbone_snapshot <directory or checkpoint prefix> is needed: a fresh run takes %s* from it'
+                             % matching.BACKBONE_SCOPE[weights])
         backbone = matching.resolve_snapshot(args.backbone_snapshot)
+        # a checkpoint of the other backbone is refused from its index; one that lacks a variable, when it is loaded
+        matching.check_backbone_variables({name for name, _s, _d in tf_checkpoint.list_variables(backbone)}, weights)
     scenes = match_eval.read_captions(args.captions_base_dir, 'train')
     if not scenes:
         raise ValueError('--captions_base_dir %r: no scene in the caption file of the train split' % args.captions_base_dir)
@@ -317,7 +356,7 @@ def build_caches(args, cfg, model, vocab, tuples):
     train_scenes = [(image_id, None) for image_id, _caption, _idx in tuples]
     n_train = len(match_cache.distinct_scenes(train_scenes)[0]) if args.scene_cache != 'off' else 0
     n_val = len(match_cache.distinct_scenes(val_scenes)[0]) if val_scenes is not None else 0
-    scene_b, feat_b = match_cache.cache_bytes(n_train, cfg.size, cfg.filters[4] if args.scene_cache == 'features' else None)
+    scene_b, feat_b = match_cache.cache_bytes(n_train, cfg.size, cfg.feat_channels if args.scene_cache == 'features' else None)
     val_b = match_cache.cache_bytes(n_val, cfg.size)[0]
     free = torch.cuda.mem_get_info(model.device)[0]
     remedy = 'run with --scene_cache off' if n_train else 'score fewer scenes (--val_scenes N) or none (--val_freq 0)'
@@ -344,7 +383,7 @@ def train(args, config=None):
     import random
     import numpy as np
     from sketchyscenecolorization_amd import match_eval, match_train, matching, tf_checkpoint
-    model = matching.MatchModel(cfg)
+    model = reserved_model(cfg)
     cursor = match_train.TupleCursor(len(tuples), random.Random(args.seed))
     start = 0
 
@@ -372,7 +411,7 @@ def train(args, config=None):
         print('loaded', resume)
     else:
         have = tf_checkpoint.read_checkpoint(backbone)
-        variables = {k: v for k, v in have.items() if k.startswith('ResNet/')}
+        variables = {k: v for k, v in have.items() if k.startswith(matching.BACKBONE_SCOPE[cfg.backbone])}
         variables.update(match_train.init_head(cfg, args.seed))
         model.load_dict(variables)
         trainer = make_trainer()
@@ -430,7 +469,7 @@ def main(argv=None, config=None, predicts_out=None):
     from sketchyscenecolorization_amd import fg_scene, matching
     scene = fg_scene.load_instances(args.scene_dir, args.image_id, cfg.size)
     matching.pack_masks(scene['boxes'], scene['masks'], cfg.size)       # a bad box is refused before the weights are read
-    model = matching.MatchModel(cfg)
+    model = reserved_model(cfg)
     model.load_tf_checkpoint(prefix)
     matched, scores, info = matching.match_instances(model, scene, args.instruction, vocab)
     model.close()

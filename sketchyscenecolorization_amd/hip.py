@@ -270,6 +270,8 @@ SIGNATURES = {
     'ssc_dev_scaled_add': [_P, _P, _P, _I, _I, _L, _I, _P],
     'ssc_attn_plane_dots': [_P, _P, _L, _L, _I, _P, _P, _L, _P],
     'ssc_attn_scores_bwd': [_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
+    'ssc_max_pool2_argmax': [_P, _P, _I, _I, _I, _I, _P, _P, _P],
+    'ssc_unpool2': [_P, _P, _I, _I, _I, _I, _P, _P],
 }
 
 
@@ -1289,6 +1291,36 @@ def max_pool3s2(x, ab=None, out=None):
         out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=torch.float32, device=x.device)
     assert out.is_contiguous() and tuple(out.shape) == (n, (h + 1) // 2, (w + 1) // 2, c), tuple(out.shape)
     check(lib().ssc_max_pool3s2(ptr(x), ptr(ab), n, h, w, c, ptr(out), stream_ptr()), 'max_pool3s2')
+    return out
+
+
+def max_pool2_argmax(x, ab=None, out=None, code=None):
+    """tf.nn.max_pool_with_argmax(2x2, stride 2) of relu(a*x + b) (ab [2C]; None: of x itself), x float [N,H,W,C] with even H, W
+    -> (out float [N,H/2,W/2,C], code uint8 of that shape: 2*dy + dx of the first tap in row-major order that attains the maximum)."""
+    n, h, w, c = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and (ab is None or (_f32c(ab) and ab.numel() == 2 * c))
+    assert h % 2 == 0 and w % 2 == 0 and c % 4 == 0, tuple(x.shape)
+    shape = (n, h // 2, w // 2, c)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if code is None:
+        code = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape, tuple(out.shape)
+    assert code.dtype == torch.uint8 and code.is_contiguous() and tuple(code.shape) == shape, tuple(code.shape)
+    check(lib().ssc_max_pool2_argmax(ptr(x), ptr(ab), n, h, w, c, ptr(out), ptr(code), stream_ptr()), 'max_pool2_argmax')
+    return out, code
+
+
+def unpool2(x, code, out=None):
+    """The way back from max_pool2_argmax (segnet_model.py::_unpool_2d): x float, code uint8 [N,h,w,C] -> out [N,2h,2w,C] with
+    x at the window position the code names and 0 at the three others; every element of out is written."""
+    n, h, w, c = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and c % 4 == 0, tuple(x.shape)
+    assert code.dtype == torch.uint8 and code.is_contiguous() and code.shape == x.shape, tuple(code.shape)
+    if out is None:
+        out = torch.empty((n, 2 * h, 2 * w, c), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 2 * h, 2 * w, c), tuple(out.shape)
+    check(lib().ssc_unpool2(ptr(x), ptr(code), n, h, w, c, ptr(out), stream_ptr()), 'unpool2')
     return out
 
 

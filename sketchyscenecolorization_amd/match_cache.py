@@ -81,7 +81,7 @@ class MatchSceneCache(object):
                 raise RuntimeError('the matcher has no weights: the feature cache is built after they are loaded')
             if features.cfg.size != S:
                 raise ValueError('the model reads scenes of %d, the cache holds %d' % (features.cfg.size, S))
-            channels = features.cfg.filters[4]
+            channels = features.cfg.feat_channels
         self.scene_bytes, self.feature_bytes = cache_bytes(n, S, channels)
         self.nbytes = self.scene_bytes + self.feature_bytes
         if self.device.type == 'cuda':

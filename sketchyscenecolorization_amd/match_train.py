@@ -333,7 +333,7 @@ class MatchTrainer(object):
         hip.join_wgrad()
         hip.call('ssc_group_rowsum', dvp, c.v_emb, 1, R, c.v_emb, g['vproj/b'], 0)
         if dfeat is not None:       # d feat = dvp . DW^T
-            hip.matmul_nt(dvp, d['vproj/w'].view(c.filters[4], c.v_emb), dfeat.view(R, c.filters[4]))
+            hip.matmul_nt(dvp, d['vproj/w'].view(c.feat_channels, c.v_emb), dfeat.view(R, c.feat_channels))
 
     # ------------------------------------------------------------------ loss, optimiser
     def loss_and_grad(self, pred, sketch_d, labels_d, lut_d, slot=0):
@@ -390,7 +390,7 @@ class MatchTrainer(object):
             sketch_d, labels_d = self._resident(scene['sketch_d'], (c.size, c.size, 3), torch.uint8, 'sketch_d'), \
                 self._resident(scene['labels_d'], (c.size, c.size), torch.uint8, 'labels_d')
             if 'feat_d' in scene:       # the frozen backbone's output is given: neither the preprocessing nor the backbone runs
-                feat = self._resident(scene['feat_d'], (1, c.feat, c.feat, c.filters[4]), torch.float32, 'feat_d')
+                feat = self._resident(scene['feat_d'], (1, c.feat, c.feat, c.feat_channels), torch.float32, 'feat_d')
             else:
                 feat = self._features(sketch_d)
         else:
@@ -459,16 +459,21 @@ class MatchTrainer(object):
         self.step_count = int(step)
 
 
-def snapshot_prefix(snapshot_root, iteration):
-    return os.path.join(snapshot_root, '%s_iter_%d.tfmodel' % (MODEL_NAME, iteration))
+def model_name(backbone='deeplab'):
+    """The reference's weights_name + '_' + model_name: deeplab_RMI, segnet_RMI."""
+    return MODEL_NAME if backbone == 'deeplab' else '%s_RMI' % backbone
+
+
+def snapshot_prefix(snapshot_root, iteration, backbone='deeplab'):
+    return os.path.join(snapshot_root, '%s_iter_%d.tfmodel' % (model_name(backbone), iteration))
 
 
 def write_snapshot(trainer, snapshot_root, iteration, cursor):
-    """<snapshot_root>/deeplab_RMI_iter_<n>.tfmodel.{index, data-00000-of-00001}, the ``checkpoint`` file that names it and
-    <prefix>.train_state.json with the cursor, the shuffled order and the generator's state.  -> the prefix."""
+    """<snapshot_root>/<deeplab|segnet>_RMI_iter_<n>.tfmodel.{index, data-00000-of-00001}, the ``checkpoint`` file that names it
+    and <prefix>.train_state.json with the cursor, the shuffled order and the generator's state.  -> the prefix."""
     from . import tf_checkpoint
     os.makedirs(snapshot_root, exist_ok=True)
-    prefix = snapshot_prefix(snapshot_root, iteration)
+    prefix = snapshot_prefix(snapshot_root, iteration, trainer.cfg.backbone)
     tf_checkpoint.write_checkpoint(prefix, trainer.snapshot_tensors())
     with open(prefix + '.train_state.json', 'w') as f:
         json.dump(dict(cursor.state(), iteration=int(iteration)), f)

@@ -21,8 +21,12 @@ evaluation on a split (match_eval.py).
 ``head``, ``unit``, ``backbone`` and ``features`` are also the forward pass of training: with ``keep`` they leave what a backward
 pass reads in buffers of its own (match_train.py, match_backbone_train.py; DESIGN.md sections 8.8 and 8.10).
 
-Not here: the backward pass and the optimiser (match_train.py), the other backbones, fusion_type 'RecurAttn',
-post_processing_mask_with_segmentation."""
+MatchConfig(backbone='segnet'): the SegNet backbone of segnet_model.py (is_intermediate) in place of the DeepLab-ResNet -- 18 3x3
+convs, each behind the batch-statistics norm of the one image, five 2x2 pools that remember where each maximum was
+(ssc_max_pool2_argmax) and two unpools that put values back there (ssc_unpool2); ``MatchModel.segnet``, DESIGN.md section 8.12.
+
+Not here: the backward pass and the optimiser (match_train.py), the backbones fcn_8s and deeplab_v3plus,
+SegNet's backward, fusion_type 'RecurAttn', post_processing_mask_with_segmentation."""
 import os
 import re
 
@@ -36,6 +40,11 @@ NORM_PARTS = ('beta', 'gamma', 'factor', 'mean', 'variance')
 ATTN_MAX_LEN = 64           # hip.ATTN_MAX_T: the words the attention kernels hold
 HEAD = 'text_sketchyscene/'          # the scope of the fusion head's variables
 ATTN_VARIABLES = (HEAD + 'attn_fc/DW', HEAD + 'attn_fc/biases')
+# backbone -> (its released widths); the scope of its variables in a checkpoint
+BACKBONES = {'deeplab': (64, 256, 512, 1024, 2048), 'segnet': (64, 128, 256, 512, 512)}
+BACKBONE_SCOPE = {'deeplab': 'ResNet/', 'segnet': 'SegNet/'}
+# tf.contrib.layers.batch_norm with its defaults (segnet_model.py:133): no gamma; the moving moments exist and are never read
+SEGNET_NORM_PARTS = ('beta', 'moving_mean', 'moving_variance')
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -150,7 +159,7 @@ def unpack_head(config, dev):
     c, h = config, HEAD
     cw, cm = pad32(c.w_rnn), pad32(c.m_rnn)
     d = {k: np.asarray(v, dtype=np.float32) for k, v in dev.items()}
-    out = {h + 'visual_feat_projection/DW': d['vproj/w'].reshape(1, 1, c.filters[4], c.v_emb),
+    out = {h + 'visual_feat_projection/DW': d['vproj/w'].reshape(1, 1, c.feat_channels, c.v_emb),
            h + 'visual_feat_projection/biases': d['vproj/b'].reshape(c.v_emb),
            h + 'embedding': d['embedding'].reshape(c.vocab_size, c.w_emb)}
     out[h + 'wLSTM/lstm_cell/kernel'] = np.concatenate(
@@ -168,21 +177,31 @@ def unpack_head(config, dev):
 
 
 class MatchConfig(object):
-    """The sizes of the matcher.  The defaults are the released model; the tests run small ones through the same code."""
+    """The sizes of the matcher.  The defaults are the released model; the tests run small ones through the same code.
+    backbone: 'deeplab' (units and filters: the bottleneck groups of the DeepLab-ResNet) or 'segnet' (filters: the widths of
+    enc_1 .. enc_5 of segnet_model.py, units is not read); filters None: the backbone's released widths."""
 
-    def __init__(self, size=768, units=(3, 4, 23, 3), filters=(64, 256, 512, 1024, 2048), v_emb=1000, w_emb=1000, w_rnn=1000,
-                 m_rnn=500, vocab_size=76, max_len=15, use_attn=False):
+    def __init__(self, size=768, units=(3, 4, 23, 3), filters=None, v_emb=1000, w_emb=1000, w_rnn=1000,
+                 m_rnn=500, vocab_size=76, max_len=15, use_attn=False, backbone='deeplab'):
         if use_attn not in (False, True, 0, 1):
             raise ValueError('use_attn %r: False or True' % (use_attn,))
-        self.use_attn = bool(use_attn)
+        if backbone not in BACKBONES:
+            raise ValueError("backbone %r: %s; the other backbones are not built" % (backbone, ' or '.join(map(repr, BACKBONES))))
+        self.use_attn, self.backbone = bool(use_attn), backbone
+        if filters is None:
+            filters = BACKBONES[backbone]
         self.size, self.units, self.filters = int(size), tuple(int(u) for u in units), tuple(int(f) for f in filters)
         self.v_emb, self.w_emb, self.w_rnn, self.m_rnn = int(v_emb), int(w_emb), int(w_rnn), int(m_rnn)
         self.vocab_size, self.max_len = int(vocab_size), int(max_len)
         if self.size < 32 or self.size % 32:
-            raise ValueError('size %d: the matcher needs a multiple of 32 (its 1/8 map is cut into 4 x 4 sub-images)' % self.size)
+            raise ValueError('size %d: the matcher needs a multiple of 32 (%s)' % (self.size, 'SegNet pools 2 x 2 five times'
+                             if backbone == 'segnet' else 'its 1/8 map is cut into 4 x 4 sub-images'))
         if len(self.units) != 4 or min(self.units) < 1 or len(self.filters) != 5:
             raise ValueError('units %r / filters %r: four groups of at least one unit, five widths' % (self.units, self.filters))
-        for name, c in [('filters[0]', self.filters[0])] + [('filters[%d] / 4' % k, f // 4) for k, f in enumerate(self.filters) if k] + \
+        # a bottleneck's inner width is a quarter of its outer one; SegNet's convs have the widths themselves
+        widths = [('filters[%d]' % k, f) for k, f in enumerate(self.filters)] if backbone == 'segnet' else \
+            [('filters[0]', self.filters[0])] + [('filters[%d] / 4' % k, f // 4) for k, f in enumerate(self.filters) if k]
+        for name, c in widths + \
                 [('v_emb', self.v_emb), ('w_emb', self.w_emb), ('w_rnn', self.w_rnn), ('m_rnn', self.m_rnn)]:
             if c < 4 or c % 4:
                 raise ValueError('%s = %d: every channel count must be a multiple of 4' % (name, c))
@@ -205,9 +224,63 @@ class MatchConfig(object):
                 out.append(('ResNet/group_%d_%d' % (g + 2, i), f[g] if i == 0 else f[g + 1], f[g + 1], stride if i == 0 else 1, rate))
         return out
 
-    def variable_shapes(self):
-        """{checkpoint name: shape} of everything inference reads."""
-        f, s = self.filters, {}
+    @property
+    def feat_channels(self):
+        """The channels of the visual feature map: the last group's of the DeepLab-ResNet, dec_4's (= enc_4's) of SegNet."""
+        return self.filters[3] if self.backbone == 'segnet' else self.filters[4]
+
+    def segnet_stages(self):
+        """[(stage, [(cin, cout)] of its 3x3 convs)] of segnet_model.py:56-95 up to intermediate_feat.  An encoder stage ends in
+        its 2x2 pool; a decoder stage begins with the unpool by the codes of the encoder stage of its number, whose width its
+        input therefore has: dec_5 ends at enc_4's width."""
+        f1, f2, f3, f4, f5 = self.filters
+        return [('enc_1', [(3, f1), (f1, f1)]), ('enc_2', [(f1, f2), (f2, f2)]), ('enc_3', [(f2, f3), (f3, f3), (f3, f3)]),
+                ('enc_4', [(f3, f4), (f4, f4), (f4, f4)]), ('enc_5', [(f4, f5), (f5, f5), (f5, f5)]),
+                ('dec_5', [(f5, f5), (f5, f5), (f5, f4)]), ('dec_4', [(f4, f4), (f4, f4)])]
+
+    def segnet_plan(self):
+        """The device pass of the SegNet backbone as [(op, stage, k, channels in, channels out, side in, side out)], op one of
+        'conv' (k: the conv's number from 0), 'pool', 'act' (a decoder stage's last norm and relu materialised) and 'unpool'."""
+        plan, h = [], self.size
+        for stage, convs in self.segnet_stages():
+            if stage.startswith('dec'):
+                plan.append(('unpool', stage, None, convs[0][0], convs[0][0], h, 2 * h))
+                h *= 2
+            for k, (cin, cout) in enumerate(convs):
+                plan.append(('conv', stage, k, cin, cout, h, h))
+            if stage.startswith('enc'):
+                plan.append(('pool', stage, None, cout, cout, h, h // 2))
+                h //= 2
+            else:
+                plan.append(('act', stage, None, cout, cout, h, h))
+        return plan
+
+    def segnet_scratch_floats(self):
+        """The floats of the two scratch buffers the SegNet pass alternates between: every step reads what the step before it
+        wrote and writes into the other buffer, so each holds the largest tensor that falls to it; the last step's output (the
+        feature map) has a buffer of its own."""
+        need = [0, 0]
+        for n, (_op, _stage, _k, _cin, cout, _h, oh) in enumerate(self.segnet_plan()[:-1]):
+            need[n & 1] = max(need[n & 1], oh * oh * cout)
+        return need
+
+    def segnet_scratch_bytes(self):
+        """What the SegNet pass allocates beyond the weights: the two scratch buffers, the input, the codes of the five pools
+        (one byte per pooled element) and the feature map."""
+        codes = sum(oh * oh * cout for op, _s, _k, _cin, cout, _h, oh in self.segnet_plan() if op == 'pool')
+        return 4 * (sum(self.segnet_scratch_floats()) + self.size * self.size * 4 + self.feat * self.feat * self.feat_channels) + codes
+
+    def _segnet_variable_shapes(self, s):
+        for stage, convs in self.segnet_stages():
+            for k, (cin, cout) in enumerate(convs):
+                s['SegNet/%s/conv%d/DW' % (stage, k + 1)] = (3, 3, cin, cout)
+                s['SegNet/%s/conv%d/biases' % (stage, k + 1)] = (cout,)
+            for k, (_cin, cout) in enumerate(convs):        # the norms of a stage are numbered in call order
+                for p in SEGNET_NORM_PARTS:
+                    s['%s/%s' % (segnet_norm_scope(stage, k), p)] = (cout,)
+
+    def _deeplab_variable_shapes(self, s):
+        f = self.filters
 
         def norm(scope, c):
             for p in NORM_PARTS:
@@ -220,8 +293,13 @@ class MatchConfig(object):
                     ((('block_add', (1, 1, cin, cout)),) if cin != cout else ()):
                 s['%s/%s/conv/DW' % (scope, blk)] = shape
                 norm('%s/%s/bn' % (scope, blk), shape[3])
+
+    def variable_shapes(self):
+        """{checkpoint name: shape} of everything inference reads (and, of SegNet, the moving moments that ride along unread)."""
+        s = {}
+        (self._segnet_variable_shapes if self.backbone == 'segnet' else self._deeplab_variable_shapes)(s)
         h = HEAD
-        s[h + 'visual_feat_projection/DW'] = (1, 1, f[4], self.v_emb)
+        s[h + 'visual_feat_projection/DW'] = (1, 1, self.feat_channels, self.v_emb)
         s[h + 'visual_feat_projection/biases'] = (self.v_emb,)
         s[h + 'embedding'] = (self.vocab_size, self.w_emb)
         s[h + 'wLSTM/lstm_cell/kernel'] = (self.w_emb + self.w_rnn, 4 * self.w_rnn)
@@ -234,6 +312,33 @@ class MatchConfig(object):
             s[h + 'attn_fc/DW'] = (self.w_rnn, 1)
             s[h + 'attn_fc/biases'] = (1,)
         return s
+
+
+def segnet_norm_scope(stage, k):
+    """The scope of the norm behind conv k (from 0) of a SegNet stage: tf.contrib.layers.batch_norm's default scope, numbered
+    within the stage in call order -- BatchNorm, BatchNorm_1, BatchNorm_2."""
+    return 'SegNet/%s/BatchNorm%s' % (stage, '' if k == 0 else '_%d' % k)
+
+
+def check_backbone_variables(names, backbone):
+    """names: the variable names of a checkpoint (any container).  ValueError when it holds the variables of the other backbone:
+    a head trained on one backbone's feature map gives nothing meaningful on the other's.  Names the flag and a variable."""
+    for other, scope in BACKBONE_SCOPE.items():
+        if other != backbone:
+            found = sorted(n for n in names if n.startswith(scope))
+            if found:
+                raise ValueError("the checkpoint holds %s: it belongs to the %s backbone (--weights %s), not to --weights %s"
+                                 % (found[0], other, other, backbone))
+
+
+def check_segnet_scratch(config, free):
+    """The bytes MatchModel.segnet allocates at its first pass (MatchConfig.segnet_scratch_bytes) against ``free``, the bytes free
+    on the device: -> the bytes; ValueError when they are more than half of what is free."""
+    need = config.segnet_scratch_bytes()
+    if need > int(free) // 2:
+        raise ValueError('the SegNet backbone needs %d bytes of scratch memory at size %d, more than half of the %d bytes free on '
+                         'the device' % (need, config.size, int(free)))
+    return need
 
 
 def check_attention_variables(names, use_attn):
@@ -275,15 +380,15 @@ def random_variables(config, seed=0):
     for name, shape in config.variable_shapes().items():
         leaf = name.rsplit('/', 1)[1]
         n = int(np.prod(shape))
-        if leaf == 'DW' and name.startswith('ResNet/'):
+        if leaf == 'DW' and name.startswith(('ResNet/', 'SegNet/')):
             v = rng.randn(*shape) * np.sqrt(2.0 / (shape[0] * shape[1] * shape[3]))
         elif leaf in ('DW', 'kernel', 'embedding'):
             v = draw_head_weight(rng, leaf, shape)
-        elif leaf in ('gamma', 'variance'):
+        elif leaf in ('gamma', 'variance', 'moving_variance'):
             v = rng.uniform(0.5, 1.5, shape)
         elif leaf == 'factor':
             v = rng.uniform(0.8, 1.25, shape)
-        elif leaf in ('beta', 'mean', 'bias', 'biases'):
+        elif leaf in ('beta', 'mean', 'bias', 'biases', 'moving_mean'):
             v = rng.randn(n).reshape(shape) * 0.1
         else:
             raise AssertionError(name)
@@ -340,8 +445,17 @@ class MatchModel(object):
                     s[name] = shape
                 elif leaf == 'gamma':
                     s[scope] = (2 * shape[0],)
+            elif name.startswith('SegNet/'):
+                # the filters (the first one's 3 input channels padded to 4) and the betas; the biases cancel in the norm and the
+                # moving moments are never read
+                if leaf == 'DW':
+                    s[name] = (3, 3, max(shape[2], 4), shape[3])
+                elif leaf == 'beta':
+                    s[name] = shape
+        if c.backbone == 'segnet':
+            s['SegNet/ones'] = (max(c.filters),)      # the scale of a norm without gamma
         cw, cm = self.cw, self.cm
-        s['vproj/w'], s['vproj/b'] = (1, 1, c.filters[4], c.v_emb), (c.v_emb,)
+        s['vproj/w'], s['vproj/b'] = (1, 1, c.feat_channels, c.v_emb), (c.v_emb,)
         s['embedding'] = (c.vocab_size, c.w_emb)
         s['w/Kx'], s['w/Kh'], s['w/b'] = (c.w_emb, 4 * cw), (cw, 4 * cw), (4 * cw,)
         s['m/Kv'], s['m/Kw'], s['m/Kl'], s['m/Ks'] = (c.v_emb, 4 * cm), (c.w_emb, 4 * cm), (cw, 4 * cm), (8, 4 * cm)
@@ -361,12 +475,17 @@ class MatchModel(object):
         import torch
         c, host = self.cfg, {}
         check_attention_variables(variables, c.use_attn)
+        check_backbone_variables(variables, c.backbone)
         for name, shape in c.variable_shapes().items():
             src = name
             if src not in variables:
                 for new, old in OLD_CELL_NAMES.items():
                     if name.endswith(new) and name[:-len(new)] + old in variables:
                         src = name[:-len(new)] + old
+            if src not in variables and name.startswith('SegNet/') and name.rsplit('/', 1)[1] in SEGNET_NORM_PARTS[1:]:
+                # a checkpoint without the moving moments: their initial values; nothing reads them, snapshots carry them
+                host[name] = (np.ones if name.endswith('variance') else np.zeros)(shape, dtype=np.float32)
+                continue
             if src not in variables:
                 raise ValueError('the checkpoint has no variable %s' % name)
             v = np.asarray(variables[src])
@@ -381,6 +500,13 @@ class MatchModel(object):
                     dev[name] = v
                 elif leaf == 'gamma':
                     dev[scope] = fold_norm(*[host[scope + '/' + p] for p in NORM_PARTS])
+            elif name.startswith('SegNet/'):
+                if leaf == 'DW':
+                    dev[name] = np.pad(v, ((0, 0), (0, 0), (0, max(4 - v.shape[2], 0)), (0, 0)))
+                elif leaf == 'beta':
+                    dev[name] = v
+        if c.backbone == 'segnet':
+            dev['SegNet/ones'] = np.ones(max(c.filters), np.float32)
         dev.update(pack_head(c, host))
         dev['spatial'] = spatial_features(c.feat, c.feat).reshape(-1, 8)
         assert set(dev) == set(self.d), set(dev) ^ set(self.d)
@@ -473,6 +599,10 @@ class MatchModel(object):
         from . import hip
         from .hip import View
         c, d = self.cfg, self.d
+        if c.backbone == 'segnet':
+            if keep is not None:
+                raise ValueError('the SegNet backward is not built: its backbone is run frozen, nothing is kept of its pass')
+            return self.segnet(x4)
         s = c.size
         own = '' if keep is None else 'bt/'
         r0 = self._buf(own + 'conv1', (1, s // 2, s // 2, c.filters[0]))
@@ -491,6 +621,43 @@ class MatchModel(object):
         if keep is not None:
             keep.update(units=units, x4=x4, r0=r0)
         return self.ungroup(x, cur, 'b2s' if keep is None else 'bt/b2s{}')     # group_last's relu: the last unit's output is one already
+
+    def segnet(self, x4):
+        """The SegNet backbone (segnet_model.py:56-99, is_intermediate): x4 float [1,S,S,4] -> the visual feature
+        [1,S/8,S/8,filters[3]] in the buffer sn/feat.  Every conv is followed by the batch-statistics norm of its one image
+        (no gamma, eps 0.001) and a relu: hip.conv_forward folds the statistics to [a | b] behind the conv, and the next conv or
+        the pool applies them and the relu as it loads.  The conv's bias is left out: the norm takes it off again with the mean.
+        The steps alternate between two scratch buffers (MatchConfig.segnet_scratch_floats); the pools' codes have buffers of
+        their own (sn/code/<stage>), enc_5's and enc_4's are read by the unpools."""
+        import torch
+        from . import hip
+        from .hip import ACT_NONE, ACT_RELU, View
+        c, d = self.cfg, self.d
+        plan = c.segnet_plan()
+        flat = [self._buf('sn/scratch%d' % k, (n,)) for k, n in enumerate(c.segnet_scratch_floats())]
+        x, ab, codes = x4, None, {}
+        for n, (op, stage, k, cin, cout, h, oh) in enumerate(plan):
+            last = n == len(plan) - 1
+            out = self._buf('sn/feat', (1, oh, oh, cout)) if last else flat[n & 1][:oh * oh * cout].view(1, oh, oh, cout)
+            assert out.data_ptr() != x.data_ptr()
+            if op == 'conv':
+                norm = segnet_norm_scope(stage, k)
+                ab_new, stats = self._buf('sn/ab/' + norm, (2 * cout,)), self._buf('sn/stats/' + norm, (2 * cout,))
+                hip.conv_forward(View(x, None, ab, ACT_RELU if ab is not None else ACT_NONE),
+                                 d['SegNet/%s/conv%d/DW' % (stage, k + 1)], 1, 0, out, same=True,
+                                 bn=(d['SegNet/ones'][:cout], d[norm + '/beta'], ab_new, stats, NORM_EPS))
+                ab = ab_new
+            elif op == 'pool':
+                codes[stage] = self._buf('sn/code/' + stage, (1, oh, oh, cout), torch.uint8)
+                hip.max_pool2_argmax(x, ab, out=out, code=codes[stage])
+                ab = None
+            elif op == 'act':       # a decoder stage's last norm and relu, materialised for the unpool and for the head
+                hip.call('ssc_affine_act', x, cout, ab, cout, ACT_RELU, out, cout, oh * oh, cout)
+                ab = None
+            else:
+                hip.unpool2(x, codes['enc_' + stage[4:]], out=out)
+            x = out
+        return x
 
     # ------------------------------------------------------------------ head
     def _lstm_planes(self, tag, rows, C):
