@@ -97,40 +97,63 @@ TRAIN_FLAGS = [
 SCENE_CACHE_MODES = ('off', 'device', 'features')
 
 
-def checked_use_attn(args):
-    """--use_attn: 0 or 1, anything else is a ValueError."""
+def checked_model(args):
+    """The flags that every mode reads -- --use_attn, --weights, --text_len, --scene_size, --vocab_size and --vocab_file: ->
+    (config, vocab).  ValueError for a bad one."""
+    from sketchyscenecolorization_amd import match_backbones, matching
     if args.use_attn not in (0, 1):
         raise ValueError('--use_attn %d: 0 (the last state feeds the projection) or 1 (the attention-weighted sum of every '
                          "word's state)" % args.use_attn)
-    return bool(args.use_attn)
-
-
-def checked_weights(args):
-    """--weights: -> 'deeplab' or 'segnet', anything else is a ValueError."""
-    from sketchyscenecolorization_amd import matching
-    if args.weights not in matching.BACKBONES:
+    if args.weights not in match_backbones.BACKBONES:
         raise ValueError('--weights %r: only %s (the other backbones are not built)'
-                         % (args.weights, ' or '.join(repr(b) for b in matching.BACKBONES)))
-    return args.weights
+                         % (args.weights, ' or '.join(repr(b) for b in match_backbones.BACKBONES)))
+    if args.text_len < 1:
+        raise ValueError('--text_len %d: at least one word' % args.text_len)
+    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len,
+                                  use_attn=bool(args.use_attn), backbone=args.weights)
+    if not os.path.isfile(args.vocab_file):
+        raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
+    vocab = matching.load_vocab(args.vocab_file)
+    if len(vocab) != args.vocab_size or matching.UNK not in vocab or matching.PAD not in vocab:
+        raise ValueError('--vocab_file %r holds %d words, --vocab_size is %d; <unk> and <pad> must be among them'
+                         % (args.vocab_file, len(vocab), args.vocab_size))
+    return config, vocab
 
 
-def checked_snapshot_attention(prefix, use_attn, backbone='deeplab'):
-    """The snapshot's variable names against --use_attn and --weights, read from its index alone: MatchModel.load_dict's
-    refusals, before anything is allocated."""
+def checked_snapshot_variables(path, config):
+    """A snapshot (matching.resolve_snapshot) -> its prefix.  Its variable names are held against the configuration's backbone
+    (--weights) and --use_attn, read from its index alone: MatchModel.load_dict's refusals, before anything is allocated."""
     from sketchyscenecolorization_amd import matching, tf_checkpoint
+    prefix = matching.resolve_snapshot(path)
     names = {name for name, _shape, _dtype in tf_checkpoint.list_variables(prefix)}
-    matching.check_backbone_variables(names, backbone)
-    matching.check_attention_variables(names, use_attn)
+    config.net.check_variables(names)
+    matching.check_attention_variables(names, config.use_attn)
+    return prefix
+
+
+def checked_scenes(scenes, data_base_dir, split, more_paths=lambda image_id: (), no_category=None):
+    """A split's scenes (match_eval.read_captions): ValueError for a scene without one of its ground-truth files or of
+    ``more_paths(image_id)``, for a caption without a word and -- no_category: that message, with %r for the caption -- for one
+    that names no category."""
+    from sketchyscenecolorization_amd import match_eval, matching
+    for image_id, pairs in scenes:
+        for path in match_eval.ground_truth_paths(data_base_dir, split, image_id) + tuple(more_paths(image_id)):
+            if not os.path.isfile(path):
+                raise ValueError('scene %s: %s: no such file' % (image_id, path))
+        for caption, _idx in pairs:
+            if not matching.sentence_tokens(caption):
+                raise ValueError('scene %s: the caption %r holds no word' % (image_id, caption))
+            if no_category is not None and match_eval.caption_category(caption)[0] is None:
+                raise ValueError('scene %s: %s' % (image_id, no_category % (caption,)))
 
 
 def reserved_model(cfg):
-    """The MatchModel of a configuration.  With the SegNet backbone the scratch memory of its pass is added up first, printed, and
-    refused as a ValueError when it is more than half of what is free on the device."""
+    """The MatchModel of a configuration.  What its backbone reserves as scratch memory at its first pass is added up first,
+    refused as a ValueError when it is more than half of what is free on the device, and printed when there is any."""
     from sketchyscenecolorization_amd import matching
-    if cfg.backbone == 'segnet':
+    if cfg.net.scratch_bytes():
         import torch
-        print('segnet backbone: %d bytes of scratch memory on the device'
-              % matching.check_segnet_scratch(cfg, torch.cuda.mem_get_info()[0]))
+        print('%s backbone: %d bytes of scratch memory on the device' % (cfg.backbone, cfg.net.check_scratch(torch.cuda.mem_get_info()[0])))
     return matching.MatchModel(cfg)
 
 
@@ -162,21 +185,10 @@ def checked_arguments(args):
         raise ValueError('--snapshot <directory or checkpoint prefix> is needed: the matcher has no weights of its own')
     if args.image_id is None or args.image_id == '' or args.instruction == '':
         raise ValueError("--image_id <id> and --instruction '<text>' are needed")
-    use_attn, weights = checked_use_attn(args), checked_weights(args)
-    if args.text_len < 1:
-        raise ValueError('--text_len %d: at least one word' % args.text_len)
-    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn,
-                                  backbone=weights)
     if not matching.sentence_tokens(args.instruction):
         raise ValueError('--instruction %r holds no word' % args.instruction)
-    if not os.path.isfile(args.vocab_file):
-        raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
-    vocab = matching.load_vocab(args.vocab_file)
-    if len(vocab) != args.vocab_size or matching.UNK not in vocab or matching.PAD not in vocab:
-        raise ValueError('--vocab_file %r holds %d words, --vocab_size is %d; <unk> and <pad> must be among them'
-                         % (args.vocab_file, len(vocab), args.vocab_size))
-    prefix = matching.resolve_snapshot(args.snapshot)
-    checked_snapshot_attention(prefix, use_attn, weights)
+    config, vocab = checked_model(args)
+    prefix = checked_snapshot_variables(args.snapshot, config)
     for sub, name in (('sketches', args.image_id + '.png'), ('inner_masks', args.image_id + '.mat'),
                       ('seg_data', args.image_id + '_datas.npz')):
         if not os.path.isfile(os.path.join(args.scene_dir, sub, name)):
@@ -194,38 +206,20 @@ def checked_eval_arguments(args):
         raise ValueError("--dataset %r: 'val' or 'test'" % args.dataset)
     if args.mask_ap not in (0, 1):
         raise ValueError('--mask_ap %d: 0 or 1' % args.mask_ap)
-    use_attn, weights = checked_use_attn(args), checked_weights(args)
     if args.max_scenes < 0:
         raise ValueError('--max_scenes %d: a count, 0 for every scene' % args.max_scenes)
-    if args.text_len < 1:
-        raise ValueError('--text_len %d: at least one word' % args.text_len)
     if args.eval_result_root == '':
         raise ValueError('--eval_result_root is empty')
-    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn,
-                                  backbone=weights)
-    if not os.path.isfile(args.vocab_file):
-        raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
-    vocab = matching.load_vocab(args.vocab_file)
-    if len(vocab) != args.vocab_size or matching.UNK not in vocab or matching.PAD not in vocab:
-        raise ValueError('--vocab_file %r holds %d words, --vocab_size is %d; <unk> and <pad> must be among them'
-                         % (args.vocab_file, len(vocab), args.vocab_size))
-    prefix = matching.resolve_snapshot(args.snapshot)
-    checked_snapshot_attention(prefix, use_attn, weights)
+    config, vocab = checked_model(args)
+    prefix = checked_snapshot_variables(args.snapshot, config)
     scenes = match_eval.read_captions(args.captions_base_dir, args.dataset)
     if args.max_scenes:
         scenes = scenes[:args.max_scenes]
     if not scenes:
         raise ValueError('--captions_base_dir %r: no scene in the caption file of %r' % (args.captions_base_dir, args.dataset))
-    for image_id, pairs in scenes:
-        for path in match_eval.ground_truth_paths(args.data_base_dir, args.dataset, image_id) + \
-                (match_eval.seg_data_path(args.seg_data_dir, args.dataset, image_id),):
-            if not os.path.isfile(path):
-                raise ValueError('scene %s: %s: no such file' % (image_id, path))
-        for caption, _idx in pairs:
-            if not matching.sentence_tokens(caption):
-                raise ValueError('scene %s: the caption %r holds no word' % (image_id, caption))
-            if args.augment_seed is not None and match_eval.caption_category(caption)[0] is None:
-                raise ValueError('scene %s: --augment_seed: the caption %r names no category' % (image_id, caption))
+    checked_scenes(scenes, args.data_base_dir, args.dataset,
+                   more_paths=lambda image_id: (match_eval.seg_data_path(args.seg_data_dir, args.dataset, image_id),),
+                   no_category=None if args.augment_seed is None else '--augment_seed: the caption %r names no category')
     return config, prefix, vocab, scenes
 
 
@@ -236,7 +230,7 @@ def evaluate(args, config=None, predicts_out=None):
         cfg = agreed_config(config, cfg)
     import random
     import numpy as np
-    from sketchyscenecolorization_amd import match_eval, match_train, matching
+    from sketchyscenecolorization_amd import match_eval
     model = reserved_model(cfg)
     model.load_tf_checkpoint(prefix)
     rng = None if args.augment_seed is None else random.Random(args.augment_seed)
@@ -247,7 +241,7 @@ def evaluate(args, config=None, predicts_out=None):
     block = totals.block(prefix)
     print(block)
     os.makedirs(args.eval_result_root, exist_ok=True)
-    with open(os.path.join(args.eval_result_root, '%s_%s_result.txt' % (match_train.model_name(cfg.backbone), args.dataset)), 'a') as f:
+    with open(os.path.join(args.eval_result_root, '%s_%s_result.txt' % (cfg.net.model_name, args.dataset)), 'a') as f:
         f.write(block)
     record = dict(totals.record(), split=args.dataset, snapshot=prefix, scenes=len(scenes), augment_seed=args.augment_seed,
                   per_caption=records)
@@ -279,67 +273,47 @@ def checked_train_arguments(args):
                             ('fusion_type', 'RMI', "'RecurAttn' is not built; the attention that is built is --use_attn 1"), ('summary', 0, 'event summaries are not written')):
         if getattr(args, name) != want:
             raise ValueError('--%s %r: only %r (%s)' % (name, getattr(args, name), want, why))
-    weights = checked_weights(args)
     if args.max_iteration < 1 or args.save_model_freq < 1 or args.log_freq < 1:
         raise ValueError('--max_iteration %d, --save_model_freq %d, --log_freq %d: each at least 1'
                          % (args.max_iteration, args.save_model_freq, args.log_freq))
     if not (args.start_lr > 0 and args.end_lr >= 0 and args.lr_decay_step >= 1 and args.weight_decay >= 0):
         raise ValueError('--start_lr %r, --end_lr %r, --lr_decay_step %d, --weight_decay %r' % (args.start_lr, args.end_lr,
                                                                                              args.lr_decay_step, args.weight_decay))
-    if args.text_len < 1:
-        raise ValueError('--text_len %d: at least one word' % args.text_len)
     if args.snapshot_root == '' or args.log_root == '':
         raise ValueError('--snapshot_root or --log_root is empty')
     if args.scene_cache not in SCENE_CACHE_MODES:
         raise ValueError("--scene_cache %r: 'off', 'device' or 'features'" % args.scene_cache)
     if args.train_backbone not in (0, 1):
         raise ValueError('--train_backbone %d: 0 (the fusion head alone) or 1 (and the backbone)' % args.train_backbone)
-    if args.train_backbone and weights == 'segnet':
-        raise ValueError('--train_backbone 1 --weights segnet: the SegNet backward is not built; its backbone is run frozen '
-                         '(--train_backbone 0)')
+    config, vocab = checked_model(args)
+    if args.train_backbone and not config.net.trainable:
+        raise ValueError('--train_backbone 1 --weights %s: the %s backward is not built; its backbone is run frozen '
+                         '(--train_backbone 0)' % (config.backbone, config.net.title))
     if args.train_backbone and args.scene_cache == 'features':
         raise ValueError('--train_backbone 1 --scene_cache features: cached features are those of the initial backbone; '
                          'use --scene_cache device')
     if args.val_freq < 0 or args.val_scenes < 0:
         raise ValueError('--val_freq %d, --val_scenes %d: counts, 0 for never and for every scene' % (args.val_freq, args.val_scenes))
-    use_attn = checked_use_attn(args)
-    config = matching.MatchConfig(size=args.scene_size, vocab_size=args.vocab_size, max_len=args.text_len, use_attn=use_attn,
-                                  backbone=weights)
-    if not os.path.isfile(args.vocab_file):
-        raise ValueError('--vocab_file %r: no such file' % args.vocab_file)
-    vocab = matching.load_vocab(args.vocab_file)
-    if len(vocab) != args.vocab_size or matching.UNK not in vocab or matching.PAD not in vocab:
-        raise ValueError('--vocab_file %r holds %d words, --vocab_size is %d; <unk> and <pad> must be among them'
-                         % (args.vocab_file, len(vocab), args.vocab_size))
     if vocab[matching.PAD] != 0:
         raise ValueError('--vocab_file %r: <pad> is word %d; training needs it as word 0 (the embedding gradient skips row 0)'
                          % (args.vocab_file, vocab[matching.PAD]))
     resume = backbone = None
     if os.path.exists(os.path.join(args.snapshot_root, 'checkpoint')):
-        resume = matching.resolve_snapshot(args.snapshot_root)
+        resume = checked_snapshot_variables(args.snapshot_root, config)     # a resume goes on with the head the snapshot was trained with
         match_train.snapshot_iteration(resume)
         if not os.path.isfile(resume + '.train_state.json'):
             raise ValueError('%s.train_state.json: no such file; the snapshot cannot be resumed from' % resume)
-        checked_snapshot_attention(resume, use_attn, weights)       # a resume goes on with the head the snapshot was trained with
     else:
         if args.backbone_snapshot == '':
             raise ValueError('--backbone_snapshot <directory or checkpoint prefix> is needed: a fresh run takes %s* from it'
-                             % matching.BACKBONE_SCOPE[weights])
+                             % config.net.scope)
         backbone = matching.resolve_snapshot(args.backbone_snapshot)
         # a checkpoint of the other backbone is refused from its index; one that lacks a variable, when it is loaded
-        matching.check_backbone_variables({name for name, _s, _d in tf_checkpoint.list_variables(backbone)}, weights)
+        config.net.check_variables({name for name, _s, _d in tf_checkpoint.list_variables(backbone)})
     scenes = match_eval.read_captions(args.captions_base_dir, 'train')
     if not scenes:
         raise ValueError('--captions_base_dir %r: no scene in the caption file of the train split' % args.captions_base_dir)
-    for image_id, pairs in scenes:
-        for path in match_eval.ground_truth_paths(args.data_base_dir, 'train', image_id):
-            if not os.path.isfile(path):
-                raise ValueError('scene %s: %s: no such file' % (image_id, path))
-        for caption, _idx in pairs:
-            if not matching.sentence_tokens(caption):
-                raise ValueError('scene %s: the caption %r holds no word' % (image_id, caption))
-            if match_eval.caption_category(caption)[0] is None:
-                raise ValueError('scene %s: the caption %r names no category to add an attribute to' % (image_id, caption))
+    checked_scenes(scenes, args.data_base_dir, 'train', no_category='the caption %r names no category to add an attribute to')
     validation_scenes(args)
     return config, vocab, match_train.training_tuples(scenes), resume, backbone
 
@@ -411,7 +385,7 @@ def train(args, config=None):
         print('loaded', resume)
     else:
         have = tf_checkpoint.read_checkpoint(backbone)
-        variables = {k: v for k, v in have.items() if k.startswith(matching.BACKBONE_SCOPE[cfg.backbone])}
+        variables = {k: v for k, v in have.items() if k.startswith(cfg.net.scope)}
         variables.update(match_train.init_head(cfg, args.seed))
         model.load_dict(variables)
         trainer = make_trainer()

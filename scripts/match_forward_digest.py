@@ -8,7 +8,13 @@ commit's tree and on this one,
     python scripts/match_forward_digest.py --tree /path/to/a/built/checkout --tag parent
 
 the lines must be equal: profiles/match_forward_once.txt keeps the parent's, tests/test_gpu_match_train.py holds this tree's
-against them (the two ``host`` lines, which need no device: tests/test_match_train.py).  Only what both trees have is used."""
+against them (the two ``host`` lines, which need no device: tests/test_match_train.py).  Only what both trees have is used.
+
+``segnet_digests`` (--segnet 1) is the same record for MatchConfig(backbone='segnet'): filters (8, 16, 32, 32, 32) at size 64 with
+both head widths and the attention off and on -- the initial variables, inference, the head trainer on the frozen backbone, its
+snapshot, a resumed step, the launch names -- and inference alone at size 96, where the last pool reaches an odd 3 x 3 map.
+profiles/match_backbones_once.txt keeps the parent's lines; tests/test_gpu_match_segnet.py and tests/test_match_segnet.py hold
+this tree's against them."""
 import argparse
 import hashlib
 import os
@@ -19,6 +25,8 @@ SMALL = dict(size=64, units=(1, 1, 1, 1), filters=(8, 16, 32, 64, 128))
 WIDTHS = {'narrow': dict(v_emb=24, w_emb=24, w_rnn=40, m_rnn=20), 'bf': dict(v_emb=128, w_emb=128, w_rnn=128, m_rnn=128)}
 CASES = [(w, a) for w in ('narrow', 'bf') for a in (0, 1)]
 BACKBONE_UNITS = (2, 1, 2, 2)
+SEGNET_FILTERS = (8, 16, 32, 32, 32)
+SEGNET_CASES = [(w, a, 64) for w, a in CASES] + [('narrow', 0, 96)]       # (widths, use_attn, size); 96: inference only
 
 
 def case_name(widths, use_attn):
@@ -109,16 +117,12 @@ def _train(out, tag, make_trainer, cfg, variables, scene, sentences, resident):
     model.close()
 
 
-def device_digests(widths, use_attn):
-    """-> [(what, sha256)] of one case, from the sketchyscenecolorization_amd that is importable now."""
+def _inference_and_head_trainer(out, tag, cfg, variables, train=True):
+    """Inference and the head trainer of one configuration into ``out``; -> (scene, the trainers' sentences)."""
     import numpy as np
     import torch
-    from sketchyscenecolorization_amd import match_backbone_train, match_train, matching
-    tag = case_name(widths, use_attn)
-    cfg = _config(widths, use_attn)
-    variables = matching.random_variables(cfg, 41)
+    from sketchyscenecolorization_amd import match_train, matching
     rng = np.random.RandomState(42)
-    out = []
     sk = np.full((cfg.size, cfg.size, 3), 255, np.uint8)
     sk[rng.rand(cfg.size, cfg.size) < 0.5] = 0
     labels = np.zeros((cfg.size, cfg.size), np.uint8)
@@ -131,7 +135,7 @@ def device_digests(widths, use_attn):
     # inference: the head after a longer sentence (stale rows behind L), the whole pass, the pass in two halves
     model = matching.MatchModel(cfg)
     model.load_dict(variables)
-    feat = torch.from_numpy(np.maximum(rng.randn(1, cfg.feat, cfg.feat, cfg.filters[4]), 0).astype(np.float32)).cuda()
+    feat = torch.from_numpy(np.maximum(rng.randn(1, cfg.feat, cfg.feat, cfg.feat_channels), 0).astype(np.float32)).cuda()
     with _Launches() as rec:
         for idx, L in sentences[:3]:
             out.append(('%s head L=%d pred' % (tag, L), _sha(model.head(feat, torch.from_numpy(idx.astype(np.int32)).cuda(), L))))
@@ -145,7 +149,18 @@ def device_digests(widths, use_attn):
     model.close()
     scene = {'sketch': sk, 'labels': labels}
     order = [sentences[3], sentences[1], sentences[0]]
-    _train(out, tag + ' head trainer', match_train.MatchTrainer, cfg, variables, scene, order, True)
+    if train:
+        _train(out, tag + ' head trainer', match_train.MatchTrainer, cfg, variables, scene, order, True)
+    return scene, order
+
+
+def device_digests(widths, use_attn):
+    """-> [(what, sha256)] of one case, from the sketchyscenecolorization_amd that is importable now."""
+    from sketchyscenecolorization_amd import match_backbone_train, matching
+    tag = case_name(widths, use_attn)
+    cfg = _config(widths, use_attn)
+    out = []
+    scene, order = _inference_and_head_trainer(out, tag, cfg, matching.random_variables(cfg, 41))
     deep = _config(widths, use_attn, units=BACKBONE_UNITS)
     _train(out, tag + ' backbone trainer', match_backbone_train.BackboneMatchTrainer, deep, matching.random_variables(deep, 41), scene,
            order, False)
@@ -154,6 +169,22 @@ def device_digests(widths, use_attn):
 
 def digests(widths, use_attn):
     return host_digests(widths, use_attn) + device_digests(widths, use_attn)
+
+
+def segnet_case_name(widths, use_attn, size):
+    return 'segnet %s attn=%d size=%d' % (widths, use_attn, size)
+
+
+def segnet_digests(widths, use_attn, size, host_only=False):
+    """-> [(what, sha256)] of one SegNet case: the ``host`` line, and unless host_only the device lines."""
+    from sketchyscenecolorization_amd import matching
+    tag = segnet_case_name(widths, use_attn, size)
+    cfg = matching.MatchConfig(size=size, filters=SEGNET_FILTERS, backbone='segnet', use_attn=bool(use_attn), **WIDTHS[widths])
+    variables = matching.random_variables(cfg, 41)
+    out = [(tag + ' host random_variables(41)', _sha(b''.join(variables[k].tobytes() for k in variables)))]
+    if not host_only:
+        _inference_and_head_trainer(out, tag, cfg, variables, train=size == 64)
+    return out
 
 
 def recorded(path, tag='parent'):
@@ -172,8 +203,13 @@ if __name__ == '__main__':
     ap.add_argument('--tree', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument('--tag', default='tree')
     ap.add_argument('--host_only', type=int, default=0, help='1: only the lines that need no device')
+    ap.add_argument('--segnet', type=int, default=0, help='1: the cases of segnet_digests in place of the DeepLab ones')
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
-    for widths, use_attn in CASES:
-        for what, sha in (host_digests if a.host_only else digests)(widths, use_attn):
+    if a.segnet:
+        cases = [segnet_digests(*case, host_only=bool(a.host_only)) for case in SEGNET_CASES]
+    else:
+        cases = [(host_digests if a.host_only else digests)(widths, use_attn) for widths, use_attn in CASES]
+    for lines in cases:
+        for what, sha in lines:
             print('%s sha256 %s %s' % (a.tag, sha, what), flush=True)

@@ -90,7 +90,7 @@ def main():
                                                         torch.cuda.get_device_name(0), hip.build_hash()),
              'load (host-made random weights, fold, pad, upload; wall clock, once)   %9.1f ms' % (load_s * 1e3),
              'backbone (input copy, preprocess, %d convs, max-pool, 4 rearrangements)   %9.3f ms  (min %.3f, max %.3f)'
-             % (1 + sum(3 + (cin != cout) for _s, cin, cout, _st, _r in cfg.unit_list()), med['backbone'], min(stages['backbone']),
+             % (1 + sum(3 + (cin != cout) for _s, cin, cout, _st, _r in cfg.net.unit_list()), med['backbone'], min(stages['backbone']),
                 max(stages['backbone'])),
              'head (projection, l2 norms, %d + %d LSTM steps, squash + projection)      %9.3f ms  (min %.3f, max %.3f)'
              % (seq_len, seq_len, med['head'], min(stages['head']), max(stages['head'])),

@@ -1,21 +1,21 @@
-"""What the matcher's SegNet backbone (match_main.py --weights segnet) costs at 768 x 768, in one session on
-one card:
+"""What the matcher's two backbones (match_main.py --weights deeplab | segnet; DESIGN.md sections 8.6 and 8.12) cost at 768 x 768,
+on this tree and on another one (the parent commit), in one session on one card:
 
-  * the backbone's forward pass (MatchModel.segnet) between device events, beside the DeepLab-ResNet's (MatchModel.backbone);
-  * ssc_max_pool2_argmax at the five pool sizes and ssc_unpool2 at the two unpool sizes of that pass, between device events, with
-    the bytes each moves;
-  * one iteration of ``match_main.py --mode train`` with --scene_cache device and features, --weights segnet and --weights deeplab,
-    and the --weights deeplab command line of another tree (the parent commit, which reads no such flag in these modes) -- every
-    configuration --repeats times, in turn;
+  * the two backbones' forward passes (MatchModel.backbone) between device events, a process per tree, --repeats times in turn;
+  * ssc_max_pool2_argmax at the five pool sizes and ssc_unpool2 at the two unpool sizes of SegNet's pass, between device events,
+    with the bytes each moves (this tree's first process only);
+  * one iteration of ``match_main.py --mode train`` with --scene_cache device and features, --weights deeplab and --weights segnet,
+    of this tree and of the other one -- every configuration --repeats times, in turn;
   * scripts/match_forward_digest.py on this tree against the other tree: the lines must be equal.
 
-    python scripts/match_segnet_rate.py --parent /path/to/a/built/checkout/of/the/parent --out profiles/match_segnet.txt
+    python scripts/match_segnet_rate.py --parent /path/to/a/built/checkout/of/the/parent --out profiles/match_backbones.txt
 
 The synthetic scenes, the random backbones, the processes under their own time limits and the windows are those of
-scripts/match_cache_rate.py.  A run that fails ends the session: nothing more is started.  No threshold is set for SegNet: there
-is no earlier figure; the bar for --weights deeplab is the parent's figure within the session's run-to-run spread."""
+scripts/match_cache_rate.py.  A run that fails ends the session: nothing more is started.  The bar for every figure is the
+parent's figure for the same configuration within the session's run-to-run spread."""
 import argparse
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -46,8 +46,9 @@ def _timed(fn, reps, warm=3):
 
 
 def worker(args):
-    """One process: the two backbones' forward passes and the two kernels at the pass's sizes."""
-    sys.path.insert(0, ROOT)
+    """One process: the two backbones' forward passes of the tree --tree and, with --kernels, the two kernels at the sizes of
+    SegNet's pass."""
+    sys.path.insert(0, os.path.abspath(args.tree))
     import numpy as np
     import torch
     from sketchyscenecolorization_amd import hip, matching
@@ -59,12 +60,13 @@ def worker(args):
         model.init_random(1)
         x4, _stroke = hip.match_preprocess_u8(model.put_sketch(sk), out=model._buf('x4', (1, 768, 768, 4)))
         ms = [_timed(lambda: model.backbone(x4), args.reps) for _ in range(3)]
-        extra = ', %d bytes of scratch memory' % cfg.segnet_scratch_bytes() if backbone == 'segnet' else ''
-        print('%s backbone forward at 768 x 768, random weights: %s ms per pass (three windows of %d passes between two device events)%s'
-              % (backbone, ' '.join('%.3f' % m for m in ms), args.reps, extra))
+        print('%s backbone forward at 768 x 768, random weights: %s ms per pass (three windows of %d passes between two device events)'
+              % (backbone, ' '.join('%.3f' % m for m in ms), args.reps))
         model.close()
         del model
         torch.cuda.empty_cache()
+    if not args.kernels:
+        return
     print('the two kernels at the sizes of that pass, %d calls between two device events on the same buffers (repeated calls find '
           'much of a tensor in the last-level cache, so the rates are not those of the memory; the small sizes are bounded by the '
           'launch):' % (10 * args.reps))
@@ -96,6 +98,23 @@ def digests(tree, timeout):
     return [line.split(' ', 3)[2:] for line in r.stdout.strip().split('\n') if line.startswith('x sha256 ')]
 
 
+def forwards(tree, args, kernels):
+    """The worker on ``tree`` in a process of its own -> ({backbone: mean ms of its three windows}, the lines it printed)."""
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--worker', '--reps', str(args.reps), '--tree', tree] +
+                       (['--kernels'] if kernels else []), stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True,
+                       timeout=args.timeout)
+    if r.returncode != 0:
+        sys.stderr.write(r.stderr[-4000:])
+        raise SystemExit('the worker failed on %s: exit status %d -- nothing more is started' % (tree, r.returncode))
+    said, ms = r.stdout.strip().split('\n'), {}
+    for line in said:
+        m = re.match(r'(\w+) backbone forward .*?: ([0-9. ]+) ms per pass', line)
+        if m:
+            w = [float(v) for v in m.group(2).split()]
+            ms[m.group(1)] = sum(w) / len(w)
+    return ms, said
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--parent', default='', help='a built checkout of the parent commit (timed and digested beside this tree)')
@@ -109,16 +128,20 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--out', default='')
     ap.add_argument('--worker', action='store_true')
+    ap.add_argument('--tree', default=ROOT, help='worker: the tree whose package it imports')
+    ap.add_argument('--kernels', action='store_true', help='worker: the two kernels as well')
     args = ap.parse_args()
     if args.worker:
         return worker(args)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--worker', '--reps', str(args.reps)], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, universal_newlines=True, timeout=args.timeout)
-    if r.returncode != 0:
-        sys.stderr.write(r.stderr[-4000:])
-        raise SystemExit('the worker failed: exit status %d -- nothing more is started' % r.returncode)
-    lines = r.stdout.strip().split('\n')
-    print('\n'.join(lines), flush=True)
+    trees = [('tree', ROOT)] + ([('parent', os.path.abspath(args.parent))] if args.parent else [])
+    lines, res = [], {}
+    for rep in range(args.repeats):
+        for who, tree in trees:
+            ms, said = forwards(tree, args, kernels=rep == 0 and tree == ROOT)
+            for backbone, v in ms.items():
+                res.setdefault('%s %s forward' % (who, backbone), []).append(v)
+            lines += ['[%-6s run %d] %s' % (who, rep + 1, s) for s in said]
+            print('\n'.join(lines[-len(said):]), flush=True)
     base = tempfile.mkdtemp()
     t0 = time.time()
     base_rate.write_data(base, args.scenes, args.captions)
@@ -133,32 +156,27 @@ def main():
     seg = ['--weights', 'segnet', '--backbone_snapshot', segnet]
     plan = []
     for cache in ('device', 'features'):
-        if args.parent:
-            plan.append(('parent ' + cache, os.path.abspath(args.parent), ['--scene_cache', cache]))
-        plan.append(('deeplab ' + cache, ROOT, ['--scene_cache', cache, '--weights', 'deeplab']))
-        plan.append(('segnet ' + cache, ROOT, ['--scene_cache', cache] + seg))
-    res = {name: [] for name, _, _ in plan}
+        for who, tree in trees:
+            plan.append(('%s deeplab %s' % (who, cache), tree, ['--scene_cache', cache, '--weights', 'deeplab']))
+            plan.append(('%s segnet %s' % (who, cache), tree, ['--scene_cache', cache] + seg))
+    res.update({name: [] for name, _, _ in plan})
     for rep in range(args.repeats):
         for name, tree, extra in plan:
             ms, said = base_rate.run(tree, base, '%s_%d' % (name.replace(' ', '_'), rep), args, extra)
             res[name].append(sum(ms[1:]) / max(1, len(ms[1:])))
-            lines.append('[%-16s run %d] %s  -> %.2f' % (name, rep + 1, ' '.join('%.2f' % m for m in ms), res[name][-1]))
+            lines.append('[%-22s run %d] %s  -> %.2f' % (name, rep + 1, ' '.join('%.2f' % m for m in ms), res[name][-1]))
             if rep == 0:
-                lines += ['[%-16s run 1] %s' % (name, s) for s in said if s.startswith('scene cache:')]
+                lines += ['[%-22s run 1] %s' % (name, s) for s in said if s.startswith('scene cache:')]
             print(lines[-1], flush=True)
     mean = {k: sum(v) / len(v) for k, v in res.items()}
     spread = {k: max(v) - min(v) for k, v in res.items()}
-    lines.append('mean of the runs (run-to-run spread): ' + ', '.join('%s %.2f (%.2f)' % (k, mean[k], spread[k]) for k in res))
-    for cache in ('device', 'features'):
-        if args.parent:
-            a, b = 'deeplab ' + cache, 'parent ' + cache
-            s, d = max(spread[a], spread[b]), mean[a] - mean[b]
-            lines.append('--weights deeplab --scene_cache %s %.2f ms against the parent %.2f ms: %+.2f ms (%+.1f %%), %s the run-to-run '
-                         'spread of %.2f ms' % (cache, mean[a], mean[b], d, 100 * d / mean[b],
-                                                'not slower beyond' if d <= s else 'SLOWER by more than', s))
-        d = mean['segnet ' + cache] - mean['deeplab ' + cache]
-        lines.append('--weights segnet --scene_cache %s %.2f ms against --weights deeplab %.2f ms: %+.2f ms (recorded, not bounded)'
-                     % (cache, mean['segnet ' + cache], mean['deeplab ' + cache], d))
+    lines.append('mean of the runs (run-to-run spread), ms: ' + ', '.join('%s %.3f (%.3f)' % (k, mean[k], spread[k]) for k in res))
+    if args.parent:
+        for what in [k[len('tree '):] for k in res if k.startswith('tree ')]:
+            a, b = 'tree ' + what, 'parent ' + what
+            sp, d = max(spread[a], spread[b]), mean[a] - mean[b]
+            lines.append('%s: this tree %.3f ms against the parent %.3f ms: %+.3f ms (%+.1f %%), %s the run-to-run spread of %.3f ms'
+                         % (what, mean[a], mean[b], d, 100 * d / mean[b], 'not slower beyond' if d <= sp else 'SLOWER by more than', sp))
     shutil.rmtree(base, ignore_errors=True)
     if args.parent:
         here, there = digests(ROOT, args.timeout), digests(os.path.abspath(args.parent), args.timeout)

@@ -1,10 +1,10 @@
 """Training the matcher's backbone beside its fusion head (match_main.py --train_backbone 1; RMI_model.py::train_op with
-train_fusion_var_only=False, RMI_model.py:320-330): every ResNet/*/DW filter of the DeepLab-ResNet learns, through norms that stay
-as they were loaded -- beta, gamma, factor, mean and variance are trainable=False and bn=False reads the stored moments
-(deeplab_model.py:176-231).  DESIGN.md section 8.10.
+train_fusion_var_only=False, RMI_model.py:320-330): every filter of the DeepLab-ResNet (DeepLabBackbone.trained_variable_names:
+ResNet/*/DW) learns, through norms that stay as they were loaded -- beta, gamma, factor, mean and variance are trainable=False and
+bn=False reads the stored moments (deeplab_model.py:176-231).  DESIGN.md section 8.10.
 
-    forward   backbone_train: MatchModel.backbone with keep (the feature map has inference's bits): every unit's raw conv
-              outputs r1, r2, r3, sc and its merged output in buffers of their own
+    forward   backbone_train: MatchModel.backbone with keep (DeepLabBackbone.forward; the feature map has inference's bits): every
+              unit's raw conv outputs r1, r2, r3, sc and its merged output in buffers of their own
     backward  MatchTrainer.backward with dfeat = dvp . DW^T -> ssc_space_to_batch(2) per doubling of the rate (the backward of
               the final ungroup) -> per unit, last to first: ssc_unit_merge_bwd (the closing relu, both branches), conv_wgrad /
               conv_dgrad through block_3, block_2, block_1 with ssc_frozen_act_bwd between them (the consumer-side views are the
@@ -23,8 +23,9 @@ from .match_train import MatchTrainer
 
 
 def backbone_variable_names(config):
-    """The trained backbone variables under their checkpoint names, in variable_shapes' order: the ResNet/*/DW filters."""
-    return [n for n in config.variable_shapes() if n.startswith('ResNet/') and n.endswith('/DW')]
+    """The trained backbone variables under their checkpoint names, in variable_shapes' order: the backbone object's (for the
+    DeepLab-ResNet its filters; ValueError from a backbone without a backward)."""
+    return config.net.trained_variable_names()
 
 
 def trained_variable_names(config, train_backbone):
@@ -36,7 +37,7 @@ def unit_geometry(config):
     """[(scope, cin, cout, stride, space_to_batch(2) moves in front of the unit, shape of its input, shape of its output)] as
     ``backbone_train`` runs the units: groups 4 and 5 in the space-to-batch layout."""
     n, h, cur, out = 1, config.size // 4, 1, []
-    for scope, cin, cout, stride, rate in config.unit_list():
+    for scope, cin, cout, stride, rate in config.net.unit_list():
         moves = 0
         while cur < rate:
             n, h, cur, moves = n * 4, h // 2, cur * 2, moves + 1
@@ -65,7 +66,7 @@ def forward_buffer_shapes(config):
             s['bt/%s/%s' % (scope, tag)] = (n, oh, ow, ch)
     while cur > 1:
         n, oh, ow, cur = n // 4, oh * 2, ow * 2, cur // 2
-        s['bt/b2s%d' % cur] = (n, oh, ow, c.filters[4])
+        s['bt/b2s%d' % cur] = (n, oh, ow, c.feat_channels)
     return s
 
 
@@ -77,7 +78,7 @@ def backward_buffer_shapes(config):
     def add(tag, shape):
         key, shape = _gkey(tag, shape)
         s[key] = shape
-    s['bb/dfeat'] = (1, c.feat, c.feat, c.filters[4])
+    s['bb/dfeat'] = (1, c.feat, c.feat, c.feat_channels)
     n, h, w, ch = s['bb/dfeat']
     while n < geo[-1][6][0]:
         n, h, w = n * 4, h // 2, w // 2
@@ -102,11 +103,7 @@ def backward_buffer_shapes(config):
 def training_bytes(config):
     """-> (bytes of the kept activations, bytes of the backward's scratch, bytes of the gradient and the two Adam slot buffers)."""
     n = lambda shapes: 4 * sum(int(np.prod(v)) for v in shapes.values())
-    span = 0
-    for name, shape in config.variable_shapes().items():
-        scope, leaf = name.rsplit('/', 1)
-        if name.startswith('ResNet/') and leaf in ('DW', 'gamma'):
-            span += -(-(int(np.prod(shape)) * (2 if leaf == 'gamma' else 1)) // 64) * 64
+    span = sum(-(-int(np.prod(shape)) // 64) * 64 for shape in config.net.device_tensors().values())      # as MatchModel lays them out
     return n(forward_buffer_shapes(config)), n(backward_buffer_shapes(config)), 3 * 4 * span
 
 
@@ -132,7 +129,7 @@ class BackboneMatchTrainer(MatchTrainer):
         self.b_names = backbone_variable_names(self.cfg)
         self.b_hi = self.lo             # the backbone is the stretch of the flat buffer in front of the head
         inside = [n for n, (o, _s) in lay.items() if o < self.b_hi]
-        assert all(n.startswith('ResNet/') for n in inside) and [n for n in inside if n.endswith('/DW')] == self.b_names, inside
+        assert inside == list(self.cfg.net.device_tensors()) and [n for n in inside if n in self.b_names] == self.b_names, inside
         self.b_params, (self.b_grad, self.b_adam_m, self.b_adam_v), self.b_spans, (self.bg, self.bm, self.bv) = \
             match_train.trained_stretch(model, self.b_names, 0, self.b_hi)
         self._kept = None           # what MatchModel.backbone kept of the latest pass: units, x4, r0
@@ -176,7 +173,7 @@ class BackboneMatchTrainer(MatchTrainer):
         if self._kept is None:
             raise RuntimeError('backward without a backbone_train before it')
         if dfeat is None:
-            dfeat = self._bbuf('bb/dfeat', (1, c.feat, c.feat, c.filters[4]))
+            dfeat = self._bbuf('bb/dfeat', (1, c.feat, c.feat, c.feat_channels))
         MatchTrainer.backward(self, dpred, dfeat)
         self.backbone_backward(dfeat)
 
@@ -184,10 +181,10 @@ class BackboneMatchTrainer(MatchTrainer):
         return self._bbuf(*_gkey(tag, shape))
 
     def backbone_backward(self, dfeat):
-        """dfeat float [1,S/8,S/8,filters[4]]: the gradient on ``backbone_train``'s feature map.  Fills ``bg``."""
+        """dfeat float [1,S/8,S/8,feat_channels]: the gradient on ``backbone_train``'s feature map.  Fills ``bg``."""
         from . import hip
         from .hip import ACT_RELU, View
-        c, d, bg = self.cfg, self.model.d, self.bg
+        c, d, bg, net = self.cfg, self.model.d, self.bg, self.cfg.net
         units = self._kept['units']
         # the scratch buffers are reused from unit to unit: every launch, the filter gradients included, is on this one stream
         assert hip.WGRAD_STREAM is None
@@ -240,8 +237,8 @@ class BackboneMatchTrainer(MatchTrainer):
                 self.on_part(scope.rsplit('/', 1)[1][:-2])         # 'group_5' .. 'group_2': the group's units are behind us
         # the pool with conv1's relu, then conv1's filter: 3 real channels of the 4-channel input, SAME pad (2, 3)
         r0 = self._kept['r0']
-        dr0 = hip.max_pool3s2_bwd(g, r0, d['ResNet/group_1/bn_conv1'], out=self._bbuf('bb/dr0', r0.shape))
-        hip.conv_wgrad(View(self._kept['x4']), View(dr0), bg['ResNet/group_1/conv1/DW'], 2, hip.same_pad_before(c.size, 7, 2))
+        dr0 = hip.max_pool3s2_bwd(g, r0, d[net.CONV1_NORM], out=self._bbuf('bb/dr0', r0.shape))
+        hip.conv_wgrad(View(self._kept['x4']), View(dr0), bg[net.CONV1], 2, hip.same_pad_before(c.size, 7, 2))
         hip.join_wgrad()
         if self.on_part is not None:
             self.on_part('pool and conv1')

@@ -57,7 +57,7 @@ class MatchSceneCache(object):
     match_eval.load_ground_truth (its ValueErrors pass through), on at most 16 threads.
 
     On the device: ``sketch`` uint8 [n,S,S,3], ``labels`` uint8 [n,S,S] and, with ``features`` = a loaded MatchModel, ``feat``
-    float [n,S/8,S/8,filters[4]]: entry i is model.features(sketch[i]) copied, so build the cache after the weights are loaded.
+    float [n,S/8,S/8,feat_channels]: entry i is model.features(sketch[i]) copied, so build the cache after the weights are loaded.
     On the host: ``n_inst`` int64 [n], ``area`` int64 [n,256] (ssc_label_hist_u8 of every label map).
     ``beside``: the bytes of the caches that are on the device already and count against the same limit;
     ``remedy_scenes`` / ``remedy_features``: what the refusal tells the user to do."""

@@ -1,5 +1,5 @@
 """Training the matcher's fusion head (Instance_Matching/matching_main.py::train, RMI_model.py::train_op with
-train_fusion_var_only, utils/loss.py): the DeepLab backbone stays frozen, the text_sketchyscene/* head -- the visual projection,
+train_fusion_var_only, utils/loss.py): the backbone stays frozen, the text_sketchyscene/* head -- the visual projection,
 the embedding, the word LSTM, the multimodal LSTM and the output projection -- learns.  DESIGN.md section 8.8.
 
     per iteration  MatchModel.features (frozen backbone) -> head_train (MatchModel.head with keep: every step's state kept)
@@ -29,10 +29,10 @@ import random
 import numpy as np
 
 from . import matching
+from .match_backbones import BACKBONES
 from .matching import HEAD, pack_head, unpack_head, unpad_gate_columns  # noqa: F401 (the head's packing lives beside pad_lstm)
 
 BETA1, BETA2, EPSILON = 0.9, 0.999, 1e-8
-MODEL_NAME = 'deeplab_RMI'
 LIVE_MAX_BYTE = 104         # im[..., 0] < 0 with mu_0 = 104.00698793
 
 
@@ -242,7 +242,7 @@ class MatchTrainer(object):
     # ------------------------------------------------------------------ backward
     def backward(self, dpred, dfeat=None):
         """dpred float [h,w]: the gradient on ``head_train``'s pred.  Fills the gradient of every trained tensor (device layout).
-        dfeat float [1,h,w,filters[4]]: receives the gradient on ``head_train``'s feat (match_backbone_train.py); without it
+        dfeat float [1,h,w,feat_channels]: receives the gradient on ``head_train``'s feat (match_backbone_train.py); without it
         nothing goes into the backbone."""
         import torch
         from . import hip
@@ -373,7 +373,7 @@ class MatchTrainer(object):
     def step(self, scene, lut, tok, seq_len, lr):
         """scene: {'sketch': uint8 [S,S,3], 'labels': uint8 [S,S]} (host arrays, or a dict ``upload_scene`` has been applied to:
         'labels_d'), or its device-resident form (match_cache.MatchSceneCache.entry): {'sketch_d': uint8 [S,S,3], 'labels_d':
-        uint8 [S,S]} on the device, the loss reads them where they are, and with 'feat_d' float [1,S/8,S/8,filters[4]] -- what
+        uint8 [S,S]} on the device, the loss reads them where they are, and with 'feat_d' float [1,S/8,S/8,feat_channels] -- what
         MatchModel.features gives for that sketch -- the backbone does not run; lut uint8 [256]; tok the sentence's max_len
         indices; seq_len its real length; lr the step's learning rate.
         One iteration.  -> the class loss of the PREVIOUS step (None at the first): the value is read one step late, the step
@@ -461,7 +461,7 @@ class MatchTrainer(object):
 
 def model_name(backbone='deeplab'):
     """The reference's weights_name + '_' + model_name: deeplab_RMI, segnet_RMI."""
-    return MODEL_NAME if backbone == 'deeplab' else '%s_RMI' % backbone
+    return BACKBONES[backbone].model_name
 
 
 def snapshot_prefix(snapshot_root, iteration, backbone='deeplab'):

@@ -1,14 +1,15 @@
-"""The instance matcher of the scene pipeline, inference only, batch 1 (Pipeline_utils/fg_matching_utils.py::
-build_instance_matching): RMI_model.py in eval mode (fusion_type 'RMI', no attention) on the DeepLab-ResNet backbone of
-deeplab_model.py (is_intermediate, frozen norms), then get_pred_instance_mask's choice of the instances the prediction covers.
-DESIGN.md section 8.6.  MatchConfig(use_attn=True): the model class's word attention (RMI_model.py:202-217) -- a softmax over the
-word LSTM's outputs weighs the multimodal LSTM's outputs of every word, their sum feeds the projection; DESIGN.md section 8.11.
+"""The instance matcher of the scene pipeline, batch 1 (Pipeline_utils/fg_matching_utils.py::build_instance_matching): RMI_model.py
+(fusion_type 'RMI') on one of its backbones, then get_pred_instance_mask's choice of the instances the prediction covers.  This
+module holds the host side (text, padding, MatchConfig), the fusion head and the whole pass, for inference and -- with ``keep`` --
+as the forward pass of training; everything that depends on which backbone runs is in match_backbones.py.  DESIGN.md section 8.6.
+MatchConfig(use_attn=True): the model class's word attention (RMI_model.py:202-217) -- a softmax over the word LSTM's outputs
+weighs the multimodal LSTM's outputs of every word, their sum feeds the projection; DESIGN.md section 8.11.
 
     sketch uint8 [S,S,3] --ssc_match_preprocess_u8--> x [1,S,S,4], stroke [S,S]
-    backbone: 7x7 s2 conv, max-pool (ssc_max_pool3s2), bottleneck units [3,4,23,3] -- hip.conv_forward with the producer's frozen
-              norm and relu folded into the consumer's View, ssc_residual_merge at every unit's end.  Groups 4 and 5 (atrous
-              rates 2 and 4) run in the space-to-batch layout, where their 3x3 convs are plain ones: ssc_space_to_batch(2) in
-              front of either group, ssc_batch_to_space(2) twice behind the last unit.
+    backbone: MatchModel.backbone -> MatchConfig.net.forward, the pass of a class of match_backbones.py on this model's buffers
+              and weights -> the visual feature [1,S/8,S/8,feat_channels].  MatchConfig(backbone='deeplab'): the DeepLab-ResNet of
+              deeplab_model.py, frozen norms (DeepLabBackbone); 'segnet': SegNet of segnet_model.py, the norms of the one image
+              (SegNetBackbone)
     head:     1x1 projection + l2 norm, word LSTM, multimodal LSTM per location (hip.lstm_step_fwd on gate blocks padded to a
               multiple of 32), ssc_squash_project, ssc_match_finish -> up [S,S], predicts [S,S]
               use_attn: ssc_attn_scores_fwd behind the word LSTM, ssc_dev_scaled_add behind every multimodal step, and
@@ -18,12 +19,8 @@ word LSTM's outputs weighs the multimodal LSTM's outputs of every word, their su
 ``features`` and ``predict`` are the pass in two halves -- the backbone once per scene, the head once per caption -- for the
 evaluation on a split (match_eval.py).
 
-``head``, ``unit``, ``backbone`` and ``features`` are also the forward pass of training: with ``keep`` they leave what a backward
-pass reads in buffers of its own (match_train.py, match_backbone_train.py; DESIGN.md sections 8.8 and 8.10).
-
-MatchConfig(backbone='segnet'): the SegNet backbone of segnet_model.py (is_intermediate) in place of the DeepLab-ResNet -- 18 3x3
-convs, each behind the batch-statistics norm of the one image, five 2x2 pools that remember where each maximum was
-(ssc_max_pool2_argmax) and two unpools that put values back there (ssc_unpool2); ``MatchModel.segnet``, DESIGN.md section 8.12.
+``head``, ``backbone`` and ``features`` are also the forward pass of training: with ``keep`` they leave what a backward pass reads
+in buffers of its own (match_train.py, match_backbone_train.py; DESIGN.md sections 8.8 and 8.10).
 
 Not here: the backward pass and the optimiser (match_train.py), the backbones fcn_8s and deeplab_v3plus,
 SegNet's backward, fusion_type 'RecurAttn', post_processing_mask_with_segmentation."""
@@ -32,23 +29,18 @@ import re
 
 import numpy as np
 
-NORM_EPS = 0.001
+from .match_backbones import BACKBONES, NORM_PARTS, fold_norm  # noqa: F401 (folding a frozen norm stays part of the host interface)
+
 OCCUPIED_THRESH = 0.5
 UNK, PAD = '<unk>', '<pad>'
 _SPLIT = re.compile(r'(\W+)')
-NORM_PARTS = ('beta', 'gamma', 'factor', 'mean', 'variance')
 ATTN_MAX_LEN = 64           # hip.ATTN_MAX_T: the words the attention kernels hold
 HEAD = 'text_sketchyscene/'          # the scope of the fusion head's variables
 ATTN_VARIABLES = (HEAD + 'attn_fc/DW', HEAD + 'attn_fc/biases')
-# backbone -> (its released widths); the scope of its variables in a checkpoint
-BACKBONES = {'deeplab': (64, 256, 512, 1024, 2048), 'segnet': (64, 128, 256, 512, 512)}
-BACKBONE_SCOPE = {'deeplab': 'ResNet/', 'segnet': 'SegNet/'}
-# tf.contrib.layers.batch_norm with its defaults (segnet_model.py:133): no gamma; the moving moments exist and are never read
-SEGNET_NORM_PARTS = ('beta', 'moving_mean', 'moving_variance')
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# host: text, spatial table, folding and padding
+# host: text, spatial table, padding
 # ---------------------------------------------------------------------------------------------------------------------------
 def load_vocab(path):
     """One word per line -> {word: line number} (load_vocab_dict_from_file)."""
@@ -85,15 +77,6 @@ def spatial_features(h, w):
             ymin, ymax = y / h * 2 - 1, (y + 1) / h * 2 - 1
             out[y, x, :] = [xmin, ymin, xmax, ymax, (xmin + xmax) / 2, (ymin + ymax) / 2, 1 / w, 1 / h]
     return out
-
-
-def fold_norm(beta, gamma, factor, mean, variance):
-    """The frozen norm y = (x - mean/factor) * rsqrt(variance/factor + 0.001) * gamma + beta as y = a*x + b: float32 [2C] =
-    [a | b], worked out in float64."""
-    beta, gamma, mean, variance = (np.asarray(v, np.float64).reshape(-1) for v in (beta, gamma, mean, variance))
-    factor = float(np.asarray(factor, np.float64).reshape(-1)[0])
-    a = gamma / np.sqrt(variance / factor + NORM_EPS)
-    return np.concatenate([a, beta - mean / factor * a]).astype(np.float32)
 
 
 def pad32(c):
@@ -178,8 +161,8 @@ def unpack_head(config, dev):
 
 class MatchConfig(object):
     """The sizes of the matcher.  The defaults are the released model; the tests run small ones through the same code.
-    backbone: 'deeplab' (units and filters: the bottleneck groups of the DeepLab-ResNet) or 'segnet' (filters: the widths of
-    enc_1 .. enc_5 of segnet_model.py, units is not read); filters None: the backbone's released widths."""
+    backbone: a name of match_backbones.BACKBONES; size, units and filters (None: the released widths) are that backbone's, whose
+    object is ``net``."""
 
     def __init__(self, size=768, units=(3, 4, 23, 3), filters=None, v_emb=1000, w_emb=1000, w_rnn=1000,
                  m_rnn=500, vocab_size=76, max_len=15, use_attn=False, backbone='deeplab'):
@@ -188,25 +171,12 @@ class MatchConfig(object):
         if backbone not in BACKBONES:
             raise ValueError("backbone %r: %s; the other backbones are not built" % (backbone, ' or '.join(map(repr, BACKBONES))))
         self.use_attn, self.backbone = bool(use_attn), backbone
-        if filters is None:
-            filters = BACKBONES[backbone]
-        self.size, self.units, self.filters = int(size), tuple(int(u) for u in units), tuple(int(f) for f in filters)
         self.v_emb, self.w_emb, self.w_rnn, self.m_rnn = int(v_emb), int(w_emb), int(w_rnn), int(m_rnn)
         self.vocab_size, self.max_len = int(vocab_size), int(max_len)
-        if self.size < 32 or self.size % 32:
-            raise ValueError('size %d: the matcher needs a multiple of 32 (%s)' % (self.size, 'SegNet pools 2 x 2 five times'
-                             if backbone == 'segnet' else 'its 1/8 map is cut into 4 x 4 sub-images'))
-        if len(self.units) != 4 or min(self.units) < 1 or len(self.filters) != 5:
-            raise ValueError('units %r / filters %r: four groups of at least one unit, five widths' % (self.units, self.filters))
-        # a bottleneck's inner width is a quarter of its outer one; SegNet's convs have the widths themselves
-        widths = [('filters[%d]' % k, f) for k, f in enumerate(self.filters)] if backbone == 'segnet' else \
-            [('filters[0]', self.filters[0])] + [('filters[%d] / 4' % k, f // 4) for k, f in enumerate(self.filters) if k]
-        for name, c in widths + \
-                [('v_emb', self.v_emb), ('w_emb', self.w_emb), ('w_rnn', self.w_rnn), ('m_rnn', self.m_rnn)]:
-            if c < 4 or c % 4:
-                raise ValueError('%s = %d: every channel count must be a multiple of 4' % (name, c))
-        if any(f % 4 for f in self.filters):
-            raise ValueError('filters %r: every channel count must be a multiple of 4' % (self.filters,))
+        self.net = net = BACKBONES[backbone](size, units, filters)      # the backbone object: everything that depends on which one
+        self.size, self.units, self.filters = net.size, net.units, net.filters
+        self.feat_channels = net.feat_channels      # the channels of the visual feature map
+        net.check_widths([('v_emb', self.v_emb), ('w_emb', self.w_emb), ('w_rnn', self.w_rnn), ('m_rnn', self.m_rnn)])
         if self.vocab_size < 2 or self.max_len < 1:
             raise ValueError('vocab_size %d, max_len %d' % (self.vocab_size, self.max_len))
         if self.use_attn and self.max_len > ATTN_MAX_LEN:
@@ -216,88 +186,10 @@ class MatchConfig(object):
     def feat(self):
         return self.size // 8
 
-    def unit_list(self):
-        """[(scope, cin, cout, stride, rate)] of the bottleneck units in order."""
-        out, f = [], self.filters
-        for g, (n, stride, rate) in enumerate(zip(self.units, (1, 2, 1, 1), (1, 1, 2, 4))):
-            for i in range(n):
-                out.append(('ResNet/group_%d_%d' % (g + 2, i), f[g] if i == 0 else f[g + 1], f[g + 1], stride if i == 0 else 1, rate))
-        return out
-
-    @property
-    def feat_channels(self):
-        """The channels of the visual feature map: the last group's of the DeepLab-ResNet, dec_4's (= enc_4's) of SegNet."""
-        return self.filters[3] if self.backbone == 'segnet' else self.filters[4]
-
-    def segnet_stages(self):
-        """[(stage, [(cin, cout)] of its 3x3 convs)] of segnet_model.py:56-95 up to intermediate_feat.  An encoder stage ends in
-        its 2x2 pool; a decoder stage begins with the unpool by the codes of the encoder stage of its number, whose width its
-        input therefore has: dec_5 ends at enc_4's width."""
-        f1, f2, f3, f4, f5 = self.filters
-        return [('enc_1', [(3, f1), (f1, f1)]), ('enc_2', [(f1, f2), (f2, f2)]), ('enc_3', [(f2, f3), (f3, f3), (f3, f3)]),
-                ('enc_4', [(f3, f4), (f4, f4), (f4, f4)]), ('enc_5', [(f4, f5), (f5, f5), (f5, f5)]),
-                ('dec_5', [(f5, f5), (f5, f5), (f5, f4)]), ('dec_4', [(f4, f4), (f4, f4)])]
-
-    def segnet_plan(self):
-        """The device pass of the SegNet backbone as [(op, stage, k, channels in, channels out, side in, side out)], op one of
-        'conv' (k: the conv's number from 0), 'pool', 'act' (a decoder stage's last norm and relu materialised) and 'unpool'."""
-        plan, h = [], self.size
-        for stage, convs in self.segnet_stages():
-            if stage.startswith('dec'):
-                plan.append(('unpool', stage, None, convs[0][0], convs[0][0], h, 2 * h))
-                h *= 2
-            for k, (cin, cout) in enumerate(convs):
-                plan.append(('conv', stage, k, cin, cout, h, h))
-            if stage.startswith('enc'):
-                plan.append(('pool', stage, None, cout, cout, h, h // 2))
-                h //= 2
-            else:
-                plan.append(('act', stage, None, cout, cout, h, h))
-        return plan
-
-    def segnet_scratch_floats(self):
-        """The floats of the two scratch buffers the SegNet pass alternates between: every step reads what the step before it
-        wrote and writes into the other buffer, so each holds the largest tensor that falls to it; the last step's output (the
-        feature map) has a buffer of its own."""
-        need = [0, 0]
-        for n, (_op, _stage, _k, _cin, cout, _h, oh) in enumerate(self.segnet_plan()[:-1]):
-            need[n & 1] = max(need[n & 1], oh * oh * cout)
-        return need
-
-    def segnet_scratch_bytes(self):
-        """What the SegNet pass allocates beyond the weights: the two scratch buffers, the input, the codes of the five pools
-        (one byte per pooled element) and the feature map."""
-        codes = sum(oh * oh * cout for op, _s, _k, _cin, cout, _h, oh in self.segnet_plan() if op == 'pool')
-        return 4 * (sum(self.segnet_scratch_floats()) + self.size * self.size * 4 + self.feat * self.feat * self.feat_channels) + codes
-
-    def _segnet_variable_shapes(self, s):
-        for stage, convs in self.segnet_stages():
-            for k, (cin, cout) in enumerate(convs):
-                s['SegNet/%s/conv%d/DW' % (stage, k + 1)] = (3, 3, cin, cout)
-                s['SegNet/%s/conv%d/biases' % (stage, k + 1)] = (cout,)
-            for k, (_cin, cout) in enumerate(convs):        # the norms of a stage are numbered in call order
-                for p in SEGNET_NORM_PARTS:
-                    s['%s/%s' % (segnet_norm_scope(stage, k), p)] = (cout,)
-
-    def _deeplab_variable_shapes(self, s):
-        f = self.filters
-
-        def norm(scope, c):
-            for p in NORM_PARTS:
-                s[scope + '/' + p] = (1,) if p == 'factor' else (c,)
-        s['ResNet/group_1/conv1/DW'] = (7, 7, 3, f[0])
-        norm('ResNet/group_1/bn_conv1', f[0])
-        for scope, cin, cout, _stride, _rate in self.unit_list():
-            c4 = cout // 4
-            for blk, shape in (('block_1', (1, 1, cin, c4)), ('block_2', (3, 3, c4, c4)), ('block_3', (1, 1, c4, cout))) + \
-                    ((('block_add', (1, 1, cin, cout)),) if cin != cout else ()):
-                s['%s/%s/conv/DW' % (scope, blk)] = shape
-                norm('%s/%s/bn' % (scope, blk), shape[3])
-
     def variable_shapes(self):
-        """{checkpoint name: shape} of everything inference reads (and, of SegNet, the moving moments that ride along unread)."""
-        s = {}
-        (self._segnet_variable_shapes if self.backbone == 'segnet' else self._deeplab_variable_shapes)(s)
+        """{checkpoint name: shape} of everything inference reads: the backbone's variables (and what rides along unread with
+        them), then the head's."""
+        s = self.net.variable_shapes()
         h = HEAD
         s[h + 'visual_feat_projection/DW'] = (1, 1, self.feat_channels, self.v_emb)
         s[h + 'visual_feat_projection/biases'] = (self.v_emb,)
@@ -312,33 +204,6 @@ class MatchConfig(object):
             s[h + 'attn_fc/DW'] = (self.w_rnn, 1)
             s[h + 'attn_fc/biases'] = (1,)
         return s
-
-
-def segnet_norm_scope(stage, k):
-    """The scope of the norm behind conv k (from 0) of a SegNet stage: tf.contrib.layers.batch_norm's default scope, numbered
-    within the stage in call order -- BatchNorm, BatchNorm_1, BatchNorm_2."""
-    return 'SegNet/%s/BatchNorm%s' % (stage, '' if k == 0 else '_%d' % k)
-
-
-def check_backbone_variables(names, backbone):
-    """names: the variable names of a checkpoint (any container).  ValueError when it holds the variables of the other backbone:
-    a head trained on one backbone's feature map gives nothing meaningful on the other's.  Names the flag and a variable."""
-    for other, scope in BACKBONE_SCOPE.items():
-        if other != backbone:
-            found = sorted(n for n in names if n.startswith(scope))
-            if found:
-                raise ValueError("the checkpoint holds %s: it belongs to the %s backbone (--weights %s), not to --weights %s"
-                                 % (found[0], other, other, backbone))
-
-
-def check_segnet_scratch(config, free):
-    """The bytes MatchModel.segnet allocates at its first pass (MatchConfig.segnet_scratch_bytes) against ``free``, the bytes free
-    on the device: -> the bytes; ValueError when they are more than half of what is free."""
-    need = config.segnet_scratch_bytes()
-    if need > int(free) // 2:
-        raise ValueError('the SegNet backbone needs %d bytes of scratch memory at size %d, more than half of the %d bytes free on '
-                         'the device' % (need, config.size, int(free)))
-    return need
 
 
 def check_attention_variables(names, use_attn):
@@ -380,7 +245,7 @@ def random_variables(config, seed=0):
     for name, shape in config.variable_shapes().items():
         leaf = name.rsplit('/', 1)[1]
         n = int(np.prod(shape))
-        if leaf == 'DW' and name.startswith(('ResNet/', 'SegNet/')):
+        if leaf == 'DW' and not name.startswith(HEAD):           # a backbone's filter
             v = rng.randn(*shape) * np.sqrt(2.0 / (shape[0] * shape[1] * shape[3]))
         elif leaf in ('DW', 'kernel', 'embedding'):
             v = draw_head_weight(rng, leaf, shape)
@@ -435,25 +300,9 @@ class MatchModel(object):
             pass
 
     def _device_shapes(self):
-        """What the kernels read: conv filters as stored, every norm as its [a | b] table, the LSTM kernels cut by input rows
-        and padded by gate blocks, the spatial table."""
-        c, s = self.cfg, {}
-        for name, shape in c.variable_shapes().items():
-            scope, leaf = name.rsplit('/', 1)
-            if name.startswith('ResNet/'):
-                if leaf == 'DW':
-                    s[name] = shape
-                elif leaf == 'gamma':
-                    s[scope] = (2 * shape[0],)
-            elif name.startswith('SegNet/'):
-                # the filters (the first one's 3 input channels padded to 4) and the betas; the biases cancel in the norm and the
-                # moving moments are never read (DESIGN.md section 8.12)
-                if leaf == 'DW':
-                    s[name] = (3, 3, max(shape[2], 4), shape[3])
-                elif leaf == 'beta':
-                    s[name] = shape
-        if c.backbone == 'segnet':
-            s['SegNet/ones'] = (max(c.filters),)      # the scale of a norm without gamma
+        """What the kernels read: the backbone's tensors (Backbone.device_tensors), the LSTM kernels cut by input rows and padded
+        by gate blocks, the spatial table."""
+        c, s = self.cfg, self.cfg.net.device_tensors()
         cw, cm = self.cw, self.cm
         s['vproj/w'], s['vproj/b'] = (1, 1, c.feat_channels, c.v_emb), (c.v_emb,)
         s['embedding'] = (c.vocab_size, c.w_emb)
@@ -475,38 +324,23 @@ class MatchModel(object):
         import torch
         c, host = self.cfg, {}
         check_attention_variables(variables, c.use_attn)
-        check_backbone_variables(variables, c.backbone)
+        c.net.check_variables(variables)
         for name, shape in c.variable_shapes().items():
             src = name
             if src not in variables:
                 for new, old in OLD_CELL_NAMES.items():
                     if name.endswith(new) and name[:-len(new)] + old in variables:
                         src = name[:-len(new)] + old
-            if src not in variables and name.startswith('SegNet/') and name.rsplit('/', 1)[1] in SEGNET_NORM_PARTS[1:]:
-                # a checkpoint without the moving moments: their initial values; nothing reads them, snapshots carry them
-                host[name] = (np.ones if name.endswith('variance') else np.zeros)(shape, dtype=np.float32)
+            if src not in variables:        # only a backbone may say that a checkpoint need not hold one of its variables
+                host[name] = None if name.startswith(HEAD) else c.net.missing_variable(name, shape)
+                if host[name] is None:
+                    raise ValueError('the checkpoint has no variable %s' % name)
                 continue
-            if src not in variables:
-                raise ValueError('the checkpoint has no variable %s' % name)
             v = np.asarray(variables[src])
             if tuple(v.shape) != tuple(shape):
                 raise ValueError('variable %s is %s, the model needs %s' % (src, tuple(v.shape), tuple(shape)))
             host[name] = np.ascontiguousarray(v, dtype=np.float32)
-        dev = {}
-        for name, v in host.items():
-            scope, leaf = name.rsplit('/', 1)
-            if name.startswith('ResNet/'):
-                if leaf == 'DW':
-                    dev[name] = v
-                elif leaf == 'gamma':
-                    dev[scope] = fold_norm(*[host[scope + '/' + p] for p in NORM_PARTS])
-            elif name.startswith('SegNet/'):
-                if leaf == 'DW':
-                    dev[name] = np.pad(v, ((0, 0), (0, 0), (0, max(4 - v.shape[2], 0)), (0, 0)))
-                elif leaf == 'beta':
-                    dev[name] = v
-        if c.backbone == 'segnet':
-            dev['SegNet/ones'] = np.ones(max(c.filters), np.float32)
+        dev = c.net.device_tensors(host)
         dev.update(pack_head(c, host))
         dev['spatial'] = spatial_features(c.feat, c.feat).reshape(-1, 8)
         assert set(dev) == set(self.d), set(dev) ^ set(self.d)
@@ -534,130 +368,13 @@ class MatchModel(object):
         return b
 
     # ------------------------------------------------------------------ backbone
-    # Every pass below takes ``keep``.  None: inference -- the intermediate buffers are shared from unit to unit and from step to
-    # step, nothing beyond the result outlives the pass.  A dict: training -- every output the backward reads goes to a buffer of
-    # its own (t_* in the head, bt/* in the backbone), and the dict is filled with the record the backward reads
-    # (match_train.py, match_backbone_train.py).  The launches and their operands' values are the same either way.
-    def unit(self, x, scope, stride, slot=0, keep=None):
-        """One bottleneck unit on x float [N,H,W,cin] (materialised) -> relu(norm(block_3) + shortcut) [N,H/stride,W/stride,cout].
-        Each raw conv output is read by its consumer through the producer's folded norm and relu.  keep: x, r1, r2, r3, sc (None
-        for the identity shortcut) and out, in buffers bt/<scope>/*."""
-        from . import hip
-        from .hip import ACT_RELU, View
-        d = self.d
-        n, h, w, cin = x.shape
-        oh, ow = -(-h // stride), -(-w // stride)
-        w1, w2, w3 = (d['%s/block_%d/conv/DW' % (scope, k)] for k in (1, 2, 3))
-        c4, cout = w1.shape[3], w3.shape[3]
-        # inference: the units share r1, r2, r3 and sc, and alternate between two outputs (a unit reads its predecessor's)
-        own, out_tag = ('', 'out%d' % slot) if keep is None else ('bt/%s/' % scope, 'bt/%s/out' % scope)
-        r1 = self._buf(own + 'r1', (n, oh, ow, c4))
-        hip.conv_forward(View(x), w1, stride, 0, r1, same=True)
-        r2 = self._buf(own + 'r2', (n, oh, ow, c4))
-        hip.conv_forward(View(r1, None, d[scope + '/block_1/bn'], ACT_RELU), w2, 1, 0, r2, same=True)
-        r3 = self._buf(own + 'r3', (n, oh, ow, cout))
-        hip.conv_forward(View(r2, None, d[scope + '/block_2/bn'], ACT_RELU), w3, 1, 0, r3, same=True)
-        out = self._buf(out_tag, (n, oh, ow, cout))
-        assert out.data_ptr() != x.data_ptr()
-        wadd = d.get(scope + '/block_add/conv/DW')
-        sc = None
-        if wadd is not None:
-            sc = self._buf(own + 'sc', (n, oh, ow, cout))
-            hip.conv_forward(View(x), wadd, stride, 0, sc, same=True)
-        else:
-            assert cin == cout and stride == 1, (scope, cin, cout, stride)
-        hip.call('ssc_residual_merge', r3, d[scope + '/block_3/bn'], x if sc is None else sc, d.get(scope + '/block_add/bn'), ACT_RELU,
-                 out, n * oh * ow, cout)
-        if keep is not None:
-            keep.update(scope=scope, stride=stride, x=x, r1=r1, r2=r2, r3=r3, sc=sc, out=out)
-        return out
-
-    def regroup(self, x, rate_from, rate_to, tag='s2b'):
-        """x in the space-to-batch layout of rate_from (1: the image itself) -> the layout of rate_to (2 or 4), in the buffer
-        ``tag``: one ssc_space_to_batch(2).  Applied to the rate-2 layout it leaves sub-image (n*4 + i1*2 + j1)*4 + i2*2 + j2 with
-        the pixels y % 4 == 2*i2 + i1, x % 4 == 2*j2 + j1: every sub-image is one residue class mod 4, which is all a rate-4 conv
-        asks."""
-        from . import hip
-        assert rate_to == 2 * rate_from, (rate_from, rate_to)
-        n, h, w, c = x.shape
-        return hip.space_to_batch(x, 2, out=self._buf(tag, (n * 4, h // 2, w // 2, c)))
-
-    def ungroup(self, x, rate, tag='b2s'):
-        """The way back from ``regroup``: one ssc_batch_to_space(2) per halving of the rate, into the buffer ``tag`` formatted
-        with the rate it arrives at."""
-        from . import hip
-        while rate > 1:
-            nb, h, w, c = x.shape
-            rate //= 2
-            x = hip.batch_to_space(x, 2, out=self._buf(tag.format(rate), (nb // 4, h * 2, w * 2, c)))
-        return x
-
     def backbone(self, x4, keep=None):
-        """x4 float [1,S,S,4] (ssc_match_preprocess_u8) -> the visual feature [1,S/8,S/8,filters[4]].  keep: x4, r0 (conv1's raw
-        output) and units, the list of every unit's record with ``regroups``, the space_to_batch(2) moves in front of it; the
-        buffers are those of match_backbone_train.forward_buffer_shapes."""
-        from . import hip
-        from .hip import View
-        c, d = self.cfg, self.d
-        if c.backbone == 'segnet':
-            if keep is not None:
-                raise ValueError('the SegNet backward is not built: its backbone is run frozen, nothing is kept of its pass')
-            return self.segnet(x4)
-        s = c.size
-        own = '' if keep is None else 'bt/'
-        r0 = self._buf(own + 'conv1', (1, s // 2, s // 2, c.filters[0]))
-        hip.conv_forward(View(x4), d['ResNet/group_1/conv1/DW'], 2, 0, r0, same=True)
-        x = hip.max_pool3s2(r0, d['ResNet/group_1/bn_conv1'], out=self._buf(own + 'pool', (1, s // 4, s // 4, c.filters[0])))
-        cur, units = 1, []
-        for k, (scope, _cin, _cout, stride, rate) in enumerate(c.unit_list()):
-            rec = None if keep is None else {'regroups': 0}
-            while cur < rate:
-                x = self.regroup(x, cur, cur * 2, 's2b' if keep is None else 'bt/s2b%d' % (cur * 2))
-                cur *= 2
-                if rec is not None:
-                    rec['regroups'] += 1
-            x = self.unit(x, scope, stride, k & 1, keep=rec)
-            units.append(rec)
-        if keep is not None:
-            keep.update(units=units, x4=x4, r0=r0)
-        return self.ungroup(x, cur, 'b2s' if keep is None else 'bt/b2s{}')     # group_last's relu: the last unit's output is one already
-
-    def segnet(self, x4):
-        """The SegNet backbone (segnet_model.py:56-99, is_intermediate): x4 float [1,S,S,4] -> the visual feature
-        [1,S/8,S/8,filters[3]] in the buffer sn/feat.  Every conv is followed by the batch-statistics norm of its one image
-        (no gamma, eps 0.001) and a relu: hip.conv_forward folds the statistics to [a | b] behind the conv, and the next conv or
-        the pool applies them and the relu as it loads.  The conv's bias is left out: the norm takes it off again with the mean.
-        The steps alternate between two scratch buffers (MatchConfig.segnet_scratch_floats); the pools' codes have buffers of
-        their own (sn/code/<stage>), enc_5's and enc_4's are read by the unpools."""
-        import torch
-        from . import hip
-        from .hip import ACT_NONE, ACT_RELU, View
-        c, d = self.cfg, self.d
-        plan = c.segnet_plan()
-        flat = [self._buf('sn/scratch%d' % k, (n,)) for k, n in enumerate(c.segnet_scratch_floats())]
-        x, ab, codes = x4, None, {}
-        for n, (op, stage, k, cin, cout, h, oh) in enumerate(plan):
-            last = n == len(plan) - 1
-            out = self._buf('sn/feat', (1, oh, oh, cout)) if last else flat[n & 1][:oh * oh * cout].view(1, oh, oh, cout)
-            assert out.data_ptr() != x.data_ptr()
-            if op == 'conv':
-                norm = segnet_norm_scope(stage, k)
-                ab_new, stats = self._buf('sn/ab/' + norm, (2 * cout,)), self._buf('sn/stats/' + norm, (2 * cout,))
-                hip.conv_forward(View(x, None, ab, ACT_RELU if ab is not None else ACT_NONE),
-                                 d['SegNet/%s/conv%d/DW' % (stage, k + 1)], 1, 0, out, same=True,
-                                 bn=(d['SegNet/ones'][:cout], d[norm + '/beta'], ab_new, stats, NORM_EPS))
-                ab = ab_new
-            elif op == 'pool':
-                codes[stage] = self._buf('sn/code/' + stage, (1, oh, oh, cout), torch.uint8)
-                hip.max_pool2_argmax(x, ab, out=out, code=codes[stage])
-                ab = None
-            elif op == 'act':       # a decoder stage's last norm and relu, materialised for the unpool and for the head
-                hip.call('ssc_affine_act', x, cout, ab, cout, ACT_RELU, out, cout, oh * oh, cout)
-                ab = None
-            else:
-                hip.unpool2(x, codes['enc_' + stage[4:]], out=out)
-            x = out
-        return x
+        """x4 float [1,S,S,4] (ssc_match_preprocess_u8) -> the visual feature [1,S/8,S/8,feat_channels]: the pass of the
+        configuration's backbone (match_backbones.py) on this model's buffers and weights.  keep None: inference, nothing beyond
+        the result outlives the pass.  A dict: training -- every output the backward reads goes to a buffer of its own and the dict
+        is filled with the record the backward reads (match_backbone_train.py); ValueError from a backbone whose pass cannot be
+        kept.  The launches and their operands' values are the same either way."""
+        return self.cfg.net.forward(self, x4, keep)
 
     # ------------------------------------------------------------------ head
     def _lstm_planes(self, tag, rows, C):
@@ -690,7 +407,7 @@ class MatchModel(object):
         return acts
 
     def head(self, feat, tok, seq_len, keep=None):
-        """feat float [1,h,w,filters[4]], tok int32 [T] on the device, seq_len on the host -> pred float [h,w].  keep: the cell
+        """feat float [1,h,w,feat_channels], tok int32 [T] on the device, seq_len on the host -> pred float [h,w].  keep: the cell
         state, the output and the activated gates of every step of both cells stay (MatchTrainer.backward reads them from it)."""
         from . import hip
         from .hip import View
@@ -799,7 +516,7 @@ class MatchModel(object):
     # ------------------------------------------------------------------ the pass in two halves (match_eval.py)
     def features(self, sketch_u8, keep=None):
         """The half of ``forward`` that does not read the sentence: sketch uint8 [S,S,3] (host or device) -> (feat float
-        [1,S/8,S/8,filters[4]], stroke uint8 [S,S]), both in buffers of their own that only the next ``features`` overwrites --
+        [1,S/8,S/8,feat_channels], stroke uint8 [S,S]), both in buffers of their own that only the next ``features`` overwrites --
         no ``head``, ``predict`` or ``forward`` call touches them.  keep: ``backbone``'s."""
         import torch
         from . import hip

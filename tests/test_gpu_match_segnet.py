@@ -378,6 +378,33 @@ def test_features_and_predict_equal_forward(small_segnets):
         model.features(sk, keep={})
 
 
+def _digest_script():
+    sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+    try:
+        import match_forward_digest as D
+    finally:
+        sys.path.pop(0)
+    return D
+
+
+@pytest.mark.parametrize('widths,use_attn,size', _digest_script().SEGNET_CASES)
+def test_segnet_gives_the_parents_bits(widths, use_attn, size):
+    """profiles/match_backbones_once.txt keeps the digests scripts/match_forward_digest.py --segnet 1 printed on the parent commit's
+    tree, where the SegNet pass was a method of MatchModel behind an ``if``: head at L = 15, 3, 1, forward, features, predict, and
+    at size 64 three steps of the head trainer on the frozen backbone (one from a device-resident scene with its feature map), the
+    snapshot's bytes, a resumed step; with each the names that went through hip.call in order.  Size 96 (an odd 3 x 3 map behind
+    the last pool) is inference alone.  This tree's are the same, every line."""
+    D = _digest_script()
+    tag = D.segnet_case_name(widths, use_attn, size) + ' '
+    want = {k: v for k, v in D.recorded(os.path.join(ROOT, 'profiles', 'match_backbones_once.txt')).items()
+            if k.startswith(tag) and ' host ' not in k}
+    got = {k: v for k, v in D.segnet_digests(widths, use_attn, size) if ' host ' not in k}
+    assert len(want) == (20 if size == 64 else 10) and set(got) == set(want), set(got) ^ set(want)
+    for what, sha in got.items():
+        print('%s: %s' % (what, sha))
+        assert sha == want[what], what
+
+
 @pytest.fixture(scope='module')
 def split(tmp_path_factory):
     base = str(tmp_path_factory.mktemp('match_segnet'))
@@ -432,7 +459,7 @@ def test_command_line_in_fresh_processes(split, tmp_path):
                       '--max_iteration', '2', '--log_freq', '1', '--snapshot_root', root, '--log_root', root + '_log',
                       '--scene_cache', 'device', '--val_freq', '2'] + split['flags'], str(tmp_path))
     prefix = os.path.join(root, 'segnet_RMI_iter_2.tfmodel')
-    assert 'model saved to ' + prefix in printed and 'segnet backbone: %d bytes of scratch memory' % cfg.segnet_scratch_bytes() in printed
+    assert 'model saved to ' + prefix in printed and 'segnet backbone: %d bytes of scratch memory' % cfg.net.scratch_bytes() in printed
     assert 'firstly train, loaded ' + backbone in printed and os.path.exists(prefix + '.index')
     assert os.path.exists(os.path.join(root + '_log', 'match_validation.jsonl'))
     results = str(tmp_path / 'results')
@@ -466,7 +493,7 @@ def test_released_size_runs_and_repeats():
     times.  No oracle here, as in test_real_size_runs_and_repeats: the arithmetic is held by the tests above."""
     m = M()
     cfg = m.MatchConfig(backbone='segnet')
-    need = m.check_segnet_scratch(cfg, torch.cuda.mem_get_info()[0])
+    need = cfg.net.check_scratch(torch.cuda.mem_get_info()[0])
     model = m.MatchModel(cfg)
     model.init_random(1)
     sk = _sketch(768, 768)

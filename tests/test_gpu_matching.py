@@ -155,9 +155,9 @@ def test_regrouping_from_rate_2_to_rate_4(small_model_64):
     class mod 4 (y % 4 == 2*i2 + i1), and two batch_to_space(2) lead back."""
     m = small_model_64
     x = np.random.RandomState(3).randn(1, 8, 12, 8).astype(np.float32)
-    a = m.regroup(_dev(x), 1, 2)
+    a = m.cfg.net.regroup(m, _dev(x), 1, 2)
     assert np.array_equal(a.cpu().numpy(), _s2b(x, 2))
-    b = m.regroup(a, 2, 4)
+    b = m.cfg.net.regroup(m, a, 2, 4)
     got = b.cpu().numpy()
     assert np.array_equal(got, _s2b(_s2b(x, 2), 2))
     for i1 in range(2):
@@ -165,7 +165,7 @@ def test_regrouping_from_rate_2_to_rate_4(small_model_64):
             for i2 in range(2):
                 for j2 in range(2):
                     assert np.array_equal(got[(i1 * 2 + j1) * 4 + i2 * 2 + j2], x[0, 2 * i2 + i1::4, 2 * j2 + j1::4])
-    assert np.array_equal(m.ungroup(b, 4).cpu().numpy(), x)
+    assert np.array_equal(m.cfg.net.ungroup(m, b, 4).cpu().numpy(), x)
 
 
 # ------------------------------------------------------------------ max-pool
@@ -383,10 +383,10 @@ def test_unit_at_real_widths(wide_model, scope, cin, rate):
     S = _unit_abs_sum(x.astype(np.float64), v, scope, 1, rate)
     xd, cur = _dev(x), 1
     while cur < rate:
-        xd = m.regroup(xd, cur, cur * 2).clone()
+        xd = m.cfg.net.regroup(m, xd, cur, cur * 2).clone()
         cur *= 2
     assert tuple(xd.shape) == (rate * rate, 8 // rate, 8 // rate, cin)
-    got = m.ungroup(m.unit(xd, scope, 1), rate)
+    got = m.cfg.net.ungroup(m, m.cfg.net.unit(m, xd, scope, 1), rate)
     cout = ref.shape[3]
     K = max(9 * cout // 4, cin)
     assert (ref > 0).any() and (ref == 0).any()

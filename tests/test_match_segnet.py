@@ -3,6 +3,7 @@
 norm, the moving moments through a snapshot, and the command line's refusals -- every one before any device call."""
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -73,6 +74,22 @@ def test_the_default_configuration_is_unchanged():
         M.MatchConfig(backbone='fcn_8s')
 
 
+def test_segnet_initial_variables_have_the_parents_bits():
+    """profiles/match_backbones_once.txt keeps the digests scripts/match_forward_digest.py --segnet 1 printed on the parent commit's
+    tree; its ``host`` lines are random_variables(cfg, 41) of the SegNet cases, which rest on the order of the backbone's
+    variables and which every device line of that record starts from.  This tree's are the same."""
+    sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+    try:
+        import match_forward_digest as D
+    finally:
+        sys.path.pop(0)
+    want = {k: v for k, v in D.recorded(os.path.join(ROOT, 'profiles', 'match_backbones_once.txt')).items() if ' host ' in k}
+    got = dict(line for case in D.SEGNET_CASES for line in D.segnet_digests(*case, host_only=True))
+    assert len(want) == 5 and set(got) == set(want), set(got) ^ set(want)
+    for what, sha in got.items():
+        assert sha == want[what], what
+
+
 def test_a_size_that_is_no_multiple_of_32_is_refused():
     for size in (48, 72, 16, 760):
         with pytest.raises(ValueError, match='multiple of 32'):
@@ -87,16 +104,16 @@ def test_scratch_memory_is_the_largest_live_pair():
     element; the refusal names the bytes."""
     cfg = M.MatchConfig(backbone='segnet')
     big = 768 * 768 * 64
-    assert cfg.segnet_scratch_floats() == [big, big]
+    assert cfg.net.scratch_floats() == [big, big]
     codes = 384 * 384 * 64 + 192 * 192 * 128 + 96 * 96 * 256 + 48 * 48 * 512 + 24 * 24 * 512
     need = 4 * (2 * big + 768 * 768 * 4 + 96 * 96 * 512) + codes
-    assert cfg.segnet_scratch_bytes() == need
-    assert M.check_segnet_scratch(cfg, 2 * need) == need
+    assert cfg.net.scratch_bytes() == need
+    assert cfg.net.check_scratch(2 * need) == need
     with pytest.raises(ValueError, match=str(need)):
-        M.check_segnet_scratch(cfg, 2 * need - 2)
-    ops = [p[0] for p in cfg.segnet_plan()]
+        cfg.net.check_scratch(2 * need - 2)
+    ops = [p[0] for p in cfg.net.plan()]
     assert ops.count('conv') == 18 and ops.count('pool') == 5 and ops.count('unpool') == 2 and ops[-1] == 'act'
-    assert [(p[1], p[5], p[6]) for p in cfg.segnet_plan() if p[0] == 'unpool'] == [('dec_5', 24, 48), ('dec_4', 48, 96)]
+    assert [(p[1], p[5], p[6]) for p in cfg.net.plan() if p[0] == 'unpool'] == [('dec_5', 24, 48), ('dec_4', 48, 96)]
 
 
 # ------------------------------------------------------------------ the oracle on its own definitions

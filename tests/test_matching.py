@@ -143,7 +143,7 @@ def test_config_refusals():
     assert shapes['ResNet/group_4_22/block_2/conv/DW'] == (3, 3, 256, 256) and 'ResNet/group_4_23/block_1/conv/DW' not in shapes
     assert shapes['text_sketchyscene/mLSTM/lstm_cell/kernel'] == (3508, 2000)
     assert shapes['text_sketchyscene/wLSTM/lstm_cell/kernel'] == (2000, 4000)
-    units = cfg.unit_list()
+    units = cfg.net.unit_list()
     assert [u for u in units if u[3] == 2] == [('ResNet/group_3_0', 256, 512, 2, 1)]
     assert {u[4] for u in units if u[0].startswith('ResNet/group_4')} == {2} and {u[4] for u in units if u[0].startswith('ResNet/group_5')} == {4}
 
