@@ -198,7 +198,7 @@ int ssc_conv_forward_bn(const ssc_conv_desc* d, float* ws, int64_t ws_bytes, con
 /* the one-output patch head over a 512-channel tensor (discriminate_pix2pix layer_5, models_collection.py:833-835: 4x4,
  * stride 1, 512 -> 1) as streaming kernels (head1.hip): forward (ws: 64 B per input pixel), its data gradient (the
  * hip.conv_dgrad descriptor: one-channel dy, "NK" filter, flipped taps) and its filter gradient (ws: up to 256 x 32 KB slabs).
- * ssc_conv_forward / ssc_conv_wgrad dispatch to them when _supported; SSC_HEAD1=0 keeps the general kernels. */
+ * ssc_conv_forward / ssc_conv_wgrad dispatch to them when _supported. */
 int ssc_head1_forward_supported(const ssc_conv_desc* d);
 int ssc_head1_forward(const ssc_conv_desc* d, float* ws, int64_t ws_bytes, void* stream);
 int ssc_head1_dgrad_supported(const ssc_conv_desc* d);

@@ -1,5 +1,6 @@
 #!/bin/bash
 # lower bound (in fills of the chip's 2 x CUs workgroup slots) from which the planner may take the 128 x 128 / 16-k tile
+export SSC_DEV_SWITCHES=1
 one() { python bench.py "$@" --no-cpu-baseline --no-secondary --no-kernel-events --no-gen-fb 2>/dev/null | python -c "import sys,json; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('%8.3f ms' % j['ms_per_step'], end='  ')"; }
 for r in 1 2; do
   for v in ${HK_MINS:-0 0.5 1 2 100}; do

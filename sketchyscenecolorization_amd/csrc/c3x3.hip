@@ -403,19 +403,9 @@ __global__ __launch_bounds__(256) void c3x3n16_kernel(const ssc_conv_desc d, int
     }
 }
 
-static bool c3_on() {
-    static int on = -1;         // SSC_C3X3=0: the tile kernel (A/B)
-    if (on < 0) {
-        const char* e = ssc_dev_getenv("SSC_C3X3");
-        on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    return on != 0;
-}
-
 extern "C" int ssc_conv_c3x3_supported(const ssc_conv_desc* dp) {
     const ssc_conv_desc& d = *dp;
     const int C = d.x.C0;
-    if (!c3_on()) return 0;
     if (d.x.C1 != 0 || (C != 16 && C != 32) || d.k_real != C) return 0;
     if (d.nphase != 1 || d.TH != 3 || d.TW != 3 || d.KH != 3 || d.KW != 3 || d.in_stride != 1 || d.ioff_y != -1 || d.ioff_x != -1 ||
         d.out_stride != 1 || d.ooff_y != 0 || d.ooff_x != 0)
@@ -458,12 +448,7 @@ int ssc_conv_c3x3_forward(const ssc_conv_desc* dp, float* stat, void* stream) {
     const int G = ssc_conv_c3x3_walkers(dp);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)2 * (tr + 2) * (tcw + 2) * (d.x.C0 + 1) * sizeof(float);
-    static int n16 = -1;        // SSC_C3X3_N16=0: the 32-column instruction also at 16 outputs (A/B)
-    if (n16 < 0) {
-        const char* e = ssc_dev_getenv("SSC_C3X3_N16");
-        n16 = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    if (d.x.C0 == 16 && d.Nn <= 16 && tcw == 32 && n16) {
+    if (d.x.C0 == 16 && d.Nn <= 16 && tcw == 32) {
         hipLaunchKernelGGL(c3x3n16_kernel, dim3(G), dim3(256), 0, st, d, tiles, tiles_x, tiles_y, stat);
     } else if (d.x.C0 == 16) {
         if (tcw == 32)

@@ -533,14 +533,7 @@ __device__ __forceinline__ bool fold_rows(const float* __restrict__ partial, int
     }
     return lane == 0 && c < C;
 }
-static inline int fold_wpc(int nblk) {
-    static int force1 = -1;     // SSC_FOLD_WPC=1: always one wave per channel (A/B)
-    if (force1 < 0) {
-        const char* e = ssc_dev_getenv("SSC_FOLD_WPC");
-        force1 = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
-    return (nblk >= 512 && !force1) ? 4 : 1;
-}
+static inline int fold_wpc(int nblk) { return nblk >= 512 ? 4 : 1; }
 static inline unsigned fold_grid(int C, int wpc) { return wpc == 4 ? (unsigned)C : (unsigned)((C + 3) / 4); }
 
 __global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const float* __restrict__ partial, int nblk, int C,
@@ -1135,11 +1128,10 @@ __attribute__((target("sse4.2"))) static uint32_t crc32c_hw(const uint8_t* data,
     return c32 ^ 0xffffffffu;
 }
 static int crc32c_have_hw() {
-    static int have = -1;
-    if (have < 0) {
+    static const int have = [] {
         const char* e = getenv("SSC_CRC_TABLES");        // 1: the table form (tests compare the two)
-        have = (e != nullptr && e[0] == '1') ? 0 : (__builtin_cpu_supports("sse4.2") ? 1 : 0);
-    }
+        return (e != nullptr && e[0] == '1') ? 0 : (__builtin_cpu_supports("sse4.2") ? 1 : 0);
+    }();
     return have;
 }
 #endif

@@ -137,9 +137,7 @@ __global__ __launch_bounds__(256) void fewchan_conv_kernel(const ssc_conv_desc d
 }
 
 extern "C" int ssc_conv_fewchan_supported(const ssc_conv_desc* dp) {
-    static const bool on = ssc_dev_getenv("SSC_FEWCHAN") == nullptr || atoi(ssc_dev_getenv("SSC_FEWCHAN")) != 0;
     const ssc_conv_desc& d = *dp;
-    if (!on) return 0;
     if (d.x.C1 != 0 || (d.x.C0 != 4 && d.x.C0 != 8) || d.x.ab0 != nullptr || d.x.act != SSC_ACT_NONE) return 0;
     if (d.nphase != 1 || d.TH != 4 || d.TW != 4 || d.KH != 4 || d.KW != 4 || d.in_stride != 2 || d.ioff_y != -1 || d.ioff_x != -1 ||
         d.ky0 != 0 || d.kx0 != 0 || d.kstep != 1 || d.bmode != 0)

@@ -139,18 +139,8 @@ __global__ __launch_bounds__(256) void fewchan7_conv_kernel(const ssc_conv_desc 
     }
 }
 
-static bool f7_on() {
-    static int on = -1;         // SSC_FEWCHAN7=0: the tile kernel (A/B)
-    if (on < 0) {
-        const char* e = ssc_dev_getenv("SSC_FEWCHAN7");
-        on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    return on != 0;
-}
-
 extern "C" int ssc_conv_fewchan7_supported(const ssc_conv_desc* dp) {
     const ssc_conv_desc& d = *dp;
-    if (!f7_on()) return 0;
     if (d.x.C1 != 0 || d.x.C0 != 4 || d.x.ab0 != nullptr || d.x.act != SSC_ACT_NONE) return 0;
     if (d.nphase != 1 || d.TH != 7 || d.TW != 7 || d.KH != 7 || d.KW != 7 || d.in_stride != 2 || d.ioff_y != -2 || d.ioff_x != -2 ||
         d.ky0 != 0 || d.kx0 != 0 || d.kstep != 1 || d.bmode != 0)

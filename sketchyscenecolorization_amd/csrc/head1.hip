@@ -448,14 +448,6 @@ H1Geo make_geo(int NB, int H, int W, int OH, int OW, int ld1, int TH, int TW, in
 bool geo_ok(int NB, int H, int W) {     // multiply-high decode exact: q * (H*W) < 2^32, H*W > 1, W > 1
     return H > 1 && W > 1 && (unsigned long)NB * H * W * (unsigned long)(H * W) < 0xffffffffUL;
 }
-int env_off() {
-    static int off = -1;
-    if (off < 0) {
-        const char* e = ssc_dev_getenv("SSC_HEAD1");
-        off = (e != nullptr && e[0] == '0') ? 1 : 0;
-    }
-    return off;
-}
 unsigned wave_blocks(int npix) {        // 4 waves per block, a few pixels per wave
     int b = (npix + 15) / 16;
     if (b > 1024) b = 1024;
@@ -468,7 +460,6 @@ unsigned wave_blocks(int npix) {        // 4 waves per block, a few pixels per w
 // forward form: out[p][0] = sum_{tap, c} act(x[p@tap][c]) * w[tap][c][0]
 extern "C" int ssc_head1_forward_supported(const ssc_conv_desc* dp) {
     const ssc_conv_desc& d = *dp;
-    if (env_off()) return 0;
     return d.nphase == 1 && d.bmode == 0 && d.in_stride == 1 && d.kstep == 1 && d.ky0 == 0 && d.kx0 == 0 && d.out_stride == 1 &&
            d.ooff_y == 0 && d.ooff_x == 0 && d.Nn == 1 && d.n_off == 0 && d.Nstore >= 1 && d.Nstore <= d.ldc &&
            d.TH * d.TW <= MAXT && d.KH == d.TH && d.KW == d.TW && view_ok(d.x) && d.k_real == HC && d.wC0 == HC && d.wC1 == 1 &&
@@ -495,7 +486,6 @@ extern "C" int ssc_head1_forward(const ssc_conv_desc* dp, float* ws, int64_t ws_
 // data-gradient form (hip.conv_dgrad, stride 1): x = dy [N,h,w,>=1] channel 0, "NK" filter [KH][KW][512][1], flipped taps
 extern "C" int ssc_head1_dgrad_supported(const ssc_conv_desc* dp) {
     const ssc_conv_desc& d = *dp;
-    if (env_off()) return 0;
     return d.nphase == 1 && d.bmode == 1 && d.in_stride == 1 && d.out_stride == 1 && d.ooff_y == 0 && d.ooff_x == 0 &&
            (d.kstep == 1 || d.kstep == -1) && d.k_real == 1 && narrow_ok(d.x) && d.wC0 == HC && d.wC1 == 1 && d.n_off == 0 &&
            d.Nn == HC && d.Nstore == HC && d.ldc == HC && d.TH * d.TW <= MAXT && d.KH == d.TH && d.KW == d.TW &&
@@ -522,7 +512,6 @@ extern "C" int ssc_head1_dgrad(const ssc_conv_desc* dp, void* stream) {
 // filter-gradient form: dw[tap][c] = sum_p act(x[p@tap][c]) * dy[p][0]
 extern "C" int ssc_head1_wgrad_supported(const ssc_wgrad_desc* dp) {
     const ssc_wgrad_desc& d = *dp;
-    if (env_off()) return 0;
     return view_ok(d.g) && narrow_ok(d.d) && d.in_stride == 1 && d.Cg_real == HC && d.Nn == 1 && d.ldc == 1 &&
            d.TH * d.TW <= MAXT && al16(d.out) && geo_ok(d.NB, d.g.H, d.g.W);
 }

@@ -9,12 +9,24 @@
 // They select paths the test suite does not cover in combination -- lab tools (scripts/), not supported configurations;
 // DESIGN.md section 7 lists the supported switches.
 static inline const char* ssc_dev_getenv(const char* name) {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("SSC_DEV_SWITCHES");
-        on = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
+    static const bool on = [] { const char* e = getenv("SSC_DEV_SWITCHES"); return e != nullptr && e[0] == '1'; }();
     return on ? getenv(name) : nullptr;
+}
+// A developer switch as a number: the variable through atoi / atof when it is unlocked and set, `dflt` otherwise.  Switches
+// are 0 / 1 or a number; anything else reads as atoi / atof read it (an empty or non-numeric value is 0).  Call sites keep the
+// value in a function-local `static const`: read once per process, initialised thread-safely.
+static inline int ssc_dev_int(const char* name, int dflt) {
+    const char* e = ssc_dev_getenv(name);
+    return e != nullptr ? atoi(e) : dflt;
+}
+static inline double ssc_dev_double(const char* name, double dflt) {
+    const char* e = ssc_dev_getenv(name);
+    return e != nullptr ? atof(e) : dflt;
+}
+// SSC_ARITH=fp32 (a supported configuration, not a developer switch): every contraction on the exact-fp32 MFMA kernels
+static inline bool ssc_arith_fp32() {
+    static const bool fp32 = [] { const char* e = getenv("SSC_ARITH"); return e != nullptr && (e[0] == 'f' || e[0] == 'F'); }();
+    return fp32;
 }
 
 // true the first time this call site (its own `done` mask) runs on the current device

@@ -72,16 +72,6 @@ int ssc_sk_configure_bf(const unsigned* cfg4);
 // in-launch K-slice hand-off (conv_ut_kernel): {wait bound in ticks of the 100 MHz wall clock (lo, hi), test hook: producers
 // withhold their flags, -}.  ssc_sk_configure writes it.
 __device__ unsigned g_sk_cfg[4] = {2000000000u, 0u, 0u, 0u};
-#ifndef SSC_BDMA
-#define SSC_BDMA 1       // filter tiles of conv_ut_kernel by LDS-DMA (global_load_lds) instead of through registers
-#endif
-#ifndef SSC_ADMA
-#define SSC_ADMA 0       // gathered tiles of the launches without norm / activation by LDS-DMA too (buffer_load ... lds):
-                         // works, measured equal to the register path (1714-1720 images/s either way) -- off by default
-#endif
-#ifndef SSC_UT_SGB
-#define SSC_UT_SGB 1     // sched_group_barrier interleave hints in conv_ut_kernel (+1-2 % over the compiler's own order)
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // forward form
@@ -386,16 +376,13 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
     // lands at +16 L), no staging registers, no ds_write, no vector ALU work per K-tile.  A wave instruction covers
     // 256 / BN consecutive k rows of the [k][n] image (KN) or 8 rows of the swizzled [n][32] image (NK: each lane fetches the
     // 16-byte chunk whose swizzled position is its own slot).  Not with KMASK, whose partial chunks need zeroed rows.
-    constexpr bool BDMA = SSC_BDMA && !KMASK;
+    // (The gathered tile by LDS-DMA too, for the launches without norm / activation, measured equal to the register path --
+    // 1714-1720 images/s either way -- and is not kept.)
+    constexpr bool BDMA = !KMASK;
     constexpr int B_IPW = BK * BN / 1024;          // DMA instructions per wave and K-tile
-    // ADMA (launches without norm / activation on any source, i.e. every data gradient): the gathered tile too goes straight
-    // into LDS -- buffer_load_dwordx4 ... lds through a buffer descriptor per source, whose range check writes ZEROS for the
-    // lanes sent out of range (padding taps, rows beyond M): no mask, no staging registers, no ds_write.  The tile is the
-    // swizzled [row][32] image of the NK filter tile (8 rows per wave instruction).
-    constexpr bool ADMA = SSC_ADMA && BDMA && PLAIN && KM == 0;
-    constexpr bool AV = ADMA || UT_AV(BM, BN);
-    constexpr int A_LD = ADMA ? BK : (AV ? BK + 4 : BK + 1);
-    constexpr int A_SZ = BM * (UT_AV(BM, BN) ? BK + 4 : BK + 1);       // buffer size as the host allocates it (the ADMA image is smaller)
+    constexpr bool AV = UT_AV(BM, BN);
+    constexpr int A_LD = AV ? BK + 4 : BK + 1;
+    constexpr int A_SZ = BM * A_LD;
     // NK filters (k contiguous in memory): the B tile is [n][32] with the 16-byte chunk c of row n stored at chunk
     // c ^ ((n >> 1) & 7) -- b128 writes and b128 operand reads, both conflict-free, no padding (the scalar [n][33] image it
     // replaces cost 34 address adds per K-tile and wave)
@@ -495,11 +482,7 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
     bool a_mv[A_ROWS];
 #pragma unroll
     for (int i = 0; i < A_ROWS; ++i) {
-        // tile row and 16-byte chunk of this thread's i-th piece.  Register path: 32 rows per pass, chunk tid & 7.  ADMA: wave
-        // instruction w * A_ROWS + i covers 8 rows, lane L lands at slot L & 7 of row L >> 3 and so fetches the chunk whose
-        // swizzled position that is.
-        const int row = ADMA ? (wave * A_ROWS + i) * 8 + (lane >> 3) : (tid >> 3) + 32 * i;
-        const int a_col4 = ADMA ? ((lane & 7) ^ ((row >> 1) & 7)) : (tid & 7);
+        const int row = (tid >> 3) + 32 * i, col4 = tid & 7;        // tile row (32 rows per pass) and 16-byte chunk of this thread's i-th float4
         const long m = m0 + row;
         a_mv[i] = m < M;
         const long mm = a_mv[i] ? m : 0;
@@ -517,12 +500,12 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
         a_iyb[i] = py * d.in_stride + ph.ioff_y;
         a_ixb[i] = px * d.in_stride + ph.ioff_x;
         const int pix0 = (n * xH + a_iyb[i]) * xW + a_ixb[i];
-        a_off0[i] = (pix0 * xC0 + a_col4 * 4) * 4;      // BYTE offsets from a wave-uniform base: the loads then take the
-        a_off1[i] = (pix0 * xC1 + a_col4 * 4) * 4;      // scalar-base + 32-bit vector-offset form, no 64-bit address arithmetic
+        a_off0[i] = (pix0 * xC0 + col4 * 4) * 4;        // BYTE offsets from a wave-uniform base: the loads then take the
+        a_off1[i] = (pix0 * xC1 + col4 * 4) * 4;        // scalar-base + 32-bit vector-offset form, no 64-bit address arithmetic
         if ((tid & 7) == 0)
             rowpix[row] = ((long)n * d.OH + py * d.out_stride + ph.ooff_y) * d.OW + px * d.out_stride + ph.ooff_x;
     }
-    const int a_col4 = tid & 7;     // register path: chunk of this thread's float4s
+    const int a_col4 = tid & 7;     // chunk of this thread's float4s
     // filter offsets of this thread's float4 slots, split into the part along K (b_k: filter rows of the tile for KN,
     // element offset along the row for NK) and the rest (b_n), so that KMASK can drop the K part of an empty slot
     int b_k[B_SLOTS], b_n[B_SLOTS], b_kk[B_SLOTS];     // b_kk: k index inside the tile
@@ -581,7 +564,6 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
     float rbv[B_SLOTS];      // KMASK: 1.0 / 0.0 validity of each staged filter float4
 
     auto issue_loads = [&](int kt) {
-        if (ADMA) return;
         const int tap = div32(kt, mg.mC, mg.oneC);      // mC: magic of tpt
         const int chunk = kt - tap * tpt;
         const int ty = div32(tap, mg.mTW, mg.oneTW), tx = tap - ty * TWv;
@@ -633,30 +615,6 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
         }
     };
 
-    // ADMA: gathered K-tile kt straight into LDS buffer `buf`
-    const int a_px = d.NB * xH * xW;        // pixels of a source (host: pixels x channels < 2^29)
-    auto dma_a = [&](int kt, int buf) {
-        const int tap = div32(kt, mg.mC, mg.oneC);
-        const int chunk = kt - tap * tpt;
-        const int ty = div32(tap, mg.mTW, mg.oneTW), tx = tap - ty * TWv;
-        const bool first = chunk < nch0;
-        const int cs = first ? xC0 : xC1;
-        const int cc = (first ? chunk : chunk - nch0) * BK;
-        const int tapshift = (ty * xW + tx) * cs * 4;
-        const int fmask = first ? -1 : 0;
-        const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)((buf * A_SZ + wave * A_ROWS * 256) * 4));
-        // the descriptor of the source this K-tile reads (scalar ALU only): base, size in bytes = the range the check enforces
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(first ? xs0 : xs1), 0, a_px * cs * 4, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < A_ROWS; ++i) {
-            const int iy = a_iyb[i] + ty, ix = a_ixb[i] + tx;
-            const bool v = a_mv[i] & ((unsigned)iy < (unsigned)xH) & ((unsigned)ix < (unsigned)xW);
-            const int osel = (a_off0[i] & fmask) | (a_off1[i] & ~fmask);
-            const unsigned off = v ? (unsigned)(osel + tapshift) : 0x80000000u;     // out of range: the DMA writes zeros
-            glds16_buf(rs, off, (unsigned)(cc * 4), dst + i * 1024);
-        }
-    };
-
     // BDMA: filter K-tile kt straight into LDS buffer `buf`
     auto dma_b = [&](int kt, int buf) {
         const int tap = div32(kt, mg.mC, mg.oneC);
@@ -673,7 +631,6 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
     };
 
     auto stage = [&](int buf) {
-        if (ADMA) return;
         float* Ab = As + buf * A_SZ;
         float* Bb = Bs + buf * B_SZ;
 #pragma unroll
@@ -700,12 +657,11 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
 
     if (kt_begin < kt_end) {
         const int last = kt_end - 1;
-        if (ADMA) dma_a(kt_begin, 0);
         if (BDMA) dma_b(kt_begin, 0);
         issue_loads(kt_begin);
         stage(0);
         issue_loads(min(kt_begin + 1, last));
-        if (BDMA) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(ADMA ? 0 : A_ROWS) : "memory");   // the first DMA tile(s) have landed
+        if (BDMA) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(A_ROWS) : "memory");   // the first DMA tile has landed
         __syncthreads();
         int cur = 0;
         for (int kt = kt_begin; kt < kt_end; ++kt) {
@@ -713,13 +669,7 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
             // a lane's 16 operands of a K-tile contiguous in the [row][k] images)
             constexpr int KS = 1;                       // k stride between consecutive steps
             const int kl = lhi * (BK / 2);              // k of step 0
-            const float* Ab = As + cur * A_SZ + (wm * SM * 32 + l31) * A_LD + (ADMA ? 0 : kl);
-            // ADMA: every wave is past the barrier that ended K-tile kt-1, so buffer cur^1 is free: both tiles of K-tile kt+1
-            // are issued now and have this whole K step to land
-            if (ADMA) {
-                dma_a(min(kt + 1, last), cur ^ 1);
-                dma_b(min(kt + 1, last), cur ^ 1);
-            }
+            const float* Ab = As + cur * A_SZ + (wm * SM * 32 + l31) * A_LD + kl;
             const float* Bb = (BMODE == 0) ? (Bs + cur * B_SZ + kl * B_LD + wn * SN * 32 + l31)
                                            : (Bs + cur * B_SZ + (wn * SN * 32 + l31) * B_LD);
             const int bsw = (l31 >> 1) & 7;         // NK: chunk swizzle of this lane's rows (the same for every j)
@@ -729,8 +679,7 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
                 if (AV) {
 #pragma unroll
                     for (int i = 0; i < SM; ++i) {
-                        const float4 v = *reinterpret_cast<const float4*>(Ab + i * 32 * A_LD +
-                                                                          (ADMA ? ((lhi * 4 + g) ^ bsw) * 4 : g * FG));
+                        const float4 v = *reinterpret_cast<const float4*>(Ab + i * 32 * A_LD + g * FG);
                         av[buf][0][i] = v.x; av[buf][1][i] = v.y; av[buf][2][i] = v.z; av[buf][3][i] = v.w;
                     }
                 }
@@ -770,15 +719,14 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
             // the filter tile of K-tile kt+1 into the same free buffer; issued after the staging (whose wait on the register
             // loads would otherwise also wait for the DMA) and before the loads of K-tile kt+2 (so that the counted wait
             // at the end of the step can leave exactly those outstanding)
-            if (BDMA && !ADMA) dma_b(min(kt + 1, last), cur ^ 1);
+            if (BDMA) dma_b(min(kt + 1, last), cur ^ 1);
             fetch(2, 0);
             mfmas(1);
             issue_loads(min(kt + 2, last));         // K-tile kt+2 into the registers just drained
             fetch(3, 1);
             mfmas(2);
             mfmas(3);
-#if SSC_UT_SGB == 1
-            // interleave hint: one MFMA, then a few of the independent staging instructions
+            // interleave hint: one MFMA, then a few of the independent staging instructions (+1-2 % over the compiler's own order)
 #pragma unroll
             for (int q = 0; q < NFG * FG * SM * SN; ++q) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -787,13 +735,12 @@ __global__ __launch_bounds__(256) void conv_ut_kernel(const ssc_conv_desc d, con
                 __builtin_amdgcn_sched_group_barrier(0x004, 2, 0);
                 __builtin_amdgcn_sched_group_barrier(0x220, 1, 0);
             }
-#endif
             if (BDMA) {
                 // counted wait instead of __syncthreads(): its fence would wait vmcnt(0) and drain the register prefetch of
                 // K-tile kt+2 with the DMA.  vmcnt retires in order and the A_ROWS gather loads are the last vector-memory
                 // operations issued after the DMA on every path (the norm-table loads, when a source has a table, come before
                 // them): at most A_ROWS outstanding means the DMA has landed.  lgkmcnt(0): this wave's ds_writes of the A tile.
-                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(ADMA ? 0 : A_ROWS) : "memory");
+                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(A_ROWS) : "memory");
                 __builtin_amdgcn_s_barrier();
             } else {
                 __syncthreads();
@@ -919,13 +866,8 @@ __global__ __launch_bounds__(256) void slab_reduce4_stats_kernel(const float4* _
 }
 
 static bool slab_stats_ok(const ssc_conv_desc& d) {
-    static int off = -1;        // SSC_SLAB_STATS=0: statistics by a pass of their own after the slab sum (A/B)
-    if (off < 0) {
-        const char* e = ssc_dev_getenv("SSC_SLAB_STATS");
-        off = (e != nullptr && e[0] == '0') ? 1 : 0;
-    }
     const int cg = d.ldc / 4;
-    return !off && (d.ldc & 3) == 0 && cg >= 1 && cg <= 256 && (256 % cg) == 0 && d.Nn == d.ldc && d.Nstore == d.ldc &&
+    return (d.ldc & 3) == 0 && cg >= 1 && cg <= 256 && (256 % cg) == 0 && d.Nn == d.ldc && d.Nstore == d.ldc &&
            d.bias == nullptr && d.epi == 0 && !d.accumulate && ((uintptr_t)d.out & 15) == 0;
 }
 // rows of partial sums the statistics form of the slab sum writes (one per block)
@@ -1206,16 +1148,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const ssc_wgrad_desc d,
             fetch(3, 1);
             mfmas(2);
             mfmas(3);
-#if SSC_UT_SGB
 #pragma unroll
-            for (int q = 0; q < NFG * FG * SM * SN; ++q) {
+            for (int q = 0; q < NFG * FG * SM * SN; ++q) {      // interleave hint, as in conv_ut_kernel
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
                 __builtin_amdgcn_sched_group_barrier(0x004, 2, 0);
                 __builtin_amdgcn_sched_group_barrier(0x220, 1, 0);
             }
-#endif
             if (DDMA) {     // counted wait + bare barrier: the gathered loads of K-tile kt+2 stay in flight (conv_ut_kernel)
                 asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(A_SLOTS) : "memory");
                 __builtin_amdgcn_s_barrier();
@@ -1311,12 +1251,6 @@ static int wgrad_reduce_form(const float* ws, long count, int splitk, const floa
 }
 
 static void launch_wgrad_reduce(const float* ws, long count, int splitk, float* out, int accumulate, hipStream_t st) {
-    static int skip = -1;       // SSC_DIAG_SKIP_WGRAD_REDUCE=1: timing diagnostic only (wrong gradients): what do the slab sums cost
-    if (skip < 0) {
-        const char* e = ssc_dev_getenv("SSC_DIAG_SKIP_WGRAD_REDUCE");
-        skip = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
-    if (skip) return;
     switch (wgrad_reduce_form(ws, count, splitk, out)) {
         case 1: {
             const long c4 = count / 4;
@@ -1371,19 +1305,7 @@ static const TileCfg WG_CFGS[5] = {{0, 128, 128, 2, 1.00}, {1, 64, 128, 3, 1.00}
 // Makespan model of one launch: `blocks` equal workgroups of `w` MFMA-cycles each on ncu CUs that hold `res`
 // of them at a time and are matrix-pipe bound (co-resident workgroups share the pipe).  Split-K by s divides w
 // and multiplies the block count, at the price of writing + re-reading s partial copies of the output.
-// planner constants, overridable from the environment while tuning (read once)
-static double plan_const(const char* name, double dflt) {
-    static const char* names[16];
-    static double vals[16];
-    static int n = 0;
-    for (int i = 0; i < n; ++i)
-        if (names[i] == name) return vals[i];
-    const char* e = getenv(name);
-    const double v = (e != nullptr) ? atof(e) : dflt;
-    if (n < 16) { names[n] = name; vals[n] = v; ++n; }
-    return v;
-}
-
+// The planner's constants are developer switches while tuning (SSC_PLAN_*, read once).
 static double makespan(long blocks, double w, int res, int ncu) {
     const long slots = (long)ncu * res;
     const long full = blocks / slots, rem = blocks % slots;
@@ -1392,22 +1314,27 @@ static double makespan(long blocks, double w, int res, int ncu) {
     // ~25 % below 3 per CU at equal work)
     const long per_cu = (blocks + ncu - 1) / ncu;
     const long occ = per_cu < res ? per_cu : res;
-    if (occ <= 1) t *= plan_const("SSC_PLAN_OCC1", 1.30);
-    else if (occ == 2) t *= plan_const("SSC_PLAN_OCC2", 1.08);
+    static const double occ1 = ssc_dev_double("SSC_PLAN_OCC1", 1.30), occ2 = ssc_dev_double("SSC_PLAN_OCC2", 1.08);
+    if (occ <= 1) t *= occ1;
+    else if (occ == 2) t *= occ2;
     return t;
 }
 
+// cycles charged for the launch that sums split-K slabs
+static double plan_reduce_cost() {
+    static const double c = ssc_dev_double("SSC_PLAN_REDUCE", 6000.0);
+    return c;
+}
+
 struct Plan { int cfg; int splitk; double cost; long ts_full; int ts_s; };
+constexpr long TS_MAX_SLICES = 8;       // most in-launch K slices per tile of the tail split
 
 static Plan plan_launch(const TileCfg* cfgs, int ncfg, const bool* allowed, long M, long N, long nphase, long nkt,
                         long out_elems, int64_t ws_bytes, bool have_ws, bool can_ts = false, double cyc_scale = 1.0) {
     const int ncu = num_cu();
     Plan best = {-1, 1, 1e300, 0, 1};
-    static int force = -2;      // SSC_FWD_CFG=n: tuning aid, restricts the search to tile configuration n where allowed
-    if (force == -2) {
-        const char* e = getenv("SSC_FWD_CFG");
-        force = (e != nullptr) ? atoi(e) : -1;
-    }
+    // SSC_FWD_CFG=n (tests, tuning) restricts the search to tile configuration n where allowed
+    static const int force = [] { const char* e = getenv("SSC_FWD_CFG"); return e != nullptr ? atoi(e) : -1; }();
     for (int c = 0; c < ncfg; ++c) {
         if (!allowed[c]) continue;
         if (force >= 0 && c != force && allowed[force]) continue;
@@ -1420,7 +1347,7 @@ static Plan plan_launch(const TileCfg* cfgs, int ncfg, const bool* allowed, long
             const long per = (nkt + sk - 1) / sk;
             if ((nkt + per - 1) / per != sk) continue;      // would leave empty trailing splits
             double cost = makespan(blocks * sk, wfull * (double)per / (double)nkt, t.res, ncu) + 2500.0;
-            if (sk > 1) cost += 2.0 * sk * (double)out_elems * 4.0 / 1500.0 + plan_const("SSC_PLAN_REDUCE", 6000.0);   // slab traffic + reduce launch
+            if (sk > 1) cost += 2.0 * sk * (double)out_elems * 4.0 / 1500.0 + plan_reduce_cost();   // slab traffic + reduce launch
             const long bf = blocks;
             const int bs = 1;
             if (cost < best.cost) best = {c, sk, cost, bf, bs};
@@ -1436,12 +1363,14 @@ static Plan plan_launch(const TileCfg* cfgs, int ncfg, const bool* allowed, long
         const long blocks = ((M + t.BM - 1) / t.BM) * ((N + t.BN - 1) / t.BN) * nphase;
         long full = (blocks / ncu) * ncu, tail = blocks - full;
         long sl = 1;
-        static int ff = -2, fs = -2;        // tuning aid: SSC_TS_FORCE="whole tiles per CU,slices" pins the layout
-        if (ff == -2) {
+        struct TsForce { int full = -1, slices = -1; };
+        static const TsForce force_ts = [] {       // SSC_TS_FORCE="whole tiles per CU,slices" pins the layout (tests, tuning)
+            TsForce f;
             const char* e = getenv("SSC_TS_FORCE");
-            ff = fs = -1;
-            if (e != nullptr) sscanf(e, "%d,%d", &ff, &fs);
-        }
+            if (e != nullptr) sscanf(e, "%d,%d", &f.full, &f.slices);
+            return f;
+        }();
+        const int ff = force_ts.full, fs = force_ts.slices;
         if (ff >= 0 && fs >= 1) {
             full = (long)ff * ncu;
             if (full > blocks) full = (blocks / ncu) * ncu;
@@ -1449,8 +1378,7 @@ static Plan plan_launch(const TileCfg* cfgs, int ncfg, const bool* allowed, long
             sl = tail > 0 ? fs : 1;
         } else if (full > 0 && tail > 0 && tail * 4 <= (long)ncu * 3) {
             sl = (ncu + tail / 2) / tail;
-            const long smax = (long)plan_const("SSC_TS_MAXS", 8.0);
-            if (sl > smax) sl = smax;
+            if (sl > TS_MAX_SLICES) sl = TS_MAX_SLICES;
             while (sl > 1 && nkt / sl < 4) --sl;
         }
         if (sl > 1 && tail * sl < SSC_SK_FLAG_WORDS - 1 && (int64_t)tail * sl * t.BM * t.BN * 4 <= ws_bytes) {
@@ -1495,11 +1423,7 @@ static thread_local int64_t g_launch_ws_bytes = 0;
 static thread_local long g_launch_ts_full = 0;      // the planner's tail split: whole tiles, slices per remaining tile
 static thread_local int g_launch_ts_s = 1;
 static int tail_split_mode() {
-    static int mode = -1;
-    if (mode < 0) {
-        const char* e = ssc_dev_getenv("SSC_TAIL_SPLIT");
-        mode = (e != nullptr) ? atoi(e) : 1;
-    }
+    static const int mode = ssc_dev_int("SSC_TAIL_SPLIT", 1);
     return mode;
 }
 
@@ -1519,12 +1443,7 @@ static bool fwd_is_ut(const ssc_conv_desc& d) {
 
 // row-tap form (conv_ut_kernel<KM = 2>): plain single-source view, TW * C == 32, unflipped taps, vector filter loads
 static bool fwd_is_rowtap(const ssc_conv_desc& d) {
-    static int off = -1;
-    if (off < 0) {
-        const char* e = ssc_dev_getenv("SSC_ROWTAP");
-        off = (e != nullptr && e[0] == '0') ? 1 : 0;
-    }
-    return !off && d.bmode == 0 && d.nphase == 1 && d.kstep == 1 && d.kx0 == 0 && d.x.C1 == 0 && d.TW * d.x.C0 == BK &&
+    return d.bmode == 0 && d.nphase == 1 && d.kstep == 1 && d.kx0 == 0 && d.x.C1 == 0 && d.TW * d.x.C0 == BK &&
            d.TW == d.KW && d.k_real == d.x.C0 && d.wC0 == d.x.C0 && fwd_is_vec(d) && d.x.ab0 == nullptr &&
            d.x.act == SSC_ACT_NONE && (long)d.NB * d.x.H * d.x.W * d.x.C0 < 0x1fffffffL &&
            (long)d.KH * d.KW * d.wC0 * d.wC1 < 0x1fffffffL;
@@ -1536,29 +1455,17 @@ static bool fwd_is_utg(const ssc_conv_desc& d) {
     const bool vec = fwd_is_vec(d);
     const int C = d.x.C0 + d.x.C1;
     const int padded = ((d.x.C0 + BK - 1) / BK + (d.x.C1 + BK - 1) / BK) * BK;
-    static int off = -1;
-    if (off < 0) {
-        const char* e = ssc_dev_getenv("SSC_UTG");
-        off = (e != nullptr && e[0] == '0') ? 1 : 0;
-    }
-    static double waste = -1.0;     // SSC_UTG_WASTE: largest padded / real K width taken (tuning aid)
-    if (waste < 0.0) {
-        const char* e = ssc_dev_getenv("SSC_UTG_WASTE");
-        waste = (e != nullptr) ? atof(e) : 1.5;     // measured 1.2 / 1.25 / 1.5: MRU train 258.9 / 257.8 / 256.9 ms, MRU forward 13.47 / - / 13.20 ms
-    }
+    // largest padded / real K width taken.  Measured 1.2 / 1.25 / 1.5: MRU train 258.9 / 257.8 / 256.9 ms, MRU forward 13.47 / - / 13.20 ms
+    constexpr double waste = 1.5;
     // ... or no more K-tiles than the generic kernel's walk over taps * C would take (few channels: one chunk per tap either way)
     const long kt_chunks = (long)d.TH * d.TW * (padded / BK), kt_flat = ((long)d.TH * d.TW * C + BK - 1) / BK;
-    return !off && vec && d.k_real >= 1 && d.k_real <= C && ((double)padded <= waste * (double)C || kt_chunks <= kt_flat) &&
+    return vec && d.k_real >= 1 && d.k_real <= C && ((double)padded <= waste * (double)C || kt_chunks <= kt_flat) &&
            (long)d.NB * d.x.H * d.x.W * (d.x.C0 > d.x.C1 ? d.x.C0 : d.x.C1) < 0x1fffffffL &&
            (long)d.KH * d.KW * d.wC0 * d.wC1 < 0x1fffffffL;
 }
 
 static int xcd_order() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = ssc_dev_getenv("SSC_XCD_ORDER");
-        on = (e != nullptr) ? atoi(e) : 2;     // 0: off, 1: XCD-aware order, 2: + the 4 phases of a row tile adjacent
-    }
+    static const int on = ssc_dev_int("SSC_XCD_ORDER", 2);      // 0: off, 1: XCD-aware order, 2: + the 4 phases of a row tile adjacent
     return on;
 }
 
@@ -1638,17 +1545,12 @@ static int launch_fwd(const ssc_conv_desc& d, int splitk, float* ws, hipStream_t
 // bf16-split form (igemm_bf16.hip): the caller supplied the filter's planes, every K-tile lies inside one tap and one source,
 // the column range starts at a 32-column block.  SSC_ARITH=fp32 keeps everything on the exact-fp32 MFMA.
 static bool fwd_is_bf(const ssc_conv_desc& d) {
-    static int off = -1;
-    if (off < 0) {
-        const char* e = getenv("SSC_ARITH");
-        off = (e != nullptr && (e[0] == 'f' || e[0] == 'F')) ? 1 : 0;
-    }
     // ... or ONE source whose channel count is any multiple of 4 above 32 (MRU's materialised concats: state + image channels),
     // the partly empty last chunk of every tap masked in the staging (conv_bf_kernel<KM>); the planes pad k >= K with zeros
     const bool km = d.x.C1 == 0 && (d.x.C0 & 3) == 0 && d.x.C0 > BK && (d.x.C0 % BK) != 0 && d.k_real >= 1 && d.k_real <= d.x.C0 &&
                     d.ws_kc == 2 * ((d.x.C0 + BK - 1) / BK) && (long)d.NB * d.x.H * d.x.W * d.x.C0 < 0x1fffffffL &&
                     (long)d.KH * d.KW * d.wC0 * d.wC1 < 0x1fffffffL;
-    return !off && d.wsplit != nullptr && d.ws_kc > 0 && d.ws_nbp > 0 && (fwd_is_ut(d) || km) && (d.n_off & 31) == 0 && d.Nstore > 32 &&
+    return !ssc_arith_fp32() && d.wsplit != nullptr && d.ws_kc > 0 && d.ws_nbp > 0 && (fwd_is_ut(d) || km) && (d.n_off & 31) == 0 && d.Nstore > 32 &&
            d.TH * d.TW <= 32;
 }
 
@@ -1667,6 +1569,8 @@ static Plan plan_fwd(const ssc_conv_desc& d, int64_t ws_bytes, bool have_ws) {
     if (fwd_is_bf(d)) {
         const bool allowed_bf[5] = {d.Nstore > 64, d.Nstore > 64, true, false, true};
         // six bf16 passes = 6/16 of the fp32 MFMA's cycles; the staging beside them and the shorter K steps make it ~0.45
+        constexpr double BF_SCALE = 0.45;
+        static const double hk_min = ssc_dev_double("SSC_PLAN_BF_HK_MIN", 0.5), hk_penalty = ssc_dev_double("SSC_PLAN_BF_HK", 0.78);
         // 128 x 128 on 16-k stages (round 6): two workgroups per CU, measured 3-10 % ahead of 64 x 128 on launches of whole
         // rounds (d4 +9.5 %, dec3 +6.5 %, enc2 +6 %); the uniform form only (the partial-chunk launches keep the 32-k kernel)
         TileCfg cfgs[5];
@@ -1681,19 +1585,19 @@ static Plan plan_fwd(const ssc_conv_desc& d, int64_t ws_bytes, bool have_ws) {
             // inference at batch 16 1.325 / 1.300 / 1.300 / 1.308 / 1.293 ms, Background train step 22.3 / 21.8 / 22.1 / 22.1 / 22.0,
             // Pix2Pix train step 12.35 / 12.38 / 12.54 / 12.84 / 12.90, MRU 183.9 / 183.6 / 182.9 / 184.0 / 190.2
             const long t128 = ((M + 127) / 128) * ((d.Nstore + 127) / 128) * d.nphase;
-            if ((double)t128 < plan_const("SSC_PLAN_BF_HK_MIN", 0.5) * 2.0 * num_cu()) {
+            if ((double)t128 < hk_min * 2.0 * num_cu()) {
                 return plan_launch(cfgs, 5, allowed_bf, M, d.Nstore, d.nphase, nkt, (long)d.NB * d.OH * d.OW * d.ldc, ws_bytes,
-                                   have_ws, can_ts, plan_const("SSC_PLAN_BF_SCALE", 0.45));
+                                   have_ws, can_ts, BF_SCALE);
             }
             cfgs[0].res = 2;
             // 0.78: swept on the train steps (scripts/hk_plan_sweep.sh): Pix2Pix 12.57 -> 12.2 ms between 0.86 and 0.78 (the tile then
             // takes most whole-round launches), MRU / Residual / Background flat from 0.62 to 0.86
-            cfgs[0].penalty = plan_const("SSC_PLAN_BF_HK", 0.78);
+            cfgs[0].penalty = hk_penalty;
             // the partial-chunk form walks ceil(C / 16) chunks of 16 per tap there, 2 * ceil(C / 32) on the 32-k tiles
             if (!fwd_is_ut(d)) cfgs[0].penalty *= (double)((d.x.C0 + 15) / 16) / (double)(2 * ((d.x.C0 + 31) / 32));
         }
         return plan_launch(cfgs, 5, allowed_bf, M, d.Nstore, d.nphase, nkt, (long)d.NB * d.OH * d.OW * d.ldc, ws_bytes,
-                           have_ws, can_ts, plan_const("SSC_PLAN_BF_SCALE", 0.45));
+                           have_ws, can_ts, BF_SCALE);
     }
     return plan_launch(FWD_CFGS, 5, allowed, M, d.Nstore, d.nphase, nkt, (long)d.NB * d.OH * d.OW * d.ldc, ws_bytes,
                        have_ws, can_ts);
@@ -1774,18 +1678,13 @@ extern "C" int ssc_conv_forward_bn(const ssc_conv_desc* dp, float* ws, int64_t w
     d.stat_mode = 0;
     const long M = (long)d.NB * d.PH * d.PW;
     const long Mall = M * d.nphase;
-    static int off = -1;        // SSC_FUSE_STATS=0: always the separate pass (A/B)
-    if (off < 0) {
-        const char* e = ssc_dev_getenv("SSC_FUSE_STATS");
-        off = (e != nullptr && e[0] == '0') ? 1 : 0;
-    }
     bool fused = false;
     int64_t ws_conv = ws_bytes;
     // (the streaming kernels are dispatched BEHIND the one-output head, the few-output and the few-channel kernels in
     // ssc_conv_forward: a descriptor those take must not be promised rows only a streaming kernel writes)
     const bool earlier = ssc_head1_forward_supported(dp) || ssc_head1_dgrad_supported(dp) || ssc_conv_narrow_supported(dp) ||
                          ssc_conv_fewchan_supported(dp);
-    if (!off && !earlier && ws != nullptr && d.Nstore == d.ldc &&
+    if (!earlier && ws != nullptr && d.Nstore == d.ldc &&
         (ssc_conv_pw1x1_supported(&d) || ssc_conv_c3x3_supported(&d) || ssc_conv_s2n16_supported(&d) ||
          ssc_conv_tr4_tiny_supported(&d) || ssc_conv_fewchan7_supported(&d) || ssc_conv_tr4n16_supported(&d))) {
         // the streaming kernels take the statistics as per-lane sums over the tiles a workgroup walks: one row per walker
@@ -1805,7 +1704,7 @@ extern "C" int ssc_conv_forward_bn(const ssc_conv_desc* dp, float* ws, int64_t w
     const bool streaming = ssc_conv_pw1x1_supported(&d) || ssc_conv_c3x3_supported(&d) || ssc_conv_s2n16_supported(&d) ||
                            ssc_conv_tr4_tiny_supported(&d) || ssc_conv_fewchan7_supported(&d) ||
                            ssc_conv_tr4n16_supported(&d);     // rows per walker, not per tile
-    if (!off && !streaming && ws != nullptr && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && d.epi == 0 &&
+    if (!streaming && ws != nullptr && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && d.epi == 0 &&
         !d.accumulate && d.Nstore == d.ldc && ((d.Nstore & 3) == 0) && ((reinterpret_cast<unsigned long>(d.out) & 15) == 0) &&
         (fwd_is_ut(d) || fwd_is_utg(d) || (d.bmode == 0 && fwd_is_rowtap(d)))) {
         const Plan p = plan_fwd(d, ws_bytes, true);
@@ -1829,7 +1728,7 @@ extern "C" int ssc_conv_forward_bn(const ssc_conv_desc* dp, float* ws, int64_t w
     }
     // split-K launches (few rows, long K: the bottlenecks' 3x3 / 4x4 convs at the low resolutions, encoder_5): the statistics ride
     // in the slab sum (slab_reduce4_stats_kernel) -- slab sum + fold instead of slab sum + statistics pass + fold
-    if (!off && !streaming && ws != nullptr && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && slab_stats_ok(d) &&
+    if (!streaming && ws != nullptr && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && slab_stats_ok(d) &&
         !(ssc_head1_forward_supported(dp) || ssc_head1_dgrad_supported(dp))) {
         const Plan p = plan_fwd(d, ws_bytes, true);
         if (p.cfg >= 0 && p.splitk > 1 && p.ts_s <= 1) {
@@ -1847,19 +1746,6 @@ extern "C" int ssc_conv_forward_bn(const ssc_conv_desc* dp, float* ws, int64_t w
         }
     }
     (void)fused;
-    {
-        static int dbg = -1;        // SSC_DEBUG_BNPATH=1: why a conv + norm call took the separate statistics pass (stderr)
-        if (dbg < 0) {
-            const char* e = ssc_dev_getenv("SSC_DEBUG_BNPATH");
-            dbg = (e != nullptr && e[0] == '1') ? 1 : 0;
-        }
-        if (dbg) {
-            const Plan p = plan_fwd(d, ws_bytes, ws != nullptr);
-            fprintf(stderr, "bnpath separate: M=%ld N=%d K=%d ut=%d utg=%d narrow=%d fewchan=%d cfg=%d splitk=%d epi=%d acc=%d\n", M * d.nphase,
-                    d.Nstore, d.TH * d.TW * (d.x.C0 + d.x.C1), (int)fwd_is_ut(d), (int)fwd_is_utg(d), ssc_conv_narrow_supported(dp),
-                    ssc_conv_fewchan_supported(dp), p.cfg, p.splitk, d.epi, d.accumulate);
-        }
-    }
     const int rc = ssc_conv_forward(&d, ws, ws_bytes, stream);
     if (rc != 0) return rc;
     return ssc_bn_stats(d.out, Mall, d.Nstore, d.ldc, scale, offset, eps, ab, stats, ws, ws_bytes, stream);
@@ -1879,14 +1765,9 @@ extern "C" int ssc_conv_forward_bnbwd(const ssc_conv_desc* dp, float* ws, int64_
     d.stat_mode = 0;
     *nrows = 0;
     const long M = (long)d.NB * d.PH * d.PW;
-    static int off = -1;        // SSC_FUSE_BNBWD=0: always the separate pass (A/B)
-    if (off < 0) {
-        const char* e = ssc_dev_getenv("SSC_FUSE_BNBWD");
-        off = (e != nullptr && e[0] == '0') ? 1 : 0;
-    }
     const bool earlier = ssc_head1_forward_supported(dp) || ssc_head1_dgrad_supported(dp) || ssc_conv_narrow_supported(dp) ||
                          ssc_conv_fewchan_supported(dp);        // dispatched in front of the streaming kernels
-    if (!off && !earlier && partial != nullptr && x != nullptr && ab != nullptr && stats != nullptr && d.Nstore == d.ldc &&
+    if (!earlier && partial != nullptr && x != nullptr && ab != nullptr && stats != nullptr && d.Nstore == d.ldc &&
         (ssc_conv_c3x3_supported(&d) || ssc_conv_s2n16_supported(&d))) {
         // streaming kernels: the two sums as per-lane sums, one row per walker
         const int nblk = ssc_conv_c3x3_supported(&d) ? ssc_conv_c3x3_walkers(&d) : ssc_conv_s2n16_walkers(&d);
@@ -1897,7 +1778,7 @@ extern "C" int ssc_conv_forward_bnbwd(const ssc_conv_desc* dp, float* ws, int64_
             return ssc_conv_forward(&d, ws, ws_bytes, stream);
         }
     }
-    if (!off && ws != nullptr && partial != nullptr && x != nullptr && ab != nullptr && stats != nullptr &&
+    if (ws != nullptr && partial != nullptr && x != nullptr && ab != nullptr && stats != nullptr &&
         !ssc_conv_c3x3_supported(&d) && !ssc_conv_s2n16_supported(&d) && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && d.epi == 0 && !d.accumulate &&
         d.bias == nullptr && d.Nstore == d.ldc &&
         d.Nn == d.Nstore && ((d.Nstore & 3) == 0) && ((ldx & 3) == 0) && ((reinterpret_cast<unsigned long>(d.out) & 15) == 0) &&
@@ -1931,12 +1812,7 @@ extern "C" int ssc_conv_forward_minmax(const ssc_conv_desc* dp, float* ws, int64
     d.stat_mode = 0;
     const long P = (long)d.PH * d.PW;
     const long M = (long)d.NB * P;
-    static int off = -1;        // SSC_FUSE_MINMAX=0: always the separate pass (A/B)
-    if (off < 0) {
-        const char* e = ssc_dev_getenv("SSC_FUSE_MINMAX");
-        off = (e != nullptr && e[0] == '0') ? 1 : 0;
-    }
-    if (!off && ws != nullptr && d.nphase == 1 && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) &&
+    if (ws != nullptr && d.nphase == 1 && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) &&
         (d.epi == 0 || d.epi == 2) && !d.accumulate && d.Nstore == d.ldc && d.Nn == d.Nstore && ((d.Nstore & 3) == 0) &&
         ((reinterpret_cast<unsigned long>(d.out) & 15) == 0) && (fwd_is_ut(d) || fwd_is_utg(d))) {
         const Plan p = plan_fwd(d, ws_bytes, true);
@@ -1970,13 +1846,8 @@ extern "C" int ssc_conv_forward_bnbwd2(const ssc_conv_desc* dp, float* ws, int64
     d.stat_mode = 0;
     *nrows = 0;
     const long M = (long)d.NB * d.PH * d.PW;
-    static int off = -1;        // SSC_FUSE_BNBWD=0: always the separate pass (A/B)
-    if (off < 0) {
-        const char* e = ssc_dev_getenv("SSC_FUSE_BNBWD");
-        off = (e != nullptr && e[0] == '0') ? 1 : 0;
-    }
     const int C1 = d.Nstore - C0;
-    if (!off && ws != nullptr && s0 != nullptr && s1 != nullptr && s0->x && s1->x && s0->ab && s1->ab && s0->stats && s1->stats &&
+    if (ws != nullptr && s0 != nullptr && s1 != nullptr && s0->x && s1->x && s0->ab && s1->ab && s0->stats && s1->stats &&
         s0->partial && s1->partial && C0 > 0 && C1 > 0 && (C0 % 128) == 0 && (C1 & 3) == 0 &&
         !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && d.epi == 0 && !d.accumulate &&
         d.bias == nullptr && d.Nstore == d.ldc && d.Nn == d.Nstore && ((s0->ldx | s1->ldx) & 3) == 0 &&
@@ -2138,14 +2009,10 @@ static int launch_wgrad_v(const ssc_wgrad_desc& d, int splitk, float* ws, hipStr
         if (arc != 0) return arc;
     }
     dim3 grid((unsigned)mt, (unsigned)nt, (unsigned)splitk);
-    // SSC_WG_XCD=1: whole K slices per XCD.  Measured (scripts/wg_xcd_ab.sh): FETCH_SIZE of the encoder_3 filter gradient 113 ->
+    // SSC_WG_XCD=1 (developer switch): whole K slices per XCD.  Measured (scripts/wg_xcd_ab.sh): FETCH_SIZE of the encoder_3 filter gradient 113 ->
     // 35 MB, the launch itself unchanged (94.5 vs 94.9 TFLOP/s), the train step 0.4 % SLOWER (18.05 vs 17.98 ms) -- the re-reads
     // of the plain order are served by the Infinity Cache while all XCDs walk the same pixel range -- so it stays off
-    static int wg_xcd = -1;
-    if (wg_xcd < 0) {
-        const char* e = ssc_dev_getenv("SSC_WG_XCD");
-        wg_xcd = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
+    static const int wg_xcd = ssc_dev_int("SSC_WG_XCD", 0);
     const int xcd = (wg_xcd && splitk > 1 && (((long)mt * nt * splitk) & 7) == 0) ? 1 : 0;
     hipLaunchKernelGGL((conv_wgrad_kernel<WM, WN, SM, SN, GPLAIN, DPLAIN, DDMA>), grid, dim3(256), lds, st, d, mg, ws, out_count,
                        splitk, xcd);
@@ -2156,13 +2023,9 @@ static int launch_wgrad_v(const ssc_wgrad_desc& d, int splitk, float* ws, hipStr
 // the view form (GPLAIN, DPLAIN, DDMA) of a launch: 0 TTT, 1 FTT, 2 TTF, 3 FTF, 4 FFF
 static int wgrad_view_form(const ssc_wgrad_desc& d) {
     const bool gp = gview_plain(d.g), dp = gview_plain(d.d);
-    static int ddma_on = -1;       // SSC_WGRAD_DMA=0: dense tiles through registers (A/B)
-    if (ddma_on < 0) {
-        const char* e = ssc_dev_getenv("SSC_WGRAD_DMA");
-        ddma_on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
+    static const int ddma_on = ssc_dev_int("SSC_WGRAD_DMA", 1);       // 0: dense tiles through registers (A/B)
     // LDS-DMA of the dense tile: one plain tensor whose byte offsets fit 32 bits
-    const bool ddma = SSC_BDMA && ddma_on && dp && d.d.C1 == 0 && (long)d.NB * d.PH * d.PW * d.d.C0 < 0x1fffffffL;
+    const bool ddma = ddma_on && dp && d.d.C1 == 0 && (long)d.NB * d.PH * d.PW * d.d.C0 < 0x1fffffffL;
     if (dp && ddma) return gp ? 0 : 1;
     if (dp) return gp ? 2 : 3;
     return 4;       // the full transform covers a plain side
@@ -2194,13 +2057,7 @@ static Plan plan_wgrad(const ssc_wgrad_desc& d, int64_t ws_bytes, bool have_ws) 
     allowed[4] = d.Nn <= 32;
     const int ncu = num_cu();
     Plan best = {-1, 1, 1e300, 0, 1};
-    static int force_cfg = -2, force_sk = -2;       // SSC_WG_CFG / SSC_WG_SPLITK: tuning aids
-    if (force_cfg == -2) {
-        const char* e = ssc_dev_getenv("SSC_WG_CFG");
-        force_cfg = (e != nullptr) ? atoi(e) : -1;
-        e = ssc_dev_getenv("SSC_WG_SPLITK");
-        force_sk = (e != nullptr) ? atoi(e) : -1;
-    }
+    static const int force_cfg = ssc_dev_int("SSC_WG_CFG", -1);        // restricts the search to tile configuration n where allowed
     for (int c = 0; c < 5; ++c) {
         if (!allowed[c]) continue;
         if (force_cfg >= 0 && c != force_cfg && allowed[force_cfg]) continue;
@@ -2213,8 +2070,7 @@ static Plan plan_wgrad(const ssc_wgrad_desc& d, int64_t ws_bytes, bool have_ws) 
             const long per = (nkt + sk - 1) / sk;
             if ((nkt + per - 1) / per != sk) continue;
             double cost = makespan(blocks * sk, wfull * (double)per / (double)nkt, t.res, ncu) + 2500.0;
-            if (sk > 1) cost += 2.0 * sk * (double)out_elems * 4.0 / 1500.0 + plan_const("SSC_PLAN_REDUCE", 6000.0);
-            if (force_sk > 0) cost = (double)(sk > force_sk ? sk - force_sk : force_sk - sk);     // nearest legal split
+            if (sk > 1) cost += 2.0 * sk * (double)out_elems * 4.0 / 1500.0 + plan_reduce_cost();
             if (cost < best.cost) best = {c, (int)sk, cost, 0, 1};
         }
     }

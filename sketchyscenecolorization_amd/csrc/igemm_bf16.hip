@@ -1178,11 +1178,7 @@ static bool bf_tabs(const ssc_conv_desc& d, BfTabs& t) {
 // ---- the choices of a launch: the launchers below and ssc_conv_bf_plan (igemm.hip, through ssc_conv_bf_form) both ask these ----
 // SSC_BF_DIAG bit 0: no in-launch K slices (plain tiles), bit 1: no XCD-aware order (diagnostics; the 32-k kernel only)
 static int bf_diag() {
-    static int diag = -1;
-    if (diag < 0) {
-        const char* e = ssc_dev_getenv("SSC_BF_DIAG");
-        diag = e != nullptr ? atoi(e) : 0;
-    }
+    static const int diag = ssc_dev_int("SSC_BF_DIAG", 0);
     return diag;
 }
 // the K-tile order: 2 the four parity classes of a stride-2 walk over an even tap window, 1 tap by tap, 0 a single tap.
@@ -1190,11 +1186,7 @@ static int bf_diag() {
 static int bf_korder(const ssc_conv_desc& d, bool pinnable) {
     int kord = -1;
     if (pinnable) {
-        static int env = -2;
-        if (env == -2) {
-            const char* e = ssc_dev_getenv("SSC_BF_KORDER");
-            env = e != nullptr ? atoi(e) : -1;
-        }
+        static const int env = ssc_dev_int("SSC_BF_KORDER", -1);
         kord = env;
     }
     const bool par_ok = d.in_stride == 2 && (d.TH & 1) == 0 && (d.TW & 1) == 0;
@@ -1318,12 +1310,8 @@ static int launch_bf_form(bool plain, bool one, bool km, const ssc_conv_desc& d,
 // the 128 x 128 tile runs on 16-k stages (conv_bfh_kernel) unless SSC_BF_HK=0 under SSC_DEV_SWITCHES (A/B: round 5's 32-k form);
 // the planner prices the tile accordingly (igemm.hip: plan_fwd)
 bool ssc_bf_hk_enabled() {
-    static int hk_env = -2;
-    if (hk_env == -2) {
-        const char* e = ssc_dev_getenv("SSC_BF_HK");
-        hk_env = e != nullptr ? (e[0] == '1' ? 1 : 0) : -1;
-    }
-    return hk_env != 0;
+    static const int hk = ssc_dev_int("SSC_BF_HK", 1);
+    return hk != 0;
 }
 
 // the instantiation of a launch: one source (ONE), its partly empty last chunk masked (KM), one LDS stage per operand (SS: the
@@ -1334,11 +1322,7 @@ static bool bf_form(int cfg, const ssc_conv_desc& d, BfForm& f) {
     f.km = f.one && (d.x.C0 % BK) != 0;
     // one LDS stage per operand (64x128 / 128x64 / 64x64 tiles) when the caller says the launch shares the chip with other streams'
     // launches (ssc_conv_desc.lds_hint); SSC_BF_SS=0 / 1 under SSC_DEV_SWITCHES pins it (A/B)
-    static int ss_env = -2;
-    if (ss_env == -2) {
-        const char* e = ssc_dev_getenv("SSC_BF_SS");
-        ss_env = e != nullptr ? (e[0] == '1' ? 1 : 0) : -1;
-    }
+    static const int ss_env = ssc_dev_int("SSC_BF_SS", -1);
     f.ss = cfg != 0 && (ss_env >= 0 ? ss_env == 1 : (d.lds_hint & 1) != 0);
     f.hk = cfg == 0 && ssc_bf_hk_enabled();
     f.BM = (cfg == 0 || cfg == 2) ? 128 : 64;

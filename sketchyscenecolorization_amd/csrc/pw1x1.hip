@@ -157,19 +157,9 @@ __global__ __launch_bounds__(256) void pw1x1_kernel(const ssc_conv_desc d, long 
     }
 }
 
-static bool pw_on() {
-    static int on = -1;         // SSC_PW1X1=0: the tile kernel (A/B)
-    if (on < 0) {
-        const char* e = ssc_dev_getenv("SSC_PW1X1");
-        on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    return on != 0;
-}
-
 extern "C" int ssc_conv_pw1x1_supported(const ssc_conv_desc* dp) {
     const ssc_conv_desc& d = *dp;
     const int K = d.x.C0;
-    if (!pw_on()) return 0;
     if (d.x.C1 != 0 || (K != 16 && K != 32 && K != 64 && K != 128) || d.k_real != K || d.wC0 != K) return 0;
     if (d.nphase != 1 || d.TH != 1 || d.TW != 1 || d.KH != 1 || d.KW != 1 || d.in_stride != 1 || d.ioff_y != 0 || d.ioff_x != 0 ||
         d.bmode != 0 || d.out_stride != 1 || d.ooff_y != 0 || d.ooff_x != 0)

@@ -182,18 +182,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
     }
 }
 
-static bool s2_on() {
-    static int on = -1;         // SSC_S2N16=0: the tile kernel (A/B)
-    if (on < 0) {
-        const char* e = ssc_dev_getenv("SSC_S2N16");
-        on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    return on != 0;
-}
-
 extern "C" int ssc_conv_s2n16_supported(const ssc_conv_desc* dp) {
     const ssc_conv_desc& d = *dp;
-    if (!s2_on()) return 0;
     if (d.x.C1 != 0 || d.x.C0 != S2_C || d.k_real != S2_C || d.wC0 != S2_C) return 0;
     if (d.nphase != 1 || d.TH != 4 || d.TW != 4 || d.KH != 4 || d.KW != 4 || (d.in_stride != 1 && d.in_stride != 2) || d.ioff_y != -1 || d.ioff_x != -1 ||
         d.out_stride != 1 || d.ooff_y != 0 || d.ooff_x != 0 || d.bmode != 0 || d.ky0 != 0 || d.kx0 != 0 || d.kstep != 1)

@@ -719,11 +719,7 @@ extern "C" int ssc_lstm_step_fwd_bf(const float* h_in, const void* hp_in, const 
     // 64 x 64 tiles (two blocks of 8 units per workgroup) from 1152 workgroups of the 64 x 32 grid on (4.5 per CU).  Measured
     // (scripts/lstm_ub_ab.sh, us per step 64x32 -> 64x64): C = 512: 576 rows 23.9 -> 25.7, 1152 rows 39.7 -> 38.4, 2304 rows 91.5 -> 72.7;
     // C = 1024: 576 rows 57.5 -> 56.2, 2304 rows 312 -> 192, 4608 rows 598 -> 383
-    static int ub_env = -2;     // SSC_LSTM_UB=1 / 2 pins the tile (A/B)
-    if (ub_env == -2) {
-        const char* e = ssc_dev_getenv("SSC_LSTM_UB");
-        ub_env = e != nullptr ? atoi(e) : -1;
-    }
+    static const int ub_env = ssc_dev_int("SSC_LSTM_UB", -1);       // 1 / 2 pins the tile (A/B)
     const long wgs1 = ((rows + 63) / 64) * (C / 8);
     const int ub = ((C / 8) & 1) ? 1 : (ub_env == 1 || ub_env == 2 ? ub_env : (wgs1 >= 1152 ? 2 : 1));
     const dim3 grid((unsigned)(wgs1 / ub));
@@ -741,15 +737,10 @@ extern "C" int ssc_lstm_step_fwd(const float* h_in, const float* Kh, int ldk, co
                                  const int* mask, int mdiv, const float* c_in, int64_t rows, int C, int with_gemm,
                                  float* c_out, float* h_out, float* acts, void* stream) {
     if ((C & 31) || (ldk & 3) || rows <= 0 || rows > 0x7fffffffL / (4L * C)) return -1;
-    // few rows: the K-split form while the plain grid holds under ~4.5 workgroups per CU (SSC_LSTM_K2=0 / 1 pins it).  Measured:
+    // few rows: the K-split form while the plain grid holds under ~4.5 workgroups per CU.  Measured:
     // batch 16 (576 rows) generator forward 9080 -> 9390 images/s; batch 32 (1152 rows) train step 17.96 -> 17.88 ms
-    static int k2 = -2;
-    if (k2 == -2) {
-        const char* e = ssc_dev_getenv("SSC_LSTM_K2");
-        k2 = (e == nullptr) ? -1 : atoi(e);
-    }
     const long wgs = ((rows + 63) / 64) * (C / 16);
-    const bool use_k2 = with_gemm && (C % 128) == 0 && (k2 == 1 || (k2 == -1 && wgs < 1200));     // its loads run 4 K tiles ahead
+    const bool use_k2 = with_gemm && (C % 128) == 0 && wgs < 1200;     // its loads run 4 K tiles ahead
     if (use_k2)
         hipLaunchKernelGGL(lstm_step_fwd_k2_kernel, dim3((unsigned)(((rows + 63) / 64) * (C / 8))), dim3(256), 0,
                            (hipStream_t)stream, h_in, Kh, ldk, g1, g2, div2 > 0 ? div2 : 1, mask, mdiv > 0 ? mdiv : 1, c_in,

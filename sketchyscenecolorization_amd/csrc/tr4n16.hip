@@ -165,18 +165,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     }
 }
 
-static bool t16_on() {
-    static int on = -1;         // SSC_TR4N16=0: the tile kernel (A/B)
-    if (on < 0) {
-        const char* e = ssc_dev_getenv("SSC_TR4N16");
-        on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    return on != 0;
-}
-
 extern "C" int ssc_conv_tr4n16_supported(const ssc_conv_desc* dp) {
     const ssc_conv_desc& d = *dp;
-    if (!t16_on()) return 0;
     if (d.nphase != 4 || d.TH != 2 || d.TW != 2 || d.KH != 4 || d.KW != 4 || d.bmode != 1 || d.out_stride != 2 || d.in_stride != 1 ||
         d.ky0 != 0 || d.kx0 != 0 || d.kstep != -2 || d.ioff_y != 0 || d.ioff_x != 0 || d.ooff_y != 0 || d.ooff_x != 0)
         return 0;

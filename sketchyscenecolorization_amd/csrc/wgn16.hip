@@ -225,18 +225,8 @@ __global__ __launch_bounds__(256) void wgn16_reduce_kernel(const float* __restri
     }
 }
 
-static bool wg16_on() {
-    static int on = -1;         // SSC_WGN16=0: the general filter-gradient kernel (A/B)
-    if (on < 0) {
-        const char* e = ssc_dev_getenv("SSC_WGN16");
-        on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    return on != 0;
-}
-
 // 3: the 3x3 form, 4: the 4x4 form, 0: not this kernel's
 static int wg16_form(const ssc_wgrad_desc& d) {
-    if (!wg16_on()) return 0;
     if (d.g.C1 != 0 || d.d.C1 != 0 || d.in_stride != 1 || d.ioff_y != -1 || d.ioff_x != -1) return 0;
     if (d.Nn < 4 || d.Nn > 16 || (d.Nn & 3) != 0 || d.d.C0 < d.Nn || d.ldc != d.Nn) return 0;
     if (d.g.H != d.PH || d.g.W != d.PW || d.d.H != d.PH || d.d.W != d.PW) return 0;

@@ -26,10 +26,7 @@
 #include "host_util.h"
 #include <type_traits>
 
-#ifndef SSC_WG128_BK
-#define SSC_WG128_BK 32    // pixels per K step: 32 (68 KB of LDS, two workgroups per CU) or 16 (36 KB)
-#endif
-#define BK SSC_WG128_BK
+#define BK 32            // pixels per K step (68 KB of LDS, two workgroups per CU)
 #define NP (BK / 8)      // 16-byte pieces of a staged tile per thread
 #define KPB (256 / BK)   // K steps per block of the pixel table
 #define NBB 2           // LDS buffers of the dense side
@@ -76,9 +73,8 @@ __device__ __forceinline__ float4 xform4_nomask(float4 v, const float4& a, const
 // GPLAIN: the gathered side has no folded norm / activation.  DMODE: dense side 0 = plain by LDS-DMA, 1 = plain through
 // registers (A/B), 2 = folded norm + activation through registers.  TPT: taps per tile (2: a 64-channel gathered tensor).
 template <bool GPLAIN, int DMODE, int TPT>
-__global__ __launch_bounds__(256, BK == 32 ? 2 : 3) void conv_wgrad128_kernel(const ssc_wgrad_desc d, const Magics mg,
-                                                                float* __restrict__ slab_base, long slab_stride, int splitk,
-                                                                int xcd) {
+__global__ __launch_bounds__(256, 2) void conv_wgrad128_kernel(const ssc_wgrad_desc d, const Magics mg,
+                                                   float* __restrict__ slab_base, long slab_stride, int splitk, int xcd) {
     constexpr int T_SZ = BK * TB;          // floats per operand tile
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                      // [2][BK][TB]  gathered side, [pixel][column]
@@ -384,12 +380,7 @@ static int wg128_tpt(const ssc_wgrad_desc& d) {
         if (Cg % TB == 0 && (d.g.C1 == 0 || d.g.C0 % TB == 0)) return 1;
         if (d.g.C1 == 0 && d.g.C0 == 64) return 2;
     }
-    static int span = -1;       // SSC_WG128_SPAN=0: no tap-spanning tiles (A/B)
-    if (span < 0) {
-        const char* e = ssc_dev_getenv("SSC_WG128_SPAN");
-        span = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    if (span && wg128_use_bf() && d.exact == 0 && d.g.C1 == 0 && (Cg & 3) == 0 && Cg >= 64 && d.Cg_real >= 1 && d.Cg_real <= Cg &&
+    if (wg128_use_bf() && d.exact == 0 && d.g.C1 == 0 && (Cg & 3) == 0 && Cg >= 64 && d.Cg_real >= 1 && d.Cg_real <= Cg &&
         (long)d.TH * d.TW * Cg < 0x7fffff00L)
         return Cg >= TB ? 2 : 3;
     return 0;
@@ -397,12 +388,6 @@ static int wg128_tpt(const ssc_wgrad_desc& d) {
 
 extern "C" int ssc_conv_wgrad128_supported(const ssc_wgrad_desc* dp) {
     const ssc_wgrad_desc& d = *dp;
-    static int off = -1;        // SSC_WGRAD128=0: always the 64-column kernel of igemm.hip (A/B)
-    if (off < 0) {
-        const char* e = ssc_dev_getenv("SSC_WGRAD128");
-        off = (e != nullptr && e[0] == '0') ? 1 : 0;
-    }
-    if (off) return 0;
     const int Cg = d.g.C0 + d.g.C1, Cd = d.d.C0 + d.d.C1;
     const long P = (long)d.NB * d.PH * d.PW;
     if (wg128_tpt(d) == 0) return 0;
@@ -429,11 +414,9 @@ static int wg128_splitk(const ssc_wgrad_desc& d, int64_t ws_bytes, bool have_ws)
     const long tiles = ((Mtot + TB - 1) / TB) * ((d.Nn + TB - 1) / TB);
     const long out_elems = (long)d.TH * d.TW * d.Cg_real * d.ldc;
     const int ncu = wg128_num_cu();
-    static int force = -2;
-    if (force == -2) {
-        const char* e = ssc_dev_getenv("SSC_WG128_SPLITK");
-        force = (e != nullptr) ? atoi(e) : -1;
-    }
+    static const int force = ssc_dev_int("SSC_WG128_SPLITK", -1);       // > 0: the allowed slice count nearest to it (tests, tuning)
+    // one workgroup per CU is priced below its K-tiles: in the train step it co-runs better, 1824 vs 1818 images/s (against 1.25)
+    constexpr double OCC1 = 0.9;
     long best = 1;
     double best_cost = 1e300;
     for (long sk = 1; sk <= 1024; ++sk) {
@@ -443,12 +426,7 @@ static int wg128_splitk(const ssc_wgrad_desc& d, int64_t ws_bytes, bool have_ws)
         const long wgs = tiles * sk;
         const long on_cu = (wgs + ncu - 1) / ncu;                       // workgroups on the busiest CU
         double cost = (double)on_cu * (double)(per + 5);
-        static double occ1 = -1.0;      // SSC_WG128_OCC1: penalty of one workgroup per CU (tuning aid)
-        if (occ1 < 0.0) {
-            const char* e = ssc_dev_getenv("SSC_WG128_OCC1");
-            occ1 = (e != nullptr) ? atof(e) : 0.9;      // in the train step one workgroup per CU co-runs better: 1824 vs 1818 images/s (1.25)
-        }
-        if (on_cu == 1) cost *= occ1;
+        if (on_cu == 1) cost *= OCC1;
         if (sk > 1) cost += (double)sk * (double)out_elems * 4.0 * 2.0 / 3.0e6 / 3.4 + 2.0;     // slab bytes at ~3 TB/s in K-tile units (3.4 us)
         if (force > 0) cost = (double)(sk > force ? sk - force : force - sk);
         if (cost < best_cost) { best_cost = cost; best = sk; }
@@ -462,11 +440,7 @@ void ssc_launch_wgrad_reduce(const float* ws, long count, int splitk, float* out
 // the kernel's DMODE: 0 a plain dense tile by LDS-DMA, 1 plain through registers, 2 folded norm / activation through registers
 static int wg128_dense_mode(const ssc_wgrad_desc& d) {
     if (!view_plain(d.d)) return 2;
-    static int dma = -1;        // SSC_WGRAD_DMA=0: plain dense tiles through registers (A/B)
-    if (dma < 0) {
-        const char* e = ssc_dev_getenv("SSC_WGRAD_DMA");
-        dma = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
+    static const int dma = ssc_dev_int("SSC_WGRAD_DMA", 1);      // 0: plain dense tiles through registers (A/B)
     return dma ? 0 : 1;
 }
 // workgroups of a launch: row tiles x column tiles x K slices
@@ -475,14 +449,7 @@ static long wg128_wgs(const ssc_wgrad_desc& d, int splitk) {
     return ((Mtot + TB - 1) / TB) * ((d.Nn + TB - 1) / TB) * splitk;
 }
 // whole K slices per XCD (the kernel's xcd flag): a split launch whose grid is a multiple of 8
-static int wg128_xcd(long wgs, int splitk) {
-    static int xcd_on = -1;     // SSC_WG128_XCD=0: plain grid order (A/B)
-    if (xcd_on < 0) {
-        const char* e = ssc_dev_getenv("SSC_WG128_XCD");
-        xcd_on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    return (xcd_on && splitk > 1 && (wgs & 7) == 0) ? 1 : 0;
-}
+static int wg128_xcd(long wgs, int splitk) { return (splitk > 1 && (wgs & 7) == 0) ? 1 : 0; }
 
 template <bool GPLAIN, int DMODE, int TPT>
 static int launch_wg128(const ssc_wgrad_desc& d, int splitk, float* ws, hipStream_t st) {
@@ -528,15 +495,7 @@ extern "C" int ssc_wg128_timing(unsigned long long* out8, int reset) {
 int ssc_launch_wgrad128_bf(const ssc_wgrad_desc& d, int tpt, int splitk, float* ws, hipStream_t st);
 // what that launch chooses: {gathered side plain, dense side plain, DB, xcd}
 void ssc_wgrad128_bf_form(const ssc_wgrad_desc& d, int splitk, int* out4);
-static bool wg128_use_bf() {
-    static int on = -1;         // SSC_ARITH=fp32 (everything exact) or SSC_WGRAD_BF16=0 (this kernel only): the exact-fp32 MFMA form
-    if (on < 0) {
-        const char* a = getenv("SSC_ARITH");
-        const char* w = ssc_dev_getenv("SSC_WGRAD_BF16");
-        on = ((a != nullptr && (a[0] == 'f' || a[0] == 'F')) || (w != nullptr && w[0] == '0')) ? 0 : 1;
-    }
-    return on != 0;
-}
+static bool wg128_use_bf() { return !ssc_arith_fp32(); }       // SSC_ARITH=fp32: the exact-fp32 MFMA form
 
 int ssc_conv_wgrad128_bf_selected(const ssc_wgrad_desc* dp) { return (wg128_use_bf() && dp->exact == 0) ? 1 : 0; }
 

@@ -370,12 +370,8 @@ static long wb_wgs(const ssc_wgrad_desc& d, int splitk) {
 }
 static int wb_xcd(long wgs, int splitk) { return (splitk > 1 && (wgs & 7) == 0) ? 1 : 0; }
 static int wb_db() {
-    static int db = -1;         // SSC_WGBF_DB=1: two LDS stages, one workgroup per CU (A/B)
-    if (db < 0) {
-        const char* e = ssc_dev_getenv("SSC_WGBF_DB");
-        db = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
-    return db;
+    static const int db = ssc_dev_int("SSC_WGBF_DB", 0);        // 1: two LDS stages, one workgroup per CU (A/B)
+    return db != 0;
 }
 void ssc_wgrad128_bf_form(const ssc_wgrad_desc& d, int splitk, int* out4) {
     out4[0] = wb_view_plain(d.g) ? 1 : 0;

@@ -338,7 +338,6 @@ def workspace(nbytes=256 << 20):
 # there (after waiting for everything issued so far on the current stream), so their workgroups fill the CUs that the
 # chain's small layers and kernel tails leave idle; join_wgrad() makes the current stream wait for them.
 WGRAD_STREAM = None
-WGRAD_SIDE_MAX_PIXELS = int(_dev_env('SSC_WGRAD_SIDE_PIXELS', '0')) or None   # None = every layer
 _wgrad_pending = False
 
 
@@ -528,7 +527,6 @@ _SPLITS = {}            # (data_ptr, taps, c0, c1, orient) -> _Split; the entry 
 _SPLIT_TABLES = {}      # tuple of keys -> (device job table, total threads)
 _PARAM_RANGES = []      # [lo, hi) byte ranges of the flat parameter buffers (ParamStore scopes): filters inside them are PARAMETERS
 _VOLATILE_MAX = 256     # entries of filters that are not parameters (see filter_split)
-_SPLIT_ALWAYS = _dev_env('SSC_SPLIT_ALWAYS', '0') == '1'      # diagnostic: every filter treated as volatile
 
 
 class _Split(object):
@@ -588,7 +586,7 @@ def filter_split(w, orient):
         e = _Split()
         e.key, e.w, e.kc, e.nbp, e.threads, e.version = key, w, kc.value, nbp.value, threads.value, None
         e.taps, e.c0, e.c1, e.orient = KH * KW, c0, c1, orient
-        e.param = (not _SPLIT_ALWAYS) and any(lo <= key[0] < hi for lo, hi in _PARAM_RANGES)
+        e.param = any(lo <= key[0] < hi for lo, hi in _PARAM_RANGES)
         e.buf = torch.empty(nbytes.value, dtype=torch.uint8, device=w.device)
         e.pinned, e.gen = False, 0
         if e.param:
@@ -691,9 +689,6 @@ def _refresh_entries(es):
     check(lib().ssc_filter_split_batch(ptr(tab[0]), len(es), tab[1], stream_ptr()), 'ssc_filter_split_batch')
 
 
-_BF_PARTIAL = _dev_env('SSC_BF_PARTIAL', '1') == '1'      # A/B: the partial-chunk form of the bf16 conv kernel
-
-
 def bf_form(d):
     """Which bf16-split form of the conv kernel a launch descriptor qualifies for (the library decides again: fwd_is_bf):
     'uniform' -- every 32-wide K-tile inside one tap and one source; 'partial' -- ONE source with any multiple of 4 channels
@@ -704,7 +699,7 @@ def bf_form(d):
         return None
     if not ((d.x.C0 % 32) or (d.x.C1 % 32) or d.k_real != d.x.C0 + d.x.C1):
         return 'uniform'
-    if _BF_PARTIAL and d.x.C1 == 0 and d.x.C0 > 32 and d.x.C0 % 4 == 0 and d.x.C0 % 32 != 0 and \
+    if d.x.C1 == 0 and d.x.C0 > 32 and d.x.C0 % 4 == 0 and d.x.C0 % 32 != 0 and \
             (d.wC1 if d.bmode else d.wC0) == d.k_real and -(-d.k_real // 32) == -(-d.x.C0 // 32):
         return 'partial'
     return None
@@ -822,8 +817,7 @@ def _run_conv(d, bn=None, bnbwd=None, minmax=None):
 def _run_wgrad(d, side=False):
     global _wgrad_pending
     d.exact = 0 if ARITH_BF16 else 1
-    if side and WGRAD_STREAM is not None and PROFILE is None and \
-            (WGRAD_SIDE_MAX_PIXELS is None or d.NB * d.PH * d.PW <= WGRAD_SIDE_MAX_PIXELS):
+    if side and WGRAD_STREAM is not None and PROFILE is None:
         WGRAD_STREAM.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(WGRAD_STREAM):
             ws = workspace()
