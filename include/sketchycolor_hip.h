@@ -848,6 +848,15 @@ int ssc_max_pool2_argmax(const float* x, const float* ab, int N, int H, int W, i
  * (code[n,y,x,c] & 3) == 2*dy + dx and 0 at the window's three other positions.  Every element of out is written. */
 int ssc_unpool2(const float* x, const uint8_t* code, int N, int h, int w, int C, float* out, void* stream);
 
+/* --- the scene session's turn report (scene_system.hip): scene_session.py; DESIGN.md section 8.14 --- */
+/* out int64 [256]: out[g] = #{p < H*W : inner[p] == g && the three bytes of prev at 3p differ from those of next in at least one
+ * channel}; prev, next uint8 [H,W,3], inner uint8 [H,W].  The entry point zeroes out on the stream; every workgroup keeps 256
+ * bins in LDS and adds its non-empty ones to out as 64-bit integers: the same bits on every run.  16-byte loads when the three
+ * pointers are on 16-byte boundaries, bytewise ones otherwise.  1 <= H*W <= 2^24; -1 for a null pointer or a bad size, -3 for
+ * an out off its 8-byte boundary: nothing is launched then */
+int ssc_scene_change_hist_u8(const uint8_t* prev, const uint8_t* next, const uint8_t* inner, int H, int W, int64_t* out,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

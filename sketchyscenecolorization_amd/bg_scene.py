@@ -3,8 +3,9 @@ the instruction spliced into the previous one, the previous result cropped to it
 generator, and the finishing on the device -- instances and sketch strokes over the generation, the sky gradient, the strokes
 once more (hip.bg_scene_crop_u8, bg_scene_compose_u8, bg_sky_gradient_u8, bg_scene_overlay_u8).
 
-The reference's result records and ``withdraw`` (customization_util.py) are not here: the caller hands the previous image and
-text in and keeps what comes back."""
+The caller hands the previous image and text in and keeps what comes back.  The reference's result records and ``withdraw``
+(customization_util.py) are scene_records.py; scene_session.SceneSession keeps them, and the previous image on the device,
+from one instruction to the next (sketchyscene_colorization_main.py)."""
 import os
 import re
 
@@ -109,14 +110,19 @@ STATUS_TEXT = {1: 'no background pixel (inner mask 0) in rows %d..%d, where the 
 
 
 def colorize_background(trainer, scene, text, previous_image=None, previous_text='', color_gradient=True, vocab=None,
-                        text_len=8, info=None):
+                        text_len=8, info=None, resident=None, on_device=False):
     """-> (background uint8 [H,W,3], fg_marked uint8 [H,W,3], processed text), the arrays on the host.
 
     trainer: a BGTrainer with the weights loaded; scene: what load_scene returns; previous_image uint8 [H,W,3] defaults to the
     sketch and previous_text to 'the sky is blue and the ground is green'; vocab: the caption vocabulary (word -> index).
     The forward pass is test mode's: one image, zero labels.  ``info`` (a dict) receives sky_color, sky_bottom and start_height
     of the gradient (None without it).  ValueError for a text that cannot be combined and for a scene the gradient has no
-    answer for."""
+    answer for.
+
+    A scene session (scene_session.py) keeps the scene on the device between its turns: previous_image may be a uint8 [H,W,3]
+    tensor on the device (it is read, never written); ``resident``: a dict of device tensors that were uploaded once -- sketch
+    uint8 [H,W,3], inner uint8 [H,W] and grass uint8 [256] (grass_table) -- read in place of the uploads here; on_device: the
+    two images come back as device tensors and are not read.  The launches are the same."""
     import torch
     from . import hip
     from .data_processing.text_processing import preprocess_sentence
@@ -128,14 +134,22 @@ def colorize_background(trainer, scene, text, previous_image=None, previous_text
         previous_image = sketch
     if previous_text == '':
         previous_text = DEFAULT_PREVIOUS_TEXT
-    previous_image = np.ascontiguousarray(previous_image, dtype=np.uint8)
-    if previous_image.shape != (h, w, 3) or sketch.shape != (h, w, 3):
-        raise ValueError('previous image %s and sketch %s must both be %d x %d x 3' % (previous_image.shape, sketch.shape, h, w))
+    previous_on_device = isinstance(previous_image, torch.Tensor)
+    if previous_on_device:
+        if previous_image.dtype != torch.uint8 or not previous_image.is_cuda or not previous_image.is_contiguous():
+            raise ValueError('a previous image given as a tensor must be contiguous uint8 on the device')
+    else:
+        previous_image = np.ascontiguousarray(previous_image, dtype=np.uint8)
+    if tuple(previous_image.shape) != (h, w, 3) or sketch.shape != (h, w, 3):
+        raise ValueError('previous image %s and sketch %s must both be %d x %d x 3' % (tuple(previous_image.shape), sketch.shape, h, w))
     processed = combine_text(text, previous_text)
     tok = np.array(preprocess_sentence(processed, vocab, text_len), dtype=np.int32)[None]
-    sketch_d, inner_d = torch.from_numpy(sketch).cuda(), torch.from_numpy(inner).cuda()
-    grass_d = torch.from_numpy(grass_table(scene['class_ids'])).cuda()
-    fg_d = hip.bg_scene_crop_u8(torch.from_numpy(previous_image).cuda(), inner_d)
+    if resident is not None:
+        sketch_d, inner_d, grass_d = resident['sketch'], resident['inner'], resident['grass']
+    else:
+        sketch_d, inner_d = torch.from_numpy(sketch).cuda(), torch.from_numpy(inner).cuda()
+        grass_d = torch.from_numpy(grass_table(scene['class_ids'])).cuda()
+    fg_d = hip.bg_scene_crop_u8(previous_image if previous_on_device else torch.from_numpy(previous_image).cuda(), inner_d)
     x = torch.empty((1, h, w, 3), dtype=torch.float32, device='cuda')
     y, xd, cnt = torch.empty_like(x), torch.empty((1, h, w, 8), dtype=torch.float32, device='cuda'), torch.empty(1, device='cuda')
     lab0 = torch.zeros((1, h, w), dtype=torch.int32, device='cuda')
@@ -156,4 +170,6 @@ def colorize_background(trainer, scene, text, previous_image=None, previous_text
                  'start_height': int(facts[2])}
     if info is not None:
         info.update(found)
+    if on_device:
+        return out_d, marked_d, processed
     return out_d.cpu().numpy(), marked_d.cpu().numpy(), processed

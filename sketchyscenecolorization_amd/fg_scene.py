@@ -7,7 +7,8 @@ obj_lib/input_pipeline.py).
 
 One instance per forward pass, in the order given, as the reference runs them (batch_size = 1, :202): the generators' norms are
 batch statistics, so a batch of instances would give every one of them other pixels.  The reference's Instance_Matching step is
-not here: the caller names the instances.  Result records and ``withdraw`` stay with the caller, as in bg_scene.py."""
+not here: the caller names the instances.  Matching, result records and ``withdraw`` are scene_session.SceneSession's, which
+calls this with the scene and the previous result kept on the device (sketchyscene_colorization_main.py)."""
 import os
 import re
 
@@ -115,7 +116,8 @@ def _cut_is_empty(s, bh, bw, margin):
     return s - 2 * int(round(s * abs(bh - bw) / max(bh, bw) / 2.)) < 1
 
 
-def colorize_instances(trainer, scene, text, inst_indices, previous_image=None, vocab=None, text_len=15, noise=None, info=None):
+def colorize_instances(trainer, scene, text, inst_indices, previous_image=None, vocab=None, text_len=15, noise=None, info=None,
+                       resident=None, on_device=False):
     """-> (result uint8 [H,W,3] on the host, processed text).
 
     trainer: a GanTrainer with the weights loaded (its image size S is the instances' size); scene: what load_instances returns;
@@ -123,6 +125,11 @@ def colorize_instances(trainer, scene, text, inst_indices, previous_image=None, 
     defaults to the sketch; vocab: the caption vocabulary (word -> index); noise: float [len(inst_indices), 256] or None (drawn
     on the device, as inference mode draws it).  ``info`` (a dict) receives per instance the [S,S,3] sketch the generator read
     (before grass is thickened), the [S,S,3] image it made and, for a road, {V, Hc}.
+
+    A scene session (scene_session.py) keeps the scene on the device between its turns: previous_image may be a uint8 [H,W,3]
+    tensor on the device (it is copied, never written); ``resident``: a dict of device tensors that were uploaded once -- sketch
+    uint8 [H,W,3], inner uint8 [H,W], grass uint8 [256] (grass_table) and masks, the list of the N small masks -- read in place
+    of the uploads here; on_device: the result comes back as a device tensor and is not read.  The launches are the same.
 
     ValueError before any launch for an instance whose class the generator does not know, and after the last launch -- nothing
     is returned then -- for a road that is a single line.  The road verdicts stay on the device until the image is read."""
@@ -139,9 +146,14 @@ def colorize_instances(trainer, scene, text, inst_indices, previous_image=None, 
     inst_indices = [int(k) for k in inst_indices]
     if previous_image is None:
         previous_image = sketch
-    previous_image = np.ascontiguousarray(previous_image, dtype=np.uint8)
-    if previous_image.shape != (h, w, 3) or sketch.shape != (h, w, 3):
-        raise ValueError('previous image %s and sketch %s must both be %d x %d x 3' % (previous_image.shape, sketch.shape, h, w))
+    previous_on_device = isinstance(previous_image, torch.Tensor)
+    if previous_on_device:
+        if previous_image.dtype != torch.uint8 or not previous_image.is_cuda or not previous_image.is_contiguous():
+            raise ValueError('a previous image given as a tensor must be contiguous uint8 on the device')
+    else:
+        previous_image = np.ascontiguousarray(previous_image, dtype=np.uint8)
+    if tuple(previous_image.shape) != (h, w, 3) or sketch.shape != (h, w, 3):
+        raise ValueError('previous image %s and sketch %s must both be %d x %d x 3' % (tuple(previous_image.shape), sketch.shape, h, w))
     if noise is not None and tuple(noise.shape) != (len(inst_indices), 256):
         raise ValueError('noise is %s, %d instances need [%d, 256]' % (tuple(noise.shape), len(inst_indices), len(inst_indices)))
     check_instances(scene.get('image_id', '?'), boxes, masks, class_ids, h, w)
@@ -156,7 +168,11 @@ def colorize_instances(trainer, scene, text, inst_indices, previous_image=None, 
                              % (k, y2 - y1, x2 - x1, s, s))
     processed = segment_user_input_text(text)
     tok = np.array(preprocess_sentence(processed, vocab, text_len), dtype=np.int32)[None]
-    result_d, inner_d = torch.from_numpy(previous_image).cuda(), torch.from_numpy(np.ascontiguousarray(inner)).cuda()
+    result_d = previous_image.clone() if previous_on_device else torch.from_numpy(previous_image).cuda()
+    if resident is not None:
+        inner_d, sketch_d, grass_d, masks_d = resident['inner'], resident['sketch'], resident['grass'], resident['masks']
+    else:
+        inner_d, sketch_d, grass_d, masks_d = torch.from_numpy(np.ascontiguousarray(inner)).cuda(), None, None, None
     if noise is not None:
         noise = torch.as_tensor(noise, dtype=torch.float32).cuda()
     roads = torch.ones((max(len(inst_indices), 1), 3), dtype=torch.int32, device='cuda')
@@ -166,7 +182,7 @@ def colorize_instances(trainer, scene, text, inst_indices, previous_image=None, 
         y1, x1, y2, x2 = boxes[k].tolist()
         bh, bw = y2 - y1, x2 - x1
         margin = 0 if cls == ROAD_LABEL else 10
-        mask_d = hip.fg_scene_mask_u8(torch.from_numpy(masks[k]).cuda())
+        mask_d = hip.fg_scene_mask_u8(masks_d[k] if masks_d is not None else torch.from_numpy(masks[k]).cuda())
         if (bh, bw) != (s, s):
             sketch_k = resize_and_padding_mask_image_device(mask_d, s, margin)
         else:       # a box of the generator's size goes in as it is (:298-302): the channel is replicated, nothing more
@@ -179,8 +195,11 @@ def colorize_instances(trainer, scene, text, inst_indices, previous_image=None, 
         inst_d = reverse_resize_image_device(gen[0], bh, bw, margin_size=margin)
         hip.fg_scene_paste_u8(result_d, inner_d, inst_d, y1, x1, k + 1)
         steps.append((k, cls, sketch_k, gen))
-    hip.bg_scene_overlay_u8(result_d, inner_d, torch.from_numpy(grass_table(class_ids)).cuda(), torch.from_numpy(sketch).cuda())
-    result, verdicts = result_d.cpu().numpy(), roads.cpu().numpy()      # read together: nothing came back before
+    if resident is None:
+        grass_d, sketch_d = torch.from_numpy(grass_table(class_ids)).cuda(), torch.from_numpy(sketch).cuda()
+    hip.bg_scene_overlay_u8(result_d, inner_d, grass_d, sketch_d)
+    result = result_d if on_device else result_d.cpu().numpy()
+    verdicts = roads.cpu().numpy()      # read together: nothing came back before
     if info is not None:
         info['instances'] = [{'index': k, 'class': cls, 'sketch': sk.cpu().numpy(), 'generated': gen[0].cpu().numpy(),
                               'road': ({'V': int(verdicts[p, 1]), 'Hc': int(verdicts[p, 2])} if cls == ROAD_LABEL else None)}

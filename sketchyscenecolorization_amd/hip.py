@@ -272,6 +272,7 @@ SIGNATURES = {
     'ssc_attn_scores_bwd': [_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     'ssc_max_pool2_argmax': [_P, _P, _I, _I, _I, _I, _P, _P, _P],
     'ssc_unpool2': [_P, _P, _I, _I, _I, _I, _P, _P],
+    'ssc_scene_change_hist_u8': [_P, _P, _P, _I, _I, _P, _P],
 }
 
 
@@ -1465,6 +1466,32 @@ def instance_label_hist(labels_u8, masks_u8, boxes, offsets, out=None):
     assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == 256 * n
     check(lib().ssc_instance_label_hist(ptr(labels_u8), s, ptr(masks_u8), masks_u8.numel(), ptr(boxes), ptr(offsets), n, ptr(out),
                                         stream_ptr()), 'instance_label_hist')
+    return out
+
+
+# ---------------------------------------------------------------------------
+# the scene session's turn report (csrc/scene_system.hip; scene_session.py)
+# ---------------------------------------------------------------------------
+def scene_change_hist_u8(prev_u8, new_u8, inner_u8, out=None):
+    """prev, new uint8 [H,W,3]; inner uint8 [H,W] -> int64 [256] on the device, unread: out[g] = the number of pixels with
+    inner == g whose three bytes differ in at least one channel.  Integer sums: the same bits on every run.  ValueError, before
+    any launch, for anything that is not three contiguous uint8 tensors of these shapes on one device."""
+    for name, t in (('prev', prev_u8), ('new', new_u8), ('inner', inner_u8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError('scene_change_hist_u8: %s must be a contiguous uint8 tensor on the device' % name)
+    if inner_u8.dim() != 2 or inner_u8.numel() < 1 or inner_u8.numel() > (1 << 24):
+        raise ValueError('scene_change_hist_u8: inner is %s, it must be [H,W] with 1 <= H*W <= 2^24' % (tuple(inner_u8.shape),))
+    h, w = int(inner_u8.shape[0]), int(inner_u8.shape[1])
+    if tuple(prev_u8.shape) != (h, w, 3) or tuple(new_u8.shape) != (h, w, 3):
+        raise ValueError('scene_change_hist_u8: prev is %s and new is %s, inner %s needs both as [%d, %d, 3]'
+                         % (tuple(prev_u8.shape), tuple(new_u8.shape), tuple(inner_u8.shape), h, w))
+    if prev_u8.device != inner_u8.device or new_u8.device != inner_u8.device:
+        raise ValueError('scene_change_hist_u8: the three tensors lie on different devices')
+    if out is None:
+        out = torch.empty(256, dtype=torch.int64, device=inner_u8.device)
+    if out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != 256 or out.device != inner_u8.device:
+        raise ValueError('scene_change_hist_u8: out must be 256 contiguous int64 on the device of the images')
+    check(lib().ssc_scene_change_hist_u8(ptr(prev_u8), ptr(new_u8), ptr(inner_u8), h, w, ptr(out), stream_ptr()), 'scene_change_hist_u8')
     return out
 
 

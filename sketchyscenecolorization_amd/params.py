@@ -302,23 +302,33 @@ class Scope(object):
         return list(self.offsets.keys())
 
 
+def store_specs(block_type, vocab_size=58, img=192):
+    """-> (generator specs, discriminator specs, non-trainable specs) of a ParamStore; nothing is allocated."""
+    if block_type == 'Pix2Pix':
+        return pix2pix_param_specs(vocab_size, img)
+    if block_type == 'Residual':
+        return (residual_generator_specs('fg', vocab_size, img),) + tuple(residual_discriminator_specs())
+    if block_type == 'MRU':
+        return (mru_generator_specs(vocab_size, img),) + tuple(mru_discriminator_specs())
+    if block_type == 'BG':              # Background_Colorization (BASELINE config 5): residual generator + discriminator
+        return residual_generator_specs('bg', vocab_size, img), bg_discriminator_specs(), []
+    raise NotImplementedError('block_type %r: Pix2Pix (train+infer) and MRU/Residual/BG (generator forward) '
+                              'are built so far' % block_type)
+
+
+def store_bytes(block_type, vocab_size=58, img=192, slots=3):
+    """The device bytes of a ParamStore's flat buffers: ``slots`` float buffers per scope (parameters, gradients, Adam's second
+    moment; 4 with the first moment a BGTrainer adds) plus the non-trainables."""
+    g, d, nt = store_specs(block_type, vocab_size, img)
+    scope = lambda specs: sum((int(np.prod(shape)) + ALIGN - 1) // ALIGN * ALIGN for _, shape, _ in specs)
+    return 4 * (slots * (scope(g) + scope(d)) + sum(int(np.prod(shape)) for _, shape, _ in nt))
+
+
 class ParamStore(object):
     """All variables of one model instance (generator + discriminator + non-trainables)."""
 
     def __init__(self, block_type='Pix2Pix', vocab_size=58, img=192, device='cuda', seed=0):
-        if block_type == 'Pix2Pix':
-            g, d, nt = pix2pix_param_specs(vocab_size, img)
-        elif block_type == 'Residual':
-            g = residual_generator_specs('fg', vocab_size, img)
-            d, nt = residual_discriminator_specs()
-        elif block_type == 'MRU':
-            g = mru_generator_specs(vocab_size, img)
-            d, nt = mru_discriminator_specs()
-        elif block_type == 'BG':            # Background_Colorization (BASELINE config 5): residual generator + discriminator
-            g, d, nt = residual_generator_specs('bg', vocab_size, img), bg_discriminator_specs(), []
-        else:
-            raise NotImplementedError('block_type %r: Pix2Pix (train+infer) and MRU/Residual/BG (generator forward) '
-                                      'are built so far' % block_type)
+        g, d, nt = store_specs(block_type, vocab_size, img)
         self.block_type = block_type
         self.device = device
         self.generator = Scope('generator', g, device)
