@@ -246,6 +246,27 @@ int ssc_conv_wgrad_kernel_name(const ssc_wgrad_desc* d, char* buf, int len);
 /* the launch plan for a descriptor (host only; tuning and tests): out5 = {tile configuration, split-K slabs, whole
  * tiles, K slices per remaining tile (combined inside the launch), modelled kilo-cycles} */
 int ssc_conv_forward_plan(const ssc_conv_desc* d, int64_t ws_bytes, int* out5);
+/* what ssc_conv_forward_bn / _bnbwd / _bnbwd2 / _minmax (rider = SSC_RIDER_*) would do with a descriptor (host only, launches
+ * nothing; computed by the function those entry points decide with): out5 = {path (SSC_RIDER_PATH_*), the kernel that runs
+ * (0 the tiled ones, 1 head1 forward, 2 head1 dgrad, 3 narrow, 4 fewchan, 5 pw1x1, 6 c3x3, 7 s2n16, 8 tr4_tiny, 9 fewchan7,
+ * 10 tr4n16: the dispatch order), rows of partial results (*nrows of _bnbwd / _bnbwd2), where they lie (SSC_RIDER_ROWS_*), the
+ * workspace bytes the conv itself keeps}.  ws_bytes <= 0 stands for a NULL workspace.  site0 (_bnbwd) / site0, site1, C0
+ * (_bnbwd2) as those entry points take them, never dereferenced beyond the structs; NULL, NULL, 0 for the other riders. */
+#define SSC_RIDER_BN 0
+#define SSC_RIDER_BNBWD 1
+#define SSC_RIDER_BNBWD2 2
+#define SSC_RIDER_MINMAX 3
+#define SSC_RIDER_PATH_PLAIN 0  /* the launch as ssc_conv_forward makes it: separate pass (_bn, _minmax) or *nrows = 0 */
+#define SSC_RIDER_PATH_STREAM 1 /* a streaming kernel that carries the rider: a row per walker */
+#define SSC_RIDER_PATH_TILE 2   /* the tile epilogue: a row per row tile and phase */
+#define SSC_RIDER_PATH_SLAB 3   /* _bn of a split-K launch: the statistics ride in the slab sum */
+#define SSC_RIDER_ROWS_NONE 0
+#define SSC_RIDER_ROWS_WS_HEAD 1   /* at the workspace's start (the streaming kernels use no workspace) */
+#define SSC_RIDER_ROWS_WS_TAIL 2   /* behind the conv's share of the workspace */
+#define SSC_RIDER_ROWS_CALLER 3    /* in the sites' partial buffers */
+struct ssc_bnbwd_site;
+int ssc_conv_rider_plan(const ssc_conv_desc* d, int rider, int64_t ws_bytes, const struct ssc_bnbwd_site* site0,
+                        const struct ssc_bnbwd_site* site1, int C0, int64_t* out5);
 /* the launch plan of a filter gradient that reaches the general kernel (conv_wgrad_kernel of igemm.hip; host only, launches
  * nothing): out4 = {tile configuration (0 128x128, 1 64x128, 2 128x64, 3 64x64, 4 128x32; -1: the patch head, the 128 x 128 or
  * the 16-column kernel takes the launch), split-K slabs, view form (gathered side plain, dense side plain, dense tile by LDS-DMA:

@@ -1,10 +1,12 @@
-"""Digest of a short Foreground training run, for comparing two trees bit for bit.
+"""Digest of a short Foreground training run (and one Background configuration), for comparing two trees bit for bit.
 
 One configuration = 5 calls of ``GanTrainer.train_iteration`` at img 64, batch 2, on fixed synthetic batches with
 ``next_batch_d`` passed (the first call of a step shape runs eagerly, the second captures it, three replay).  After each
 iteration the two losses are printed as ``float.hex``; at the end the SHA-256 of the generator's and the discriminator's
 weights, of both second-moment buffers and of every spectral-norm ``u``.  Only the trainer's constructor arguments,
 ``train_iteration`` and ``synthetic.synthetic_batch`` are used, so the file runs unchanged in an older checkout.
+``background``: 4 calls of ``BGTrainer.train_step`` at image size 64 (the smallest the generator's depth takes), batch 2, on
+fixed random tensors; the five losses as ``float.hex`` per step, then the same hashes plus both first-moment buffers.
 
     python scripts/train_state_digest.py                    every configuration, each a process of its own, three at a time
     python scripts/train_state_digest.py --config NAME      one configuration in this process (two ranks: two children)
@@ -31,6 +33,7 @@ CONFIGS = {
     'mru': (1, dict(use_graphs=True, block_type='MRU'), {}),
     'world2_pix2pix': (2, dict(use_graphs=True), {}),
     'world2_pix2pix_inline': (2, dict(use_graphs=True, overlap_real=False), {}),
+    'background': (1, None, {}),        # BGTrainer: run_background
 }
 
 
@@ -58,6 +61,27 @@ def run(name, rank=0, process_group=None):
     return out
 
 
+def run_background(name):
+    import torch
+    from sketchyscenecolorization_amd.bg_colorization import BGTrainer
+    tr = BGTrainer(image_size=IMG, max_steps=50, seed=5)
+    g = torch.Generator().manual_seed(31)
+    x, y = (torch.rand(NB, IMG, IMG, 3, generator=g) * 2 - 1).cuda(), (torch.rand(NB, IMG, IMG, 3, generator=g) * 2 - 1).cuda()
+    text = torch.randint(1, 18, (NB, 8), generator=g).numpy()
+    labels = torch.randint(0, 3, (NB, IMG, IMG), generator=g, dtype=torch.int32).cuda()
+    out = []
+    for it in range(4):
+        tr.train_step(x, y, text, labels)
+        out.append('%s rank 0 it %d losses %s' % (name, it, ' '.join(float(v).hex() for v in tr.losses.cpu())))
+    torch.cuda.synchronize()
+    st = tr.store
+    for label, t in [('generator.flat', st.generator.flat), ('discriminator.flat', st.discriminator.flat),
+                     ('generator.adam_v', st.generator.adam_v), ('discriminator.adam_v', st.discriminator.adam_v),
+                     ('generator.adam_m', st.generator.adam_m), ('discriminator.adam_m', st.discriminator.adam_m)]:
+        out.append('%s rank 0 sha256 %s %s' % (name, _sha(t), label))
+    return out
+
+
 def _rank(rank, name, port, out_dir):
     import torch
     import torch.distributed as dist
@@ -75,7 +99,7 @@ def one(name):
     world, _, env = CONFIGS[name]
     os.environ.update(env)
     if world == 1:
-        print('\n'.join(run(name)), flush=True)
+        print('\n'.join(run(name) if CONFIGS[name][1] is not None else run_background(name)), flush=True)
         return
     # two gloo ranks on one device (RCCL refuses two ranks on one device), spawned as tests/two_rank_gloo_gpu_check.py does
     import tempfile

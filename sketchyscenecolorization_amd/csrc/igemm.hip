@@ -1609,41 +1609,59 @@ static void copy_name(const char* src, char* dst, int len) {
     if (len > 0) dst[i] = 0;
 }
 
+// ---- the kernels in front of the tiled ones, in dispatch order: the launch, the name and plan queries and
+// the riders all ask this table ----
+enum { FWD_TILED = 0, FWD_HEAD1, FWD_HEAD1_DGRAD, FWD_NARROW, FWD_FEWCHAN, FWD_PW1X1, FWD_C3X3, FWD_S2N16, FWD_TR4_TINY, FWD_FEWCHAN7,
+       FWD_TR4N16 };
+constexpr unsigned R_BN = 1u << SSC_RIDER_BN, R_BNBWD = 1u << SSC_RIDER_BNBWD, R_ALL = 15u;
+struct FwdKernel {
+    int id;
+    int (*supported)(const ssc_conv_desc*);
+    const char* (*name)(const ssc_conv_desc&);
+    int (*rows)(const ssc_conv_desc*);      // rows of partial sums a launch with a rider writes (one per walker or block)
+    unsigned carries;                       // riders (1 << SSC_RIDER_*) the kernel takes on its own epilogue
+    unsigned blind;                         // riders whose fields the predicate does not look at: they keep away from the kernel
+};                                          // every other rider's fields the predicate refuses
+static const FwdKernel FWD_EARLY[] = {
+    // the one-output patch head over a 512-channel tensor and its data gradient (head1.hip): streaming kernels
+    {FWD_HEAD1, ssc_head1_forward_supported, [](const ssc_conv_desc&) { return "head1_fwd"; }, nullptr, 0, 0},
+    {FWD_HEAD1_DGRAD, ssc_head1_dgrad_supported, [](const ssc_conv_desc&) { return "head1_dgrad"; }, nullptr, 0, 0},
+    // <= 4 output channels
+    {FWD_NARROW, ssc_conv_narrow_supported,
+     [](const ssc_conv_desc& d) { return d.nphase == 4 ? "narrow_fwd<transposed>" : "narrow_fwd<conv>"; }, nullptr, 0, R_ALL},
+    // 4x4 stride-2 over 4 or 8 input channels
+    {FWD_FEWCHAN, ssc_conv_fewchan_supported,
+     [](const ssc_conv_desc& d) { return d.x.C0 == 8 ? "conv_fewchan<8>" : "conv_fewchan<4>"; }, nullptr, 0, R_ALL},
+    // 1x1 expansion of a bottleneck: K <= 128, streaming kernel
+    {FWD_PW1X1, ssc_conv_pw1x1_supported, [](const ssc_conv_desc&) { return "conv_pw1x1"; }, ssc_conv_pw1x1_walkers, R_BN, 0},
+    // 3x3 of a bottleneck at 16 / 32 channels (either filter orientation)
+    {FWD_C3X3, ssc_conv_c3x3_supported, [](const ssc_conv_desc& d) { return d.bmode ? "conv_c3x3<NK>" : "conv_c3x3<KN>"; },
+     ssc_conv_c3x3_walkers, R_BN | R_BNBWD, 0},
+    // 4x4 stride-2 conv 64 -> <= 16 channels: 16-column MFMA, K split over the waves
+    {FWD_S2N16, ssc_conv_s2n16_supported, [](const ssc_conv_desc&) { return "conv_s2n16"; }, ssc_conv_s2n16_walkers, R_BN | R_BNBWD, 0},
+    // k = 4 stride-2 transposed conv, <= 4 channels in and out: a thread per lattice pixel
+    {FWD_TR4_TINY, ssc_conv_tr4_tiny_supported, [](const ssc_conv_desc&) { return "deconv_tr4_tiny"; }, ssc_conv_tr4_tiny_blocks, R_BN, 0},
+    // 7x7 stride-2 conv over the (padded) image channels
+    {FWD_FEWCHAN7, ssc_conv_fewchan7_supported, [](const ssc_conv_desc&) { return "conv_fewchan7"; }, ssc_conv_fewchan7_walkers, R_BN, 0},
+    // k = 4 stride-2 transposed conv 256 -> <= 16 channels: 16-column MFMA, a phase per workgroup
+    {FWD_TR4N16, ssc_conv_tr4n16_supported, [](const ssc_conv_desc&) { return "deconv_tr4n16"; }, ssc_conv_tr4n16_rows, R_BN, 0}};
+static_assert(sizeof(FWD_EARLY) / sizeof(FWD_EARLY[0]) == FWD_TR4N16, "one row per FWD_* id, in the enum's order");
+// the first kernel of the table that takes the launch.  under_riders: with the fields of these riders set, which the rows that
+// neither carry nor overlook them refuse
+static int fwd_early_kernel(const ssc_conv_desc* dp, bool have_ws, int64_t ws_bytes, unsigned under_riders = 0) {
+    for (const FwdKernel& k : FWD_EARLY) {
+        if ((under_riders & ~(k.carries | k.blind)) != 0 || !k.supported(dp)) continue;
+        // head1 forward keeps 16 dot products per input pixel in the workspace
+        if (k.id == FWD_HEAD1 && !(have_ws && (int64_t)dp->NB * dp->x.H * dp->x.W * 16 * 4 <= ws_bytes)) continue;
+        return k.id;
+    }
+    return FWD_TILED;
+}
+
 extern "C" int ssc_conv_forward_kernel_name(const ssc_conv_desc* dp, char* buf, int len) {
-    if (ssc_head1_forward_supported(dp) || ssc_head1_dgrad_supported(dp)) {
-        copy_name(ssc_head1_dgrad_supported(dp) ? "head1_dgrad" : "head1_fwd", buf, len);
-        return 0;
-    }
-    if (ssc_conv_narrow_supported(dp)) {
-        copy_name(dp->nphase == 4 ? "narrow_fwd<transposed>" : "narrow_fwd<conv>", buf, len);
-        return 0;
-    }
-    if (ssc_conv_fewchan_supported(dp)) {
-        copy_name(dp->x.C0 == 8 ? "conv_fewchan<8>" : "conv_fewchan<4>", buf, len);
-        return 0;
-    }
-    if (ssc_conv_pw1x1_supported(dp)) {
-        copy_name("conv_pw1x1", buf, len);
-        return 0;
-    }
-    if (ssc_conv_c3x3_supported(dp)) {
-        copy_name(dp->bmode ? "conv_c3x3<NK>" : "conv_c3x3<KN>", buf, len);
-        return 0;
-    }
-    if (ssc_conv_s2n16_supported(dp)) {
-        copy_name("conv_s2n16", buf, len);
-        return 0;
-    }
-    if (ssc_conv_tr4_tiny_supported(dp)) {
-        copy_name("deconv_tr4_tiny", buf, len);
-        return 0;
-    }
-    if (ssc_conv_fewchan7_supported(dp)) {
-        copy_name("conv_fewchan7", buf, len);
-        return 0;
-    }
-    if (ssc_conv_tr4n16_supported(dp)) {
-        copy_name("deconv_tr4n16", buf, len);
+    const int early = fwd_early_kernel(dp, true, (int64_t)1 << 40);       // the ample workspace the plan below assumes too
+    if (early != FWD_TILED) {
+        copy_name(FWD_EARLY[early - 1].name(*dp), buf, len);
         return 0;
     }
     static const char* names[2][5] = {
@@ -1665,208 +1683,192 @@ extern "C" int ssc_bn_stats(const float* x, int64_t M, int C, int ldx, const flo
                             float* ab, float* stats, float* ws, int64_t ws_bytes, void* stream);
 extern "C" int ssc_bn_finalize(const float* partial, int nblk, int C, int64_t M, const float* scale, const float* offset,
                                float eps, float* ab, float* stats, void* stream);
-
-// conv + batch-statistics norm fold of its output.  When the launch finishes every output tile in one workgroup with the
-// vector epilogue (uniform-tap kernel, no split-K slabs, 16-byte aligned rows, not the 128x128 tile whose C image leaves no
-// LDS for the reduction) the per-column sums come out of the conv epilogue; otherwise the output is read back once.
-extern "C" int ssc_conv_forward_bn(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, const float* scale,
-                                   const float* offset, float eps, float* ab, float* stats, void* stream) {
-    ssc_conv_desc d = *dp;
-    d.stat_partial = nullptr;
-    d.sb_x = nullptr;
-    d.sb2_x = nullptr;
-    d.stat_mode = 0;
-    const long M = (long)d.NB * d.PH * d.PW;
-    const long Mall = M * d.nphase;
-    bool fused = false;
-    int64_t ws_conv = ws_bytes;
-    // (the streaming kernels are dispatched BEHIND the one-output head, the few-output and the few-channel kernels in
-    // ssc_conv_forward: a descriptor those take must not be promised rows only a streaming kernel writes)
-    const bool earlier = ssc_head1_forward_supported(dp) || ssc_head1_dgrad_supported(dp) || ssc_conv_narrow_supported(dp) ||
-                         ssc_conv_fewchan_supported(dp);
-    if (!earlier && ws != nullptr && d.Nstore == d.ldc &&
-        (ssc_conv_pw1x1_supported(&d) || ssc_conv_c3x3_supported(&d) || ssc_conv_s2n16_supported(&d) ||
-         ssc_conv_tr4_tiny_supported(&d) || ssc_conv_fewchan7_supported(&d) || ssc_conv_tr4n16_supported(&d))) {
-        // the streaming kernels take the statistics as per-lane sums over the tiles a workgroup walks: one row per walker
-        const int nblk = ssc_conv_pw1x1_supported(&d) ? ssc_conv_pw1x1_walkers(&d)
-                         : (ssc_conv_c3x3_supported(&d) ? ssc_conv_c3x3_walkers(&d)
-                            : (ssc_conv_s2n16_supported(&d) ? ssc_conv_s2n16_walkers(&d)
-                               : (ssc_conv_tr4_tiny_supported(&d) ? ssc_conv_tr4_tiny_blocks(&d)
-                                  : (ssc_conv_fewchan7_supported(&d) ? ssc_conv_fewchan7_walkers(&d) : ssc_conv_tr4n16_rows(&d)))));
-        const int64_t need = (int64_t)nblk * 2 * d.Nstore * 4;
-        if (need <= ws_bytes) {
-            d.stat_partial = ws;
-            const int rc = ssc_conv_forward(&d, ws, ws_bytes, stream);
-            if (rc != 0) return rc;
-            return ssc_bn_finalize(d.stat_partial, nblk, d.Nstore, Mall, scale, offset, eps, ab, stats, stream);
-        }
-    }
-    const bool streaming = ssc_conv_pw1x1_supported(&d) || ssc_conv_c3x3_supported(&d) || ssc_conv_s2n16_supported(&d) ||
-                           ssc_conv_tr4_tiny_supported(&d) || ssc_conv_fewchan7_supported(&d) ||
-                           ssc_conv_tr4n16_supported(&d);     // rows per walker, not per tile
-    if (!streaming && ws != nullptr && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && d.epi == 0 &&
-        !d.accumulate && d.Nstore == d.ldc && ((d.Nstore & 3) == 0) && ((reinterpret_cast<unsigned long>(d.out) & 15) == 0) &&
-        (fwd_is_ut(d) || fwd_is_utg(d) || (d.bmode == 0 && fwd_is_rowtap(d)))) {
-        const Plan p = plan_fwd(d, ws_bytes, true);
-        if (p.cfg >= 0 && p.splitk == 1) {
-            const long mt = (M + FWD_CFGS[p.cfg].BM - 1) / FWD_CFGS[p.cfg].BM;
-            const int64_t need = (int64_t)mt * d.nphase * 2 * d.Nstore * 4;
-            const int64_t reserve = (need + 255) & ~(int64_t)255;
-            if (reserve * 4 <= ws_bytes) {     // the partial rows sit at the end of the workspace, the conv keeps the rest
-                ws_conv = (ws_bytes - reserve) & ~(int64_t)255;
-                const Plan p2 = plan_fwd(d, ws_conv, true);
-                if (p2.cfg == p.cfg && p2.splitk == 1) {
-                    d.stat_partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ws_conv);
-                    fused = true;
-                    const int rc = ssc_conv_forward(&d, ws, ws_conv, stream);
-                    if (rc != 0) return rc;
-                    return ssc_bn_finalize(d.stat_partial, (int)(mt * d.nphase), d.Nstore, Mall, scale, offset, eps, ab, stats,
-                                           stream);
-                }
-            }
-        }
-    }
-    // split-K launches (few rows, long K: the bottlenecks' 3x3 / 4x4 convs at the low resolutions, encoder_5): the statistics ride
-    // in the slab sum (slab_reduce4_stats_kernel) -- slab sum + fold instead of slab sum + statistics pass + fold
-    if (!streaming && ws != nullptr && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && slab_stats_ok(d) &&
-        !(ssc_head1_forward_supported(dp) || ssc_head1_dgrad_supported(dp))) {
-        const Plan p = plan_fwd(d, ws_bytes, true);
-        if (p.cfg >= 0 && p.splitk > 1 && p.ts_s <= 1) {
-            const int nblk = slab_stats_blocks(Mall, d.ldc);
-            const int64_t reserve = (((int64_t)nblk * 2 * d.Nstore * 4) + 255) & ~(int64_t)255;
-            ws_conv = (ws_bytes - reserve) & ~(int64_t)255;
-            const Plan p2 = plan_fwd(d, ws_conv, true);
-            if (ws_conv > 0 && p2.cfg == p.cfg && p2.splitk == p.splitk && p2.ts_s <= 1) {
-                d.stat_partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ws_conv);
-                const int rc = ssc_conv_forward(&d, ws, ws_conv, stream);
-                if (rc != 0) return rc;
-                return ssc_bn_finalize(d.stat_partial, nblk, d.Nstore, Mall, scale, offset, eps, ab, stats, stream);
-            }
-            d.stat_partial = nullptr;
-        }
-    }
-    (void)fused;
-    const int rc = ssc_conv_forward(&d, ws, ws_bytes, stream);
-    if (rc != 0) return rc;
-    return ssc_bn_stats(d.out, Mall, d.Nstore, d.ldc, scale, offset, eps, ab, stats, ws, ws_bytes, stream);
-}
-
-// conv whose output g is the gradient w.r.t. act(a*x+b) of a batch-statistics-normed tensor x ([rows][ldx], laid out like
-// the output): when the launch qualifies (as ssc_conv_forward_bn) the two per-channel sums of the norm's backward come out of
-// the epilogue as rows of `partial` ([rows][2][Nstore], caller's buffer of at least nphase * ceil(M / 64) rows) and *nrows is
-// their count; otherwise *nrows = 0 and the caller takes the sums with the separate pass (ssc_bn_act_backward).
-extern "C" int ssc_conv_forward_bnbwd(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, const float* x, int ldx,
-                                      const float* ab, const float* stats, int act, float* partial, int64_t partial_bytes,
-                                      int* nrows, void* stream) {
-    ssc_conv_desc d = *dp;
-    d.stat_partial = nullptr;
-    d.sb_x = nullptr;
-    d.sb2_x = nullptr;
-    d.stat_mode = 0;
-    *nrows = 0;
-    const long M = (long)d.NB * d.PH * d.PW;
-    const bool earlier = ssc_head1_forward_supported(dp) || ssc_head1_dgrad_supported(dp) || ssc_conv_narrow_supported(dp) ||
-                         ssc_conv_fewchan_supported(dp);        // dispatched in front of the streaming kernels
-    if (!earlier && partial != nullptr && x != nullptr && ab != nullptr && stats != nullptr && d.Nstore == d.ldc &&
-        (ssc_conv_c3x3_supported(&d) || ssc_conv_s2n16_supported(&d))) {
-        // streaming kernels: the two sums as per-lane sums, one row per walker
-        const int nblk = ssc_conv_c3x3_supported(&d) ? ssc_conv_c3x3_walkers(&d) : ssc_conv_s2n16_walkers(&d);
-        if ((int64_t)nblk * 2 * d.Nstore * 4 <= partial_bytes) {
-            d.stat_partial = partial;
-            d.sb_x = x; d.sb_ldx = ldx; d.sb_ab = ab; d.sb_stats = stats; d.sb_act = act;
-            *nrows = nblk;
-            return ssc_conv_forward(&d, ws, ws_bytes, stream);
-        }
-    }
-    if (ws != nullptr && partial != nullptr && x != nullptr && ab != nullptr && stats != nullptr &&
-        !ssc_conv_c3x3_supported(&d) && !ssc_conv_s2n16_supported(&d) && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && d.epi == 0 && !d.accumulate &&
-        d.bias == nullptr && d.Nstore == d.ldc &&
-        d.Nn == d.Nstore && ((d.Nstore & 3) == 0) && ((ldx & 3) == 0) && ((reinterpret_cast<unsigned long>(d.out) & 15) == 0) &&
-        ((reinterpret_cast<unsigned long>(x) & 15) == 0) &&
-        (fwd_is_ut(d) || fwd_is_utg(d) || (d.bmode == 0 && fwd_is_rowtap(d)))) {
-        const Plan p = plan_fwd(d, ws_bytes, true);
-        if (p.cfg >= 0 && p.splitk == 1) {
-            const long mt = (M + FWD_CFGS[p.cfg].BM - 1) / FWD_CFGS[p.cfg].BM;
-            if ((int64_t)mt * d.nphase * 2 * d.Nstore * 4 <= partial_bytes) {
-                d.stat_partial = partial;
-                d.sb_x = x; d.sb_ldx = ldx; d.sb_ab = ab; d.sb_stats = stats; d.sb_act = act;
-                *nrows = (int)(mt * d.nphase);
-            }
-        }
-    }
-    return ssc_conv_forward(&d, ws, ws_bytes, stream);
-}
-
 // mru_ops.hip
 extern "C" int ssc_minmax_hw(const float* x, int ld, int N, int P, int C, float* mnmx, float* workspace, int64_t workspace_bytes,
                              void* stream);
 extern "C" int ssc_minmax_finalize(const float* part, int nsplit, int N, int C, float* mnmx, void* stream);
 
-// conv (+ bias + lrelu) whose output's per-sample, per-channel extrema are wanted (the MRU gates): the per-tile minima / maxima
-// out of the epilogue when the launch qualifies as for ssc_conv_forward_bn and no tile straddles two samples
-extern "C" int ssc_conv_forward_minmax(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, float* mnmx, void* stream) {
+// ---- riders: a reduction over the output that a launch takes along (ssc_conv_forward_bn, _bnbwd, _bnbwd2, _minmax).  One
+// decision, rider_decide, for the four entry points and for ssc_conv_rider_plan ----
+static int fwd_launch(int early, const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, void* stream);
+static int fwd_desc_error(const ssc_conv_desc& d);
+
+// what the tile epilogue needs of a launch before it carries a rider, beyond the uniform-tap form, whole 16-byte aligned
+// rows (Nstore == ldc), no accumulation and a plan without split-K
+struct RiderReq {
+    bool rowtap;        // the row-tap form will do as well
+    bool epi2;          // the lrelu epilogue (epi 2) beside none
+    bool bias;          // a bias
+    bool all_real;      // Nn == Nstore required
+    bool whole_tiles;   // nphase == 1 and a sample's positions whole row tiles (P % BM == 0)
+    bool bn128;         // column tile of at most 128
+    bool caller_rows;   // the rows go to the caller's buffers (else to the end of the workspace)
+    bool round256;      // the workspace tail is reserved in multiples of 256 bytes
+};
+static const RiderReq RIDER_REQ[4] = {
+    /* SSC_RIDER_BN     */ {true, false, true, false, false, false, false, true},
+    /* SSC_RIDER_BNBWD  */ {true, false, false, true, false, false, true, false},
+    /* SSC_RIDER_BNBWD2 */ {false, false, false, true, false, true, true, false},
+    /* SSC_RIDER_MINMAX */ {false, true, true, true, true, false, false, false}};
+
+// the norm-backward sites of a launch: all there (and the column split a legal one), rows of x addressable by float4, columns
+// and capacity in bytes of either site's rows.  The riders without sites: {true, true}
+struct RiderSites {
+    bool present, aligned;
+    int cols[2];
+    int64_t cap[2];
+};
+static RiderSites rider_sites(const ssc_conv_desc& d, int rider, const ssc_bnbwd_site* s0, const ssc_bnbwd_site* s1, int C0) {
+    auto there = [](const ssc_bnbwd_site* s) { return s != nullptr && s->x && s->ab && s->stats && s->partial; };
+    auto al = [](const ssc_bnbwd_site* s) { return (s->ldx & 3) == 0 && (reinterpret_cast<unsigned long>(s->x) & 15) == 0; };
+    if (rider == SSC_RIDER_BNBWD) {
+        if (!there(s0)) return {false, false, {0, 0}, {0, 0}};
+        return {true, al(s0), {d.Nstore, 0}, {s0->partial_bytes, 0}};
+    }
+    if (rider == SSC_RIDER_BNBWD2) {
+        const int C1 = d.Nstore - C0;
+        if (!there(s0) || !there(s1) || C0 <= 0 || C1 <= 0 || (C0 % 128) != 0 || (C1 & 3) != 0) return {false, false, {0, 0}, {0, 0}};
+        return {true, al(s0) && al(s1), {C0, C1}, {s0->partial_bytes, s1->partial_bytes}};
+    }
+    return {true, true, {0, 0}, {0, 0}};
+}
+
+static bool tile_epilogue_ok(const ssc_conv_desc& d, const RiderReq& q) {
+    return (d.epi == 0 || (q.epi2 && d.epi == 2)) && !d.accumulate && (q.bias || d.bias == nullptr) && d.Nstore == d.ldc &&
+           (!q.all_real || d.Nn == d.Nstore) && (d.Nstore & 3) == 0 && (reinterpret_cast<unsigned long>(d.out) & 15) == 0 &&
+           (!q.whole_tiles || d.nphase == 1) && (fwd_is_ut(d) || fwd_is_utg(d) || (q.rowtap && d.bmode == 0 && fwd_is_rowtap(d)));
+}
+
+struct RiderPlan {
+    int path, kernel, rows, home;       // SSC_RIDER_PATH_*, FWD_*, rows of partial results, SSC_RIDER_ROWS_*
+    int64_t ws_conv;                    // workspace bytes left to the conv
+};
+// d: the launch with no rider field set.  Pure: the entry points and the query get the same answer.
+static RiderPlan rider_decide(const ssc_conv_desc& d, int rider, bool have_ws, int64_t ws_bytes, const RiderSites& s) {
+    const RiderReq& q = RIDER_REQ[rider];
+    const int k = fwd_early_kernel(&d, have_ws, ws_bytes);
+    const RiderPlan plain = {SSC_RIDER_PATH_PLAIN, k, 0, SSC_RIDER_ROWS_NONE, ws_bytes};
+    auto caller_fits = [&](long rows) {
+        return (int64_t)rows * 2 * s.cols[0] * 4 <= s.cap[0] && (int64_t)rows * 2 * s.cols[1] * 4 <= s.cap[1];
+    };
+    // the kernel once the rider's fields are set: rows of the table that refuse them stand aside
+    const int under = fwd_early_kernel(&d, have_ws, ws_bytes, 1u << rider);
+    if (under != FWD_TILED) {
+        const FwdKernel& e = FWD_EARLY[under - 1];
+        if (under != k || !(e.carries & (1u << rider)) || d.Nstore != d.ldc || !s.present) return plain;
+        // a streaming kernel: per-lane sums over the tiles a workgroup walks, one row per walker
+        const int rows = e.rows(&d);
+        if (q.caller_rows ? caller_fits(rows) : have_ws && (int64_t)rows * 2 * d.Nstore * 4 <= ws_bytes)
+            return {SSC_RIDER_PATH_STREAM, k, rows, q.caller_rows ? SSC_RIDER_ROWS_CALLER : SSC_RIDER_ROWS_WS_HEAD, ws_bytes};
+        return plain;
+    }
+    // the tiles.  Split-K launches (few rows, long K: encoder_5, the bottlenecks' convs at the low resolutions) take batch
+    // statistics in the slab sum instead (slab_reduce4_stats_kernel)
+    const bool tile_ok = s.present && s.aligned && tile_epilogue_ok(d, q);
+    const bool slab_ok = rider == SSC_RIDER_BN && k == FWD_TILED && slab_stats_ok(d);
+    if (!have_ws || !(tile_ok || slab_ok)) return plain;
+    const Plan p = plan_fwd(d, ws_bytes, true);
+    if (p.cfg < 0 || !(p.splitk == 1 ? tile_ok : slab_ok && p.ts_s <= 1)) return plain;
+    const long P = (long)d.PH * d.PW, M = (long)d.NB * P;
+    const TileCfg& t = FWD_CFGS[p.cfg];
+    if (p.splitk == 1 && ((q.whole_tiles && (P % t.BM) != 0) || (q.bn128 && t.BN > 128))) return plain;
+    const long rows = p.splitk == 1 ? (M + t.BM - 1) / t.BM * d.nphase : slab_stats_blocks(M * d.nphase, d.ldc);
+    if (q.caller_rows)
+        return caller_fits(rows) ? RiderPlan{SSC_RIDER_PATH_TILE, FWD_TILED, (int)rows, SSC_RIDER_ROWS_CALLER, ws_bytes} : plain;
+    // the rows sit at the end of the workspace and the conv plans again with the rest: it must keep its tile and its split
+    // (the two fit rules are the riders' own: unifying them would change which launches fuse)
+    const int64_t need = (int64_t)rows * 2 * d.Nstore * 4;
+    const int64_t reserve = (q.round256 || p.splitk > 1) ? (need + 255) & ~(int64_t)255 : need;
+    if (p.splitk == 1 && reserve * 4 > ws_bytes) return plain;
+    const int64_t ws_conv = (ws_bytes - reserve) & ~(int64_t)255;
+    const Plan p2 = plan_fwd(d, ws_conv, true);
+    if (p2.cfg != p.cfg || p2.splitk != p.splitk || (p.splitk > 1 && (ws_conv <= 0 || p2.ts_s > 1))) return plain;
+    return {p.splitk == 1 ? SSC_RIDER_PATH_TILE : SSC_RIDER_PATH_SLAB, FWD_TILED, (int)rows, SSC_RIDER_ROWS_WS_TAIL, ws_conv};
+}
+
+// the launch's own copy with the rider fields clear (callers leave them so; a stale one must not reach a kernel)
+static ssc_conv_desc rider_clean(const ssc_conv_desc* dp) {
     ssc_conv_desc d = *dp;
     d.stat_partial = nullptr;
     d.sb_x = nullptr;
     d.sb2_x = nullptr;
     d.stat_mode = 0;
-    const long P = (long)d.PH * d.PW;
-    const long M = (long)d.NB * P;
-    if (ws != nullptr && d.nphase == 1 && !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) &&
-        (d.epi == 0 || d.epi == 2) && !d.accumulate && d.Nstore == d.ldc && d.Nn == d.Nstore && ((d.Nstore & 3) == 0) &&
-        ((reinterpret_cast<unsigned long>(d.out) & 15) == 0) && (fwd_is_ut(d) || fwd_is_utg(d))) {
-        const Plan p = plan_fwd(d, ws_bytes, true);
-        if (p.cfg >= 0 && p.splitk == 1 && (P % FWD_CFGS[p.cfg].BM) == 0) {
-            const long mt = M / FWD_CFGS[p.cfg].BM;
-            const int64_t need = (int64_t)mt * 2 * d.Nstore * 4;
-            if (need * 4 <= ws_bytes) {
-                const int64_t ws_conv = (ws_bytes - need) & ~(int64_t)255;
-                const Plan p2 = plan_fwd(d, ws_conv, true);
-                if (p2.cfg == p.cfg && p2.splitk == 1) {
-                    d.stat_partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ws_conv);
-                    d.stat_mode = 1;
-                    const int rc = ssc_conv_forward(&d, ws, ws_conv, stream);
-                    if (rc != 0) return rc;
-                    return ssc_minmax_finalize(d.stat_partial, (int)(P / FWD_CFGS[p.cfg].BM), d.NB, d.Nstore, mnmx, stream);
-                }
-            }
-        }
-    }
-    const int rc = ssc_conv_forward(&d, ws, ws_bytes, stream);
+    return d;
+}
+static float* rider_ws_rows(const RiderPlan& r, float* ws) {
+    if (r.home == SSC_RIDER_ROWS_WS_HEAD) return ws;
+    return r.home == SSC_RIDER_ROWS_WS_TAIL ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + r.ws_conv) : nullptr;
+}
+
+extern "C" int ssc_conv_rider_plan(const ssc_conv_desc* dp, int rider, int64_t ws_bytes, const ssc_bnbwd_site* site0,
+                                   const ssc_bnbwd_site* site1, int C0, int64_t* out5) {
+    if (rider < SSC_RIDER_BN || rider > SSC_RIDER_MINMAX) return -1;
+    const ssc_conv_desc d = rider_clean(dp);
+    const int err = fwd_desc_error(d);
+    if (err != 0) return err;
+    const RiderPlan r = rider_decide(d, rider, ws_bytes > 0, ws_bytes, rider_sites(d, rider, site0, site1, C0));
+    out5[0] = r.path; out5[1] = r.kernel; out5[2] = r.rows; out5[3] = r.home; out5[4] = r.ws_conv;
+    return 0;
+}
+
+// conv + batch-statistics norm fold of its output: the per-column sums out of the launch where rider_decide finds a way,
+// otherwise the output is read back once
+extern "C" int ssc_conv_forward_bn(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, const float* scale,
+                                   const float* offset, float eps, float* ab, float* stats, void* stream) {
+    ssc_conv_desc d = rider_clean(dp);
+    const RiderPlan r = rider_decide(d, SSC_RIDER_BN, ws != nullptr, ws_bytes, rider_sites(d, SSC_RIDER_BN, nullptr, nullptr, 0));
+    const long Mall = (long)d.NB * d.PH * d.PW * d.nphase;
+    d.stat_partial = rider_ws_rows(r, ws);
+    const int rc = fwd_launch(r.kernel, &d, ws, r.ws_conv, stream);
     if (rc != 0) return rc;
-    return ssc_minmax_hw(d.out, d.ldc, d.NB, (int)P, d.Nstore, mnmx, ws, ws_bytes, stream);
+    if (r.path == SSC_RIDER_PATH_PLAIN)
+        return ssc_bn_stats(d.out, Mall, d.Nstore, d.ldc, scale, offset, eps, ab, stats, ws, ws_bytes, stream);
+    return ssc_bn_finalize(d.stat_partial, r.rows, d.Nstore, Mall, scale, offset, eps, ab, stats, stream);
+}
+
+static void rider_fill_site(ssc_conv_desc& d, const ssc_bnbwd_site& s) {
+    d.stat_partial = s.partial;
+    d.sb_x = s.x; d.sb_ldx = s.ldx; d.sb_ab = s.ab; d.sb_stats = s.stats; d.sb_act = s.act;
+}
+
+// conv whose output g is the gradient w.r.t. act(a*x+b) of a batch-statistics-normed tensor x ([rows][ldx], laid out like
+// the output): the two per-channel sums of the norm's backward come out of the launch as rows of `partial` ([rows][2][Nstore])
+// and *nrows is their count; or *nrows = 0 and the caller takes the sums with the separate pass (ssc_bn_act_backward).
+extern "C" int ssc_conv_forward_bnbwd(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, const float* x, int ldx,
+                                      const float* ab, const float* stats, int act, float* partial, int64_t partial_bytes,
+                                      int* nrows, void* stream) {
+    ssc_conv_desc d = rider_clean(dp);
+    const ssc_bnbwd_site s = {x, ab, stats, partial, partial_bytes, ldx, act};
+    const RiderPlan r = rider_decide(d, SSC_RIDER_BNBWD, ws != nullptr, ws_bytes, rider_sites(d, SSC_RIDER_BNBWD, &s, nullptr, 0));
+    if (r.path != SSC_RIDER_PATH_PLAIN) rider_fill_site(d, s);
+    *nrows = r.rows;
+    return fwd_launch(r.kernel, &d, ws, r.ws_conv, stream);
+}
+
+// conv (+ bias + lrelu) whose output's per-sample, per-channel extrema are wanted (the MRU gates): the per-tile minima / maxima
+// out of the epilogue where no tile straddles two samples
+extern "C" int ssc_conv_forward_minmax(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, float* mnmx, void* stream) {
+    ssc_conv_desc d = rider_clean(dp);
+    const RiderPlan r = rider_decide(d, SSC_RIDER_MINMAX, ws != nullptr, ws_bytes, rider_sites(d, SSC_RIDER_MINMAX, nullptr, nullptr, 0));
+    d.stat_partial = rider_ws_rows(r, ws);
+    d.stat_mode = r.path == SSC_RIDER_PATH_TILE ? 1 : 0;
+    const int rc = fwd_launch(r.kernel, &d, ws, r.ws_conv, stream);
+    if (rc != 0) return rc;
+    if (r.path == SSC_RIDER_PATH_TILE) return ssc_minmax_finalize(d.stat_partial, r.rows / d.NB, d.NB, d.Nstore, mnmx, stream);
+    return ssc_minmax_hw(d.out, d.ldc, d.NB, d.PH * d.PW, d.Nstore, mnmx, ws, ws_bytes, stream);
 }
 
 extern "C" int ssc_conv_forward_bnbwd2(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, const ssc_bnbwd_site* s0,
                                        const ssc_bnbwd_site* s1, int C0, int* nrows, void* stream) {
-    ssc_conv_desc d = *dp;
-    d.stat_partial = nullptr;
-    d.sb_x = nullptr;
-    d.sb2_x = nullptr;
-    d.stat_mode = 0;
-    *nrows = 0;
-    const long M = (long)d.NB * d.PH * d.PW;
-    const int C1 = d.Nstore - C0;
-    if (ws != nullptr && s0 != nullptr && s1 != nullptr && s0->x && s1->x && s0->ab && s1->ab && s0->stats && s1->stats &&
-        s0->partial && s1->partial && C0 > 0 && C1 > 0 && (C0 % 128) == 0 && (C1 & 3) == 0 &&
-        !ssc_conv_narrow_supported(dp) && !ssc_conv_fewchan_supported(dp) && d.epi == 0 && !d.accumulate &&
-        d.bias == nullptr && d.Nstore == d.ldc && d.Nn == d.Nstore && ((s0->ldx | s1->ldx) & 3) == 0 &&
-        ((reinterpret_cast<unsigned long>(d.out) | reinterpret_cast<unsigned long>(s0->x) |
-          reinterpret_cast<unsigned long>(s1->x)) & 15) == 0 &&
-        (fwd_is_ut(d) || fwd_is_utg(d))) {
-        const Plan p = plan_fwd(d, ws_bytes, true);
-        if (p.cfg >= 0 && p.splitk == 1 && FWD_CFGS[p.cfg].BN <= 128) {
-            const long mt = (M + FWD_CFGS[p.cfg].BM - 1) / FWD_CFGS[p.cfg].BM;
-            if ((int64_t)mt * d.nphase * 2 * C0 * 4 <= s0->partial_bytes && (int64_t)mt * d.nphase * 2 * C1 * 4 <= s1->partial_bytes) {
-                d.stat_partial = s0->partial;
-                d.sb_x = s0->x; d.sb_ldx = s0->ldx; d.sb_ab = s0->ab; d.sb_stats = s0->stats; d.sb_act = s0->act;
-                d.stat_partial2 = s1->partial; d.sb2_col0 = C0;
-                d.sb2_x = s1->x; d.sb2_ldx = s1->ldx; d.sb2_ab = s1->ab; d.sb2_stats = s1->stats; d.sb2_act = s1->act;
-                *nrows = (int)(mt * d.nphase);
-            }
-        }
+    ssc_conv_desc d = rider_clean(dp);
+    const RiderPlan r = rider_decide(d, SSC_RIDER_BNBWD2, ws != nullptr, ws_bytes, rider_sites(d, SSC_RIDER_BNBWD2, s0, s1, C0));
+    if (r.path != SSC_RIDER_PATH_PLAIN) {
+        rider_fill_site(d, *s0);
+        d.stat_partial2 = s1->partial; d.sb2_col0 = C0;
+        d.sb2_x = s1->x; d.sb2_ldx = s1->ldx; d.sb2_ab = s1->ab; d.sb2_stats = s1->stats; d.sb2_act = s1->act;
     }
-    return ssc_conv_forward(&d, ws, ws_bytes, stream);
+    *nrows = r.rows;
+    return fwd_launch(r.kernel, &d, ws, r.ws_conv, stream);
 }
 
 extern "C" int ssc_sk_configure(int timeout_ms, int test_withhold) {
@@ -1897,24 +1899,6 @@ static int fwd_desc_error(const ssc_conv_desc& d) {
         return -3;
     return 0;
 }
-// the kernels dispatched in front of the tiled ones, in the order ssc_conv_forward asks them
-enum { FWD_TILED = 0, FWD_HEAD1, FWD_HEAD1_DGRAD, FWD_NARROW, FWD_FEWCHAN, FWD_PW1X1, FWD_C3X3, FWD_S2N16, FWD_TR4_TINY, FWD_FEWCHAN7,
-       FWD_TR4N16 };
-static int fwd_early_kernel(const ssc_conv_desc* dp, bool have_ws, int64_t ws_bytes) {
-    const ssc_conv_desc& d = *dp;
-    // the one-output patch head over a 512-channel tensor and its data gradient (head1.hip): streaming kernels
-    if (have_ws && ssc_head1_forward_supported(dp) && (int64_t)d.NB * d.x.H * d.x.W * 16 * 4 <= ws_bytes) return FWD_HEAD1;
-    if (ssc_head1_dgrad_supported(dp)) return FWD_HEAD1_DGRAD;
-    if (ssc_conv_narrow_supported(dp)) return FWD_NARROW;           // <= 4 output channels
-    if (ssc_conv_fewchan_supported(dp)) return FWD_FEWCHAN;         // 4x4 stride-2 over 4 or 8 input channels
-    if (ssc_conv_pw1x1_supported(dp)) return FWD_PW1X1;             // 1x1 expansion of a bottleneck: K <= 128, streaming kernel
-    if (ssc_conv_c3x3_supported(dp)) return FWD_C3X3;               // 3x3 of a bottleneck at 16 / 32 channels (either filter orientation)
-    if (ssc_conv_s2n16_supported(dp)) return FWD_S2N16;             // 4x4 stride-2 conv 64 -> <= 16 channels: 16-column MFMA, K split over the waves
-    if (ssc_conv_tr4_tiny_supported(dp)) return FWD_TR4_TINY;       // k = 4 stride-2 transposed conv, <= 4 channels in and out: a thread per lattice pixel
-    if (ssc_conv_fewchan7_supported(dp)) return FWD_FEWCHAN7;       // 7x7 stride-2 conv over the (padded) image channels
-    if (ssc_conv_tr4n16_supported(dp)) return FWD_TR4N16;           // k = 4 stride-2 transposed conv 256 -> <= 16 channels: 16-column MFMA, a phase per workgroup
-    return FWD_TILED;
-}
 static bool fwd_bf_plain(const ssc_conv_desc& d) {
     const bool plain0 = d.x.ab0 == nullptr && d.x.act == SSC_ACT_NONE;
     const bool plain1 = d.x.C1 == 0 || (d.x.ab1 == nullptr && (d.x.act1 >= 0 ? d.x.act1 : d.x.act) == SSC_ACT_NONE);
@@ -1935,11 +1919,16 @@ extern "C" int ssc_conv_bf_plan(const ssc_conv_desc* dp, int64_t ws_bytes, int* 
 }
 
 extern "C" int ssc_conv_forward(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, void* stream) {
+    return fwd_launch(fwd_early_kernel(dp, ws != nullptr, ws_bytes), dp, ws, ws_bytes, stream);
+}
+
+// the launch on the kernel the route chose (FWD_*)
+static int fwd_launch(int early, const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, void* stream) {
     const ssc_conv_desc& d = *dp;
     hipStream_t st = (hipStream_t)stream;
     const int err = fwd_desc_error(d);
     if (err != 0) return err;
-    switch (fwd_early_kernel(dp, ws != nullptr, ws_bytes)) {
+    switch (early) {
         case FWD_HEAD1: return ssc_head1_forward(dp, ws, ws_bytes, stream);
         case FWD_HEAD1_DGRAD: return ssc_head1_dgrad(dp, stream);
         case FWD_NARROW: {
@@ -2077,32 +2066,28 @@ static Plan plan_wgrad(const ssc_wgrad_desc& d, int64_t ws_bytes, bool have_ws) 
     return best;
 }
 
-extern "C" int ssc_conv_wgrad_kernel_name(const ssc_wgrad_desc* dp, char* buf, int len) {
-    static const char* names[5] = {"conv_wgrad<128x128>", "conv_wgrad<64x128>", "conv_wgrad<128x64>",
-                                   "conv_wgrad<64x64>", "conv_wgrad<128x32>"};
-    if (ssc_head1_wgrad_supported(dp)) {
-        copy_name("head1_wgrad", buf, len);
-        return 0;
-    }
-    if (ssc_conv_wgrad128_supported(dp)) {
-        copy_name(ssc_conv_wgrad128_bf_selected(dp) ? "conv_wgrad128_bf16x6<128x128>" : "conv_wgrad128<128x128>", buf, len);
-        return 0;
-    }
-    if (ssc_conv_wgn16_supported(dp)) {
-        copy_name(dp->TH == 3 ? "conv_wgn16<3x3>" : "conv_wgn16<4x4>", buf, len);
-        return 0;
-    }
-    const Plan p = plan_wgrad(*dp, (int64_t)1 << 40, true);
-    copy_name(names[p.cfg < 0 ? 0 : p.cfg], buf, len);
-    return 0;
-}
-
 // which kernel takes a filter-gradient launch: 0 conv_wgrad_kernel, 1 head1, 2 wgrad128, 3 wgn16
 static int wgrad_route(const ssc_wgrad_desc* dp, bool have_ws, int64_t ws_bytes) {
     if (have_ws && ws_bytes >= (int64_t)16 * 512 * 4 && ssc_head1_wgrad_supported(dp)) return 1;     // the one-output patch head
     if (ssc_conv_wgrad128_supported(dp)) return 2;                                                  // the large layers
     // 16 output channels, 3x3 x 16 or 4x4 x 64 gathered: 16-column MFMA, when the workspace can hold a slab
     if (have_ws && ssc_conv_wgn16_supported(dp) && ssc_conv_wgn16_fits(dp, ws_bytes)) return 3;
+    return 0;
+}
+
+extern "C" int ssc_conv_wgrad_kernel_name(const ssc_wgrad_desc* dp, char* buf, int len) {
+    static const char* names[5] = {"conv_wgrad<128x128>", "conv_wgrad<64x128>", "conv_wgrad<128x64>",
+                                   "conv_wgrad<64x64>", "conv_wgrad<128x32>"};
+    const int64_t ample = (int64_t)1 << 40;
+    switch (wgrad_route(dp, true, ample)) {
+        case 1: copy_name("head1_wgrad", buf, len); break;
+        case 2: copy_name(ssc_conv_wgrad128_bf_selected(dp) ? "conv_wgrad128_bf16x6<128x128>" : "conv_wgrad128<128x128>", buf, len); break;
+        case 3: copy_name(dp->TH == 3 ? "conv_wgn16<3x3>" : "conv_wgn16<4x4>", buf, len); break;
+        default: {
+            const Plan p = plan_wgrad(*dp, ample, true);
+            copy_name(names[p.cfg < 0 ? 0 : p.cfg], buf, len);
+        }
+    }
     return 0;
 }
 

@@ -170,6 +170,7 @@ SIGNATURES = {
     'ssc_conv_forward_kernel_name': [C.POINTER(ConvDesc), C.c_char_p, _I],
     'ssc_conv_wgrad_kernel_name': [C.POINTER(WgradDesc), C.c_char_p, _I],
     'ssc_conv_forward_plan': [C.POINTER(ConvDesc), _L, C.POINTER(C.c_int)],
+    'ssc_conv_rider_plan': [C.POINTER(ConvDesc), _I, _L, C.POINTER(BnBwdSite), C.POINTER(BnBwdSite), _I, C.POINTER(C.c_int64)],
     'ssc_conv_wgrad_plan': [C.POINTER(WgradDesc), _L, C.POINTER(C.c_int)],
     'ssc_conv_wgrad128_plan': [C.POINTER(WgradDesc), _L, C.POINTER(C.c_int)],
     'ssc_conv_bf_plan': [C.POINTER(ConvDesc), _L, C.POINTER(C.c_int)],
@@ -738,6 +739,21 @@ class BnBwdSums(object):
 CO_RUN = False
 
 
+RIDER_PATHS = ('plain', 'stream', 'tile', 'slab')       # SSC_RIDER_PATH_*
+RIDER_LOG = None        # a list: _run_conv appends (rider, path) of every launch with a rider before it launches (tests)
+
+
+def rider_plan(d, rider, ws_bytes, site0=None, site1=None, C0=0):
+    """What the library will do with a conv that takes a reduction along (ssc_conv_rider_plan; host only): (path of RIDER_PATHS,
+    kernel, rows, where the rows lie, workspace bytes left to the conv).  rider: 0 bn, 1 bnbwd, 2 bnbwd2, 3 minmax."""
+    out = (C.c_int64 * 5)()
+    check(lib().ssc_conv_rider_plan(C.byref(d), rider, ws_bytes, C.byref(site0) if site0 is not None else None,
+                                    C.byref(site1) if site1 is not None else None, C0, out), 'ssc_conv_rider_plan')
+    if RIDER_LOG is not None:
+        RIDER_LOG.append((('bn', 'bnbwd', 'bnbwd2', 'minmax')[rider], RIDER_PATHS[out[0]]))
+    return (RIDER_PATHS[out[0]],) + tuple(out[1:])
+
+
 def _run_conv(d, bn=None, bnbwd=None, minmax=None):
     """bn = (scale, offset, ab, stats[, eps]): also fold the batch-statistics norm of the conv's output (the whole
     [rows, ldc] output must be the normed tensor).  bnbwd = BnBwdSums.take(act): the output is a gradient w.r.t. that
@@ -763,6 +779,8 @@ def _run_conv(d, bn=None, bnbwd=None, minmax=None):
                 st.partial_bytes, st.ldx, st.act = part.numel() * 4, sm.x2d.stride(0), act
                 sites.append(st)
             n = C.c_int(0)
+            if RIDER_LOG is not None:
+                rider_plan(d, 2, ws.numel() * 4, sites[0], sites[1], C0)
             check(lib().ssc_conv_forward_bnbwd2(C.byref(d), ptr(ws), ws.numel() * 4, C.byref(sites[0]), C.byref(sites[1]), C0,
                                                 C.byref(n), stream_ptr()), 'ssc_conv_forward_bnbwd2')
             for sm in (s0, s1):
@@ -780,9 +798,13 @@ def _run_conv(d, bn=None, bnbwd=None, minmax=None):
             assert sums.x2d.shape[0] == d.NB * d.OH * d.OW, (sums.x2d.shape, d.NB, d.OH, d.OW)
             part = sums.buf[sums.rows:]
             n = C.c_int(0)
-            check(lib().ssc_conv_forward_bnbwd(C.byref(d), ptr(ws), ws.numel() * 4, ptr(sums.x2d), sums.x2d.stride(0),
-                                               ptr(sums.ab), ptr(sums.stats), act, ptr(part), part.numel() * 4,
-                                               C.byref(n), stream_ptr()), 'ssc_conv_forward_bnbwd')
+            st = BnBwdSite()
+            st.x, st.ab, st.stats, st.partial = (ptr(t).value for t in (sums.x2d, sums.ab, sums.stats, part))
+            st.partial_bytes, st.ldx, st.act = part.numel() * 4, sums.x2d.stride(0), act
+            if RIDER_LOG is not None:
+                rider_plan(d, 1, ws.numel() * 4, st)
+            check(lib().ssc_conv_forward_bnbwd(C.byref(d), ptr(ws), ws.numel() * 4, st.x, st.ldx, st.ab, st.stats, st.act,
+                                               st.partial, st.partial_bytes, C.byref(n), stream_ptr()), 'ssc_conv_forward_bnbwd')
             sums.sources += 1
             if n.value > 0:
                 assert part.shape[1] == C2
@@ -791,12 +813,16 @@ def _run_conv(d, bn=None, bnbwd=None, minmax=None):
                 sums.missed += 1
         elif minmax is not None:        # mnmx [N,2,C] <- per-sample extrema of the (activated) output, out of the epilogue
             assert minmax.shape == (d.NB, 2, d.Nstore) and minmax.is_contiguous(), (minmax.shape, d.NB, d.Nstore)
+            if RIDER_LOG is not None:
+                rider_plan(d, 3, ws.numel() * 4)
             check(lib().ssc_conv_forward_minmax(C.byref(d), ptr(ws), ws.numel() * 4, ptr(minmax), stream_ptr()),
                   'ssc_conv_forward_minmax')
         elif bn is None:
             check(lib().ssc_conv_forward(C.byref(d), ptr(ws), ws.numel() * 4, stream_ptr()), 'ssc_conv_forward')
         else:
             eps = bn[4] if len(bn) > 4 else 1e-5
+            if RIDER_LOG is not None:
+                rider_plan(d, 0, ws.numel() * 4)
             check(lib().ssc_conv_forward_bn(C.byref(d), ptr(ws), ws.numel() * 4, ptr(bn[0]), ptr(bn[1]), eps, ptr(bn[2]),
                                             ptr(bn[3]), stream_ptr()), 'ssc_conv_forward_bn')
 

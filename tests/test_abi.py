@@ -112,6 +112,7 @@ NOT_KERNEL_TESTED = {
     'ssc_bf16_prepare': 'allocates per-device constants, launches nothing',
     'ssc_conv_forward_kernel_name': 'host only: name of the tile configuration',
     'ssc_conv_forward_plan': 'host only: the launch plan of a descriptor',
+    'ssc_conv_rider_plan': 'host only: which path a conv with a reduction on its epilogue takes',
     'ssc_conv_fewchan_supported': 'host only: dispatch predicate',
     'ssc_conv_narrow_supported': 'host only: dispatch predicate',
     'ssc_conv_wgrad128_supported': 'host only: dispatch predicate',

@@ -466,15 +466,23 @@ def test_norm_backward_sums_from_dgrad_epilogues(n, h, c, expect_fused):
             if fused else None
         g1 = torch.full((n, h, h, c), float('nan'), device='cuda')
         g2 = torch.full((n, h, h, c), float('nan'), device='cuda')
-        hip.conv_dgrad(hip.View(nhwc(dy1).cuda()), w1.cuda(), 2, 1, g1, bnbwd=(sums.take(2) if fused else None))
-        hip.deconv_dgrad(hip.View(nhwc(dy2).cuda()), f2.cuda(), g2, bnbwd=(sums.take(1) if fused else None))
+        hip.RIDER_LOG = log = []        # what ssc_conv_rider_plan says of each launch with a rider, asked before it launches
+        try:
+            hip.conv_dgrad(hip.View(nhwc(dy1).cuda()), w1.cuda(), 2, 1, g1, bnbwd=(sums.take(2) if fused else None))
+            hip.deconv_dgrad(hip.View(nhwc(dy2).cuda()), f2.cuda(), g2, bnbwd=(sums.take(1) if fused else None))
+        finally:
+            hip.RIDER_LOG = None
         dx = torch.full((n * h * h, c), float('nan'), device='cuda')
         ds, do = torch.empty(c, device='cuda'), torch.empty(c, device='cuda')
         hip.bn_act_backward(x2d, ab, st, g1.view(-1, c), 2, dx, g2=g2.view(-1, c), act2=1, dscale=ds, doffset=do, pre=sums)
         if fused:
             assert sums.sources == 2
+            assert len(log) == 2 and sum(p == 'plain' for _, p in log) == sums.missed, (log, sums.missed)
             if expect_fused:        # both launches finish their tiles in one workgroup each: the rows come from the epilogues
                 assert sums.missed == 0 and sums.rows > 0
+                assert log == [('bnbwd', 'tile'), ('bnbwd', 'tile')], log
+        else:
+            assert log == []
         res[fused] = (dx, ds, do)
         close(nchw(dx.view(n, h, h, c)), x.grad, tol=5e-4)
         close(ds, scale.grad, tol=5e-4)

@@ -4,6 +4,8 @@
   slab_reduce4_stats_kernel batch statistics taken by the split-K slab sum
   ssc_block_out_backward    the backward through a bottleneck's output (residual_util.py:103-109, 138-146, 165-167)
   ssc_conv_forward_minmax   the MRU gates' per-sample extrema out of the conv epilogue (mru.py:407-415)"""
+import contextlib
+
 import pytest
 import torch
 
@@ -15,6 +17,16 @@ pytestmark = pytest.mark.gpu
 def _hip():
     from sketchyscenecolorization_amd import hip
     return hip
+
+
+@contextlib.contextmanager
+def rider_log(hip):
+    """[(rider, path)] of the launches made inside: what ssc_conv_rider_plan says of each, asked before it launches."""
+    hip.RIDER_LOG = log = []
+    try:
+        yield log
+    finally:
+        hip.RIDER_LOG = None
 
 
 def nhwc(t):
@@ -62,7 +74,9 @@ def test_merged_decoder_dgrad_delivers_both_sites_sums():
                           torch.zeros(hip.BnBwdSums.rows_needed(n * h * h), 2 * x.shape[-1], device='cuda'))
             for x, (ab, st) in zip(xs, tabs)]
     g01 = torch.full((n, h, h, c0 + c1), float('nan'), device='cuda')
-    hip.deconv_dgrad(hip.View(nhwc(dy).cuda()), f.cuda(), g01, n_off=0, nn=c0 + c1, bnbwd=[sums[0].take(1), sums[1].take(1)])
+    with rider_log(hip) as log:
+        hip.deconv_dgrad(hip.View(nhwc(dy).cuda()), f.cuda(), g01, n_off=0, nn=c0 + c1, bnbwd=[sums[0].take(1), sums[1].take(1)])
+    assert log == [('bnbwd2', 'tile')], log
     assert all(sm.sources == 1 and sm.missed == 0 and sm.rows > 0 for sm in sums)       # both came out of the epilogue
     r01 = g01.view(-1, c0 + c1)
     for k, (x, ref_x, ref_s, ref_o) in enumerate(((xs[0], xd_, sd, od), (xs[1], xe_, se, oe))):
@@ -219,7 +233,9 @@ def test_gate_extrema_from_the_conv_epilogue(n, h, ci, co, ties):
     hip.conv_forward(hip.View(x), w, 1, 0, plain, bias=b, epi=2, same=True)
     out = torch.full((n, h, h, co), float('nan'), device='cuda')
     mm = torch.full((n, 2, co), float('nan'), device='cuda')
-    hip.conv_forward(hip.View(x), w, 1, 0, out, bias=b, epi=2, same=True, minmax=mm)
+    with rider_log(hip) as log:
+        hip.conv_forward(hip.View(x), w, 1, 0, out, bias=b, epi=2, same=True, minmax=mm)
+    assert log == [('minmax', 'plain' if h == 12 else 'tile')], log       # a 12 x 12 sample is not whole row tiles
     assert torch.equal(out, plain)
     flat = plain.view(n, h * h, co)
     assert torch.equal(mm[:, 0], flat.amin(1)) and torch.equal(mm[:, 1], flat.amax(1))
@@ -252,7 +268,9 @@ def test_bottleneck_expansion_conv_streaming_kernel(m_hw, k, act, with_bn):
     out = torch.full((n, h, w_, co), float('nan'), device=dev)
     scale, offset = (1.0 + 0.1 * rnd(co, seed=55)).to(dev), (0.1 * rnd(co, seed=56)).to(dev)
     a2, s2 = torch.empty(2 * co, device=dev), torch.empty(2 * co, device=dev)
-    hip.conv_forward(xv, wt, 1, 0, out, bn=(scale, offset, a2, s2) if with_bn else None)
+    with rider_log(hip) as log:
+        hip.conv_forward(xv, wt, 1, 0, out, bn=(scale, offset, a2, s2) if with_bn else None)
+    assert log == ([('bn', 'stream')] if with_bn else []), log
     z = (ab[:k] * x + ab[k:]).double()
     z = torch.relu(z) if act == 1 else (torch.maximum(z, 0.2 * z) if act == 2 else z)
     ref = z.view(-1, k) @ wt.view(k, co).double()
@@ -318,7 +336,11 @@ def test_bottleneck_3x3_conv_streaming_kernel(shape, c, act):
     hip.bn_stats(x2d, scale, offset, abx, st)
     sums = hip.BnBwdSums(x2d, abx, st, torch.zeros(hip.BnBwdSums.rows_needed(n * h * w_), 2 * c, device=dev))
     g = torch.full((n, h, w_, c), float('nan'), device=dev)
-    hip.conv_dgrad(hip.View(dy), wt, 1, 1, g, bnbwd=sums.take(max(act, 1)))
+    with rider_log(hip) as log:
+        hip.conv_dgrad(hip.View(dy), wt, 1, 1, g, bnbwd=sums.take(max(act, 1)))
+    # the streaming kernel carries the sums where it takes the launch; below that the tiles may, and the rows say whether they did
+    assert log == [('bnbwd', 'stream')] if n * h * w_ >= 16384 else log in ([('bnbwd', 'tile')], [('bnbwd', 'plain')]), log
+    assert (log[0][1] == 'plain') == (sums.missed == 1), (log, sums.missed)
     want_g = nhwc(F.conv_transpose2d(nchw(dy).double(), wt.double().permute(3, 2, 0, 1), padding=1))
     close(g, want_g, tol=2e-5)
     if n * h * w_ >= 16384:
@@ -406,7 +428,9 @@ def test_transposed_conv_data_gradient_on_the_16_column_mfma():
     hip.bn_stats(x2d, scale, offset, abx, st)
     sums = hip.BnBwdSums(x2d, abx, st, torch.zeros(hip.BnBwdSums.rows_needed(n * h * w_), 2 * ci, device=dev))
     g = torch.full((n, h, w_, ci), float('nan'), device=dev)
-    hip.deconv_dgrad(hip.View(dy), f, g, bnbwd=sums.take(1))
+    with rider_log(hip) as log:
+        hip.deconv_dgrad(hip.View(dy), f, g, bnbwd=sums.take(1))
+    assert log == [('bnbwd', 'stream')], log
     want = nhwc(F.conv2d(nchw(dy).double(), f.double().permute(3, 2, 0, 1), stride=2, padding=1))
     close(g, want, tol=2e-5)
     assert sums.sources == 1 and sums.missed == 0 and 0 < sums.rows <= 512
