@@ -78,6 +78,9 @@ FLAGS = [
                                'segment}/val and captions/val.json are coloured one per pass with the current weights and scored '
                                'on the GPU (MAE, PSNR, SSIM; region accuracy and IoU) into log/validation.jsonl'),
     ('val_records', int, 0, None, 'held-out records a pass takes, the first ones in caption-file order (0 = all)'),
+    ('val_preview', int, 0, None, 'every held-out pass (needs --val_freq F > 0) also writes log/previews/step_<n>.png and .json: a '
+                                  'row for each of the first K scenes with its foreground, the output of the pass as --mode test '
+                                  'would write it, and its background, made on the GPU; at most 32; 0 = none'),
     ('scene_dir', str, 'examples', None, '--mode scene: directory with sketches/, inner_masks/ and seg_data/'),
     ('image_id', str, None, None, '--mode scene: the scene, <id> of sketches/<id>.png'),
     ('instruction', str, None, None, "--mode scene: what to paint, e.g. 'the sky is pink'"),
@@ -422,6 +425,8 @@ def main(argv=None):
     if args.val_freq and args.mode != 'train':
         raise ValueError('--val_freq %d scores a held-out set during --mode train: test mode scores its own images with --metrics 1'
                          % args.val_freq)
+    from sketchyscenecolorization_amd import preview
+    preview.checked_count(args.val_preview, args.val_freq, args.mode)
     defaults = {name: default for name, _t, default, _c, _h in FLAGS}
     if args.mode == 'scene':
         if args.resume_from == '':

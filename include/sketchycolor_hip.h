@@ -878,6 +878,27 @@ int ssc_unpool2(const float* x, const uint8_t* code, int N, int h, int w, int C,
 int ssc_scene_change_hist_u8(const uint8_t* prev, const uint8_t* next, const uint8_t* inner, int H, int W, int64_t* out,
                              void* stream);
 
+/* --- the preview sheets of the held-out passes (preview.hip): preview.py; DESIGN.md section 8.15 --- */
+/* src uint8 [N,H,W,3], sheet uint8 [SH,SW,3]: image n becomes a tile of H/s x W/s pixels whose first pixel is sheet pixel
+ * (top + n*pitch, left).  Every byte of a tile is the mean of its s x s source bytes, rounded half up in integers:
+ * (sum + s*s/2) / (s*s); s = 1 copies; s = 6 is what a 384-pixel record is reduced by for a 64-pixel generator.  Nothing
+ * outside the N tiles is written; integers only: the same bits on every run.
+ * 4-byte loads and stores when src and the tile's first byte are on 4-byte boundaries and W and SW are multiples of 4 (then
+ * every row is), single bytes otherwise and for the W/s % 4 pixels at the end of a tile row.
+ * -1, and nothing is launched: a null pointer; N < 1 (or > 65535); a side outside 1 .. 65536; s not one of 1, 2, 4, 6, 8 or not a
+ * divisor of H and of W; a negative top, left or pitch; a tile that leaves the sheet; pitch < H/s with N > 1; src overlapping
+ * sheet.  No pointer needs an alignment (the library's -3 does not occur). */
+int ssc_sheet_tiles_u8(const uint8_t* src, int N, int H, int W, int s, uint8_t* sheet, int SH, int SW, int top, int left, int pitch,
+                       void* stream);
+/* One tile from a sketch uint8 [S,S,3] whose pixels are coloured first.  pred uint8 [S,S] or NULL (ssc_match_finish's predicts:
+ * a pixel is predicted when its byte is not 0); labels uint8 [S,S] with lut uint8 [256], or both NULL (a pixel is a target when
+ * lut[labels[p]] != 0, as in ssc_match_score).  Predicted and target: (0,170,0); predicted only: (230,0,0); target only:
+ * (0,90,255); neither: the sketch's three bytes.  With pred NULL a target pixel is (0,170,0), with labels NULL a predicted one.
+ * The coloured image is reduced as by ssc_sheet_tiles_u8 (N = 1, H = W = S) into the tile at (top, left).  Refusals as there,
+ * also for labels without lut or lut without labels and for pred, labels or lut overlapping sheet. */
+int ssc_sheet_overlay_u8(const uint8_t* sketch, const uint8_t* pred, const uint8_t* labels, const uint8_t* lut, int S, int s,
+                         uint8_t* sheet, int SH, int SW, int top, int left, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

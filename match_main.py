@@ -23,6 +23,9 @@ match_train.py): one (scene, caption) of sentence_instanc
 --scene_cache device keeps every scene's sketch and label map on the device, --scene_cache features the frozen backbone's output
 too (sketchyscenecolorization_amd/match_cache.py); --val_freq F scores sentence_instance_val.json every F iterations with the
 weights of the moment and appends a line to <log_root>/match_validation.jsonl (match_validation.py).
+--val_preview K also writes <log_root>/match_previews/iter_<n>.png and .json at every pass: the first K captions' predictions and
+targets over their sketches, made on the device (preview.py); the run is that without it, bit for bit.
+--mode eval --visualized 1 writes <visualize_pred_base_dir>/<split>/<id>/<k>_gt.png and <k>_out.png for every caption.
 
     python match_main.py --mode train --train_backbone 1 --backbone_snapshot models/SketchyScene_DeepLabv2 \
         --data_base_dir ../data --captions_base_dir data
@@ -66,6 +69,9 @@ EVAL_FLAGS = [
     ('augment_seed', int, None, 'eval: add random colour attributes to the captions as training does, drawn from random.Random(K); '
                                 'default: the captions as they are in the file'),
     ('eval_result_root', str, 'outputs/eval_results', 'eval: where the result block and eval_<split>.json go'),
+    ('visualized', int, 0, "eval: 1 to write every caption's target and prediction over the sketch as <k>_gt.png and <k>_out.png "
+                           '(plain images: the caption is in captions.json beside them, not drawn as a title)'),
+    ('visualize_pred_base_dir', str, 'outputs/visualization', 'eval: where --visualized 1 writes <split>/<image id>/<k>_{gt,out}.png'),
 ]
 TRAIN_FLAGS = [
     ('backbone_snapshot', str, '', 'train: a TensorFlow checkpoint (directory or prefix) with ResNet/*, for a fresh run'),
@@ -93,6 +99,8 @@ TRAIN_FLAGS = [
                                 "map on the device, read once) or 'features' (and the frozen backbone's output of every scene)"),
     ('val_freq', int, 0, 'train: score sentence_instance_val.json every N iterations and after the last one (0: never)'),
     ('val_scenes', int, 0, 'train: only the first N scenes of sentence_instance_val.json are scored (0: all of them)'),
+    ('val_preview', int, 0, 'train: every held-out pass also writes <log_root>/match_previews/iter_<n>.png and .json, the first K '
+                            'captions of the pass as overlays on their sketches (0: none; at most 32; needs --val_freq)'),
 ]
 SCENE_CACHE_MODES = ('off', 'device', 'features')
 
@@ -210,6 +218,8 @@ def checked_eval_arguments(args):
         raise ValueError('--max_scenes %d: a count, 0 for every scene' % args.max_scenes)
     if args.eval_result_root == '':
         raise ValueError('--eval_result_root is empty')
+    if args.visualized and args.visualize_pred_base_dir == '':
+        raise ValueError('--visualize_pred_base_dir is empty')
     config, vocab = checked_model(args)
     prefix = checked_snapshot_variables(args.snapshot, config)
     scenes = match_eval.read_captions(args.captions_base_dir, args.dataset)
@@ -235,8 +245,12 @@ def evaluate(args, config=None, predicts_out=None):
     model.load_tf_checkpoint(prefix)
     rng = None if args.augment_seed is None else random.Random(args.augment_seed)
     kept = [] if predicts_out is not None else None
+    visualizer = None
+    if args.visualized:
+        from sketchyscenecolorization_amd import preview
+        visualizer = preview.EvalVisualizer(args.visualize_pred_base_dir, args.dataset, cfg.size, model.device)
     totals, records = match_eval.evaluate(model, vocab, scenes, args.data_base_dir, args.dataset, args.seg_data_dir,
-                                          mask_ap=bool(args.mask_ap), rng=rng, keep_predicts=kept, log=print)
+                                          mask_ap=bool(args.mask_ap), rng=rng, keep_predicts=kept, log=print, visualizer=visualizer)
     model.close()
     block = totals.block(prefix)
     print(block)
@@ -265,7 +279,7 @@ def checked_train_arguments(args):
     """--mode train: every bad argument and every missing file of the whole caption file is a ValueError here, before any weight
     is read or anything is written.  -> (config, vocab, training tuples, the snapshot to resume from or None, the backbone's
     checkpoint prefix or None)."""
-    from sketchyscenecolorization_amd import match_eval, match_train, matching, tf_checkpoint
+    from sketchyscenecolorization_amd import match_eval, match_train, matching, preview, tf_checkpoint
     for name, want, why in (('train_fusion_var_only', 1, 'the backbone is trained with --train_backbone 1'),
                             ('training_ignore_bg', 1, 'the loss over every pixel is not built'),
                             ('batch_size', 1, 'the reference trains one tuple per iteration'), ('gpus', 1, 'one device'),
@@ -294,6 +308,7 @@ def checked_train_arguments(args):
                          'use --scene_cache device')
     if args.val_freq < 0 or args.val_scenes < 0:
         raise ValueError('--val_freq %d, --val_scenes %d: counts, 0 for never and for every scene' % (args.val_freq, args.val_scenes))
+    preview.checked_count(args.val_preview, args.val_freq)
     if vocab[matching.PAD] != 0:
         raise ValueError('--vocab_file %r: <pad> is word %d; training needs it as word 0 (the embedding gradient skips row 0)'
                          % (args.vocab_file, vocab[matching.PAD]))
@@ -343,7 +358,7 @@ def build_caches(args, cfg, model, vocab, tuples):
               % (len(cache), cache.scene_bytes, cache.feature_bytes, cache.build_seconds))
     if val_scenes is not None:
         validation = match_validation.MatchValidation(model, vocab, val_scenes, args.data_base_dir,
-                                                      beside=cache.nbytes if cache is not None else 0)
+                                                      beside=cache.nbytes if cache is not None else 0, preview=args.val_preview)
         print('validation cache: %d scenes, %d captions, %d bytes on the device' % (len(validation.cache), validation.captions,
                                                                                  validation.nbytes))
     return cache, validation
@@ -429,6 +444,10 @@ def main(argv=None, config=None, predicts_out=None):
     """``config``: a MatchConfig other than the released model's (the tests' small models); its size, vocabulary size and
     text length must be the flags'.  ``predicts_out``: --mode eval only, see ``evaluate``."""
     args = build_parser().parse_args(argv)
+    from sketchyscenecolorization_amd import preview
+    if args.mode != 'train':        # (--mode train holds it against --val_freq, among its own checks)
+        preview.checked_count(args.val_preview, args.val_freq, args.mode)
+    preview.checked_visualized(args.visualized, args.mode)
     if args.mode == 'eval':
         return evaluate(args, config, predicts_out)
     if args.mode == 'train':

@@ -18,6 +18,9 @@ The pass, which is the definition of the numbers it writes:
   * hip.seg_confusion counts (label, prediction) pairs of the region logits against the staged labels;
   * the [S,5] float64 rows and the [S,K*K+1] int64 rows come to the host once, behind the last scene.
 It draws nothing from ``random`` or a torch generator and writes no parameter, optimizer slot or scalars.jsonl entry.
+--val_preview K: the first K scenes also go into a preview sheet -- the foreground, hip.bg_finish_u8 of the pass's own float image
+(the bytes --mode test would write) and the background (preview.BackgroundPreview) -- written as
+log/previews/step_<n>.png and .json; it reads the pass's buffers and writes only its own.
 """
 import json
 import os
@@ -89,8 +92,12 @@ def printed_line(line, summary):
 class HeldOutEvaluator(object):
     """``run(trainer)`` is one pass over ``cache``; the slot rows are uploaded once, here."""
 
-    def __init__(self, cache, names, seg_classes):
+    def __init__(self, cache, names, seg_classes, preview=0):
         assert len(names) == len(cache)
+        self.preview = None
+        if preview:
+            from .preview import BackgroundPreview
+            self.preview = BackgroundPreview(cache, preview)
         self.cache, self.names, self.K = cache, list(names), int(seg_classes)
         dev, S = cache.device, len(cache)
         H, W = cache.fg.shape[1:3]
@@ -115,6 +122,8 @@ class HeldOutEvaluator(object):
             sf, sb, ss = (int(v) for v in c.slots[i])
             hip.image_metrics_bg_f32(gctx['image'], c.fg[sf:sf + 1], c.bg[sb:sb + 1], c.seg[ss:ss + 1], out=self.rows[i:i + 1])
             hip.seg_confusion(gctx['region_logits'], self.labels, self.K, out=self.conf[i:i + 1])
+            if self.preview is not None:
+                self.preview.scene(i, gctx['image'])
         rows = self.rows.cpu().numpy()      # the two copies to the host (the first waits for the pass)
         conf = self.conf.cpu().numpy()
         return rows, conf, time.time() - t0
@@ -126,7 +135,7 @@ def open_held_out(p, scenes_class, tr, beside=0):
     if scenes is None:
         return None
     cache = build_cache(scenes, keep, tr.losses.device, beside)
-    return HeldOutEvaluator(cache, scene_names(scenes, keep), p['seg_classes'])
+    return HeldOutEvaluator(cache, scene_names(scenes, keep), p['seg_classes'], preview=p.get('val_preview', 0))
 
 
 def run_pass(ev, tr, log_dir):
@@ -136,5 +145,7 @@ def run_pass(ev, tr, log_dir):
     line, summary = validation_line(tr.global_step, ev.names, rows, conf, seconds)
     with open(os.path.join(log_dir, 'validation.jsonl'), 'a') as fp:
         fp.write(dumps_line(line))
+    if ev.preview is not None:      # the sheet comes to the host behind the rows
+        ev.preview.write(log_dir, tr.global_step, ev.names)
     print(printed_line(line, summary))
     return line

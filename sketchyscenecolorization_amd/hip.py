@@ -274,6 +274,8 @@ SIGNATURES = {
     'ssc_max_pool2_argmax': [_P, _P, _I, _I, _I, _I, _P, _P, _P],
     'ssc_unpool2': [_P, _P, _I, _I, _I, _I, _P, _P],
     'ssc_scene_change_hist_u8': [_P, _P, _P, _I, _I, _P, _P],
+    'ssc_sheet_tiles_u8': [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P],
+    'ssc_sheet_overlay_u8': [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P],
 }
 
 
@@ -1519,6 +1521,50 @@ def scene_change_hist_u8(prev_u8, new_u8, inner_u8, out=None):
         raise ValueError('scene_change_hist_u8: out must be 256 contiguous int64 on the device of the images')
     check(lib().ssc_scene_change_hist_u8(ptr(prev_u8), ptr(new_u8), ptr(inner_u8), h, w, ptr(out), stream_ptr()), 'scene_change_hist_u8')
     return out
+
+
+# ---------------------------------------------------------------------------
+# the preview sheets of the held-out passes (csrc/preview.hip; preview.py)
+# ---------------------------------------------------------------------------
+def _sheet_dims(what, sheet_u8):
+    if not isinstance(sheet_u8, torch.Tensor) or sheet_u8.dtype != torch.uint8 or not sheet_u8.is_contiguous() or not sheet_u8.is_cuda \
+            or sheet_u8.dim() != 3 or sheet_u8.shape[2] != 3:
+        raise ValueError('%s: the sheet must be a contiguous uint8 [SH,SW,3] tensor on the device' % what)
+    return int(sheet_u8.shape[0]), int(sheet_u8.shape[1])
+
+
+def sheet_tiles_u8(src_u8, s, sheet_u8, top, left, pitch=0):
+    """src uint8 [N,H,W,3] -> N tiles of H/s x W/s pixels in sheet uint8 [SH,SW,3], image n at row top + n*pitch, column left;
+    every byte the s x s box mean rounded half up in integers.  Nothing else of the sheet is written.  ValueError, before any
+    launch, for tensors of another kind; the placement is the entry point's to refuse (RuntimeError with its code)."""
+    sh, sw = _sheet_dims('sheet_tiles_u8', sheet_u8)
+    if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8 or not src_u8.is_contiguous() or src_u8.dim() != 4 \
+            or src_u8.shape[3] != 3 or src_u8.device != sheet_u8.device:
+        raise ValueError('sheet_tiles_u8: src must be a contiguous uint8 [N,H,W,3] tensor on the device of the sheet')
+    n, h, w = (int(v) for v in src_u8.shape[:3])
+    check(lib().ssc_sheet_tiles_u8(ptr(src_u8), n, h, w, int(s), ptr(sheet_u8), sh, sw, int(top), int(left), int(pitch), stream_ptr()),
+          'sheet_tiles_u8')
+    return sheet_u8
+
+
+def sheet_overlay_u8(sketch_u8, pred_u8, labels_u8, lut_u8, s, sheet_u8, top, left):
+    """sketch uint8 [S,S,3], coloured by pred uint8 [S,S] (or None) and lut[labels] (labels uint8 [S,S] and lut uint8 [256], or
+    both None) -- green where both, red where predicted only, blue where target only -- and reduced by s into the tile of sheet
+    uint8 [SH,SW,3] at (top, left).  ValueError, before any launch, for tensors of another kind."""
+    sh, sw = _sheet_dims('sheet_overlay_u8', sheet_u8)
+    if not isinstance(sketch_u8, torch.Tensor) or sketch_u8.dtype != torch.uint8 or not sketch_u8.is_contiguous() or sketch_u8.dim() != 3 \
+            or sketch_u8.shape[0] != sketch_u8.shape[1] or sketch_u8.shape[2] != 3 or sketch_u8.device != sheet_u8.device:
+        raise ValueError('sheet_overlay_u8: sketch must be a contiguous uint8 [S,S,3] tensor on the device of the sheet')
+    size = int(sketch_u8.shape[0])
+    if (labels_u8 is None) != (lut_u8 is None):
+        raise ValueError('sheet_overlay_u8: labels and lut go together')
+    for name, t, shape in (('pred', pred_u8, (size, size)), ('labels', labels_u8, (size, size)), ('lut', lut_u8, (256,))):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous()
+                              or tuple(t.shape) != shape or t.device != sheet_u8.device):
+            raise ValueError('sheet_overlay_u8: %s must be a contiguous uint8 %s tensor on the device of the sheet' % (name, list(shape)))
+    check(lib().ssc_sheet_overlay_u8(ptr(sketch_u8), ptr(pred_u8), ptr(labels_u8), ptr(lut_u8), size, int(s), ptr(sheet_u8), sh, sw,
+                                     int(top), int(left), stream_ptr()), 'sheet_overlay_u8')
+    return sheet_u8
 
 
 # ---------------------------------------------------------------------------

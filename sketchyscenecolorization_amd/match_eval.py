@@ -404,10 +404,13 @@ def score_caption(predicts_d, scene, inst_indices, mask_ap=True):
     return out
 
 
-def evaluate(model, vocab, scenes, data_base_dir, split, seg_data_dir, mask_ap=True, rng=None, keep_predicts=None, log=None):
+def evaluate(model, vocab, scenes, data_base_dir, split, seg_data_dir, mask_ap=True, rng=None, keep_predicts=None, log=None,
+             visualizer=None):
     """scenes: read_captions' list (cut to what is wanted).  The backbone runs once per scene, the head once per caption.
     ``rng``: a random.Random for augment_caption, None for the captions as they are.  ``keep_predicts``: a list that receives
-    every caption's predicts (host, uint8).  -> (Totals, per-caption records)."""
+    every caption's predicts (host, uint8).  ``visualizer``: a preview.EvalVisualizer that writes every caption's target and
+    prediction over the sketch (--visualized 1); it reads predicts and the label map and changes no number.
+    -> (Totals, per-caption records)."""
     size, T = model.cfg.size, model.cfg.max_len
     totals, records = Totals(mask_ap), []
     for n, (image_id, pairs) in enumerate(scenes):
@@ -419,7 +422,9 @@ def evaluate(model, vocab, scenes, data_base_dir, split, seg_data_dir, mask_ap=T
         for _caption, idx in pairs:
             caption_labels(image_id, idx, scene.n_inst, scene.area)         # a bad caption is refused before the backbone runs
         feat, stroke = model.features(gt['sketch'])
-        for caption, inst_indices in pairs:
+        if visualizer is not None:
+            visualizer.scene(image_id, gt['sketch'])
+        for k, (caption, inst_indices) in enumerate(pairs):
             text = caption if rng is None else augment_caption(caption, rng)
             indices, seq_len = matching.preprocess_sentence(text, vocab, T)
             _up, predicts = model.predict(feat, stroke, indices, seq_len)
@@ -432,4 +437,10 @@ def evaluate(model, vocab, scenes, data_base_dir, split, seg_data_dir, mask_ap=T
             records.append(rec)
             if keep_predicts is not None:
                 keep_predicts.append(predicts.cpu().numpy())
+            if visualizer is not None:
+                from . import match_train
+                visualizer.caption(k, caption, text, predicts, scene.labels,
+                                   match_train.caption_lut(caption_labels(image_id, inst_indices, scene.n_inst, scene.area)))
+    if visualizer is not None:
+        visualizer.finish()
     return totals, records

@@ -67,13 +67,14 @@ class MatchValidation(object):
     are on the device already), sends every caption through match_eval.caption_labels and uploads its tokens and its lut."""
 
     def __init__(self, model, vocab, scenes, data_base_dir, split='val', beside=0,
-                 remedy='score fewer scenes (--val_scenes N) or none (--val_freq 0)'):
+                 remedy='score fewer scenes (--val_scenes N) or none (--val_freq 0)', preview=0):
         import torch
         cfg = model.cfg
         self.model, self.scenes = model, scenes
         self.cache = match_cache.MatchSceneCache(scenes, data_base_dir, split, cfg.size, model.device, beside=beside,
                                                  remedy_scenes=remedy)
         self.plan, toks, luts = [], [], []           # per scene of the file: (its entry, [(row, seq_len), ..])
+        self.texts = []                              # per caption: (scene, caption)
         for image_id, pairs in scenes:
             i = self.cache.index[image_id]
             rows = []
@@ -81,6 +82,7 @@ class MatchValidation(object):
                 labels = match_eval.caption_labels(image_id, inst_indices, int(self.cache.n_inst[i]), self.cache.area[i])
                 indices, seq_len = matching.preprocess_sentence(caption, vocab, cfg.max_len)
                 rows.append((len(toks), int(seq_len)))
+                self.texts.append((str(image_id), caption))
                 toks.append(np.asarray(indices, dtype=np.int32).reshape(-1))
                 luts.append(match_train.caption_lut(labels))
             self.plan.append((i, rows))
@@ -89,20 +91,28 @@ class MatchValidation(object):
         self.lut = torch.from_numpy(np.stack(luts)).to(model.device)
         self.rows = torch.zeros((self.captions, 5), dtype=torch.int64, device=model.device)
         self.nbytes = self.cache.nbytes
+        # --val_preview K: a sheet of the first K captions (preview.py); it reads the pass's buffers and writes only its own
+        self.preview = None
+        if preview:
+            from . import preview as P
+            self.preview = P.MatchPreview(model, self.captions, preview)
 
     def run(self, iteration):
         """One pass with the weights of the moment.  -> the record of ``validation_record``."""
         import torch
         from . import hip
         t0 = time.time()
-        cache, model = self.cache, self.model
+        cache, model, pv = self.cache, self.model, self.preview
         ws = hip.workspace()
         for i, rows in self.plan:
-            feat, _stroke = model.features(cache.sketch[i])
+            feat, stroke = model.features(cache.sketch[i])
             for k, seq_len in rows:
                 pred = model.head(feat, self.tok[k], seq_len)
                 hip.match_score(pred, cache.sketch[i], cache.labels[i], self.lut[k], out=self.rows[k], ws=ws)
+                if pv is not None:
+                    pv.caption(k, pred, stroke, cache.sketch[i], cache.labels[i], self.lut[k])
         host = self.rows.cpu().numpy()                  # the pass's one wait for the device
+        self.last_rows = host
         loss = host[:, 0].copy().view(np.float64)
         return validation_record(iteration, len(self.plan), [(host[k, 1], host[k, 2], host[k, 3], host[k, 4], loss[k])
                                                              for k in range(self.captions)], time.time() - t0)
@@ -111,6 +121,10 @@ class MatchValidation(object):
         record = self.run(iteration)
         with open(os.path.join(log_root, LOG_NAME), 'a') as f:
             f.write(json.dumps(record) + '\n')
+        if self.preview is not None:        # the sheet comes to the host here, behind the rows
+            host = self.last_rows
+            self.preview.write(log_root, iteration, [{'scene': s, 'caption': c, 'I': int(host[k, 1]), 'P': int(host[k, 2]),
+                                                      'A': int(host[k, 3])} for k, (s, c) in enumerate(self.texts[:self.preview.n])])
         if log is not None:
             log(validation_line(record))
         return record

@@ -248,7 +248,7 @@ def train(**kwargs):
             from ..train_validation import HeldOutEvaluator
             val_cache = get_record_cache(val_dir, img, distance_map, device='cuda:%d' % torch.cuda.current_device(),
                                          max_records=(int(getattr(Config, 'val_records', 0) or 0) or None))
-            evaluator = HeldOutEvaluator(val_cache, batch_size)
+            evaluator = HeldOutEvaluator(val_cache, batch_size, preview=int(getattr(Config, 'val_preview', 0) or 0))
             print('held-out cache: %d records, %d bytes (%.1f MB%s) on %s, built in %.1f s; a pass of %d batches every %d iterations'
                   % (len(val_cache), val_cache.nbytes, val_cache.nbytes / 1e6, ', distance maps included' if distance_map else '',
                      val_cache.device, val_cache.build_seconds, len(evaluator.plan), val_freq))
@@ -343,6 +343,8 @@ def train(**kwargs):
                 line, summary = validation_line(i, evaluator.names, evaluator.groups, rows, seconds)
                 val_f.write(json.dumps(line, sort_keys=True) + '\n')
                 val_f.flush()
+                if evaluator.preview is not None:       # --val_preview K: the sheet comes to the host behind the rows
+                    evaluator.preview.write(log_dir, i, evaluator.names, evaluator.groups)
                 print('held-out pass at iteration %d (%.2f s): %s' % (i, seconds, M.all_line(summary)))
             if num_gpu > 1:     # the other ranks wait for rank 0's pass, as they do for its snapshot
                 import torch.distributed as dist

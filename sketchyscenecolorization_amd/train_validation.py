@@ -14,6 +14,10 @@ The pass, which is the definition of the numbers it writes:
   * the generator's noise vectors come from a torch.Generator of the evaluator's own, seeded with ``NOISE_SEED`` at the start
     of every pass: every pass sees the same noise, no generator that training draws from is touched;
   * the [S,5] float64 rows come to the host once, behind the last batch.
+--val_preview K: the batches that hold one of the first K records also put their outputs -- hip.image_postprocess_u8 of the pass's
+own ``tower.infer_nhwc`` rows, the conversion that makes --mode val's PNGs -- into a preview sheet beside the records' sketches
+and targets (preview.ForegroundPreview).  No second forward pass, no draw from a generator, and nothing
+written but the preview's own buffers.
 """
 import time
 
@@ -55,8 +59,12 @@ def validation_line(step, names, groups, rows, seconds):
 class HeldOutEvaluator(object):
     """``run(tower)`` is one pass; the record numbers and class ids are uploaded once, here."""
 
-    def __init__(self, cache, batch_size):
+    def __init__(self, cache, batch_size, preview=0):
         self.cache, self.batch_size = cache, int(batch_size)
+        self.preview = None
+        if preview:
+            from .preview import ForegroundPreview
+            self.preview = ForegroundPreview(cache, preview)
         self.plan = batch_plan(len(cache), batch_size)
         self.names, self.groups = record_names(cache)
         dev = cache.device
@@ -70,14 +78,18 @@ class HeldOutEvaluator(object):
         training has queued there; the caller has settled every pending step."""
         from . import hip
         t0 = time.time()
-        cache = self.cache
+        cache, pv = self.cache, self.preview
         self.gen.manual_seed(NOISE_SEED)
+        if pv is not None:
+            pv.start()
         for a, b in self.plan:
             target, sketch = hip.decode_paired_cached_u8(cache, self.numbers[a:b], cache.size, noise=None)
             noise_vec = pass_noise(self.gen, b - a, cache.device)
             tower.generate(sketch, cache.text[a:b], noise_vec, labels=self.class_id[a:b], clone=False)
             out, coff = tower.infer_nhwc
             hip.image_metrics_f32(out, coff, target, out=self.rows[a:b])
+            if pv is not None:
+                pv.batch(out, coff, a, b)
         rows = self.rows.cpu().numpy()      # the one copy to the host (it waits for the pass)
         hip.check_sk('held-out pass')
         return rows, time.time() - t0
