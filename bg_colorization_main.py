@@ -285,19 +285,13 @@ def bg_colorization(**p):
         os.makedirs(res_dir, exist_ok=True)
         from sketchyscenecolorization_amd import hip
         size = p['image_size']
-        x = torch.empty((1, size, size, 3), dtype=torch.float32, device='cuda')
-        y, xd, cnt = torch.empty_like(x), torch.empty((1, size, size, 8), dtype=torch.float32, device='cuda'), torch.empty(1, device='cuda')
-        lab0 = torch.zeros((1, size, size), dtype=torch.int32, device='cuda')
         names, rows = [], []
         # one image per forward pass whatever --batch_size says: the norms are batch statistics
         for i in range(len(scenes)):
             print('Processing', i, '/', len(scenes))
             fg, bg, tok, lab, fg_name, bg_name = scenes.get(i, is_test=True)
             fg_d = torch.from_numpy(fg).cuda()
-            # the forward pass reads the stage's float inputs only: the foreground stands in for the background and a constant
-            # array for the labels, so nothing but the foreground is uploaded (y, xd and cnt are the kernel's other outputs, unread)
-            hip.bg_stage_u8(fg_d, fg_d, lab0, x, y, xd, cnt)
-            gctx = tr.G.forward(x, tok, None, 'bg')
+            gctx = tr.color_foreground(fg_d, tok)       # nothing but the foreground is uploaded
             seg_path = os.path.join(scenes.dirs['segment'], fg_name)
             inner = None
             if os.path.exists(seg_path):        # paste the foreground (segment value 0) back over the generation
@@ -349,19 +343,9 @@ def bg_colorization(**p):
 
     # the scenes of a step are stacked into pinned staging buffers of the batch shape, allocated once and used in turn (pinning
     # a fresh 1.7 MB array costs 3.5 ms a time; a copy from pageable memory returns only when it has happened, behind the step
-    # that is running).  A buffer is written again only when the copy that last read it has happened (its event).
-    ring, ring_i = {}, [0]
-
-    def staged(parts, slot, dtype):
-        if slot not in ring:
-            shape = (nb,) + tuple(parts[0].shape[1:])
-            ring[slot] = [(torch.empty(shape, dtype=dtype).pin_memory(), torch.cuda.Event()) for _ in range(4)]
-        buf, ev = ring[slot][ring_i[0] % 4]
-        ev.synchronize()
-        view = buf.numpy()
-        for i, a in enumerate(parts):
-            view[i] = a[0]
-        return buf, ev
+    # that is running).  A buffer is written again only when the copy that last read it has happened (pinned_ring.py).
+    from sketchyscenecolorization_amd.pinned_ring import PinnedRing
+    rings = []      # of the foreground, the background and the labels: made at the first step, of the shapes it loads
 
     for step in range(iter_from, p['max_steps']):
         def should(freq):
@@ -375,13 +359,16 @@ def bg_colorization(**p):
         else:
             batch = [scenes.get(i) for i in draw_batch()]
         if cache is None:
-            ring_i[0] += 1
-            fg, ev_fg = staged([b[0] for b in batch], 'fg', torch.uint8)
-            bg, ev_bg = staged([b[1] for b in batch], 'bg', torch.uint8)
-            lab, ev_lab = staged([b[3] for b in batch], 'lab', torch.int32)
+            if not rings:
+                rings = [PinnedRing((nb,) + tuple(batch[0][k].shape[1:]), dt) for k, dt in ((0, torch.uint8), (1, torch.uint8), (3, torch.int32))]
+            fg, bg, lab = [ring.next() for ring in rings]
+            for k, buf in zip((0, 1, 3), (fg, bg, lab)):        # what Scenes.get returns: fg, bg, tokens, labels, names
+                view = buf.numpy()
+                for i, b in enumerate(batch):
+                    view[i] = b[k][0]
             tr.train_step_u8(fg, bg, np.concatenate([b[2] for b in batch], 0), lab)
-            for ev in (ev_fg, ev_bg, ev_lab):
-                ev.record()
+            for ring in rings:
+                ring.queued()
         if should(p['progress_freq']) or should(p['summary_freq']):
             vals = tr.loss_values()
             # tf.train.ExponentialMovingAverage(0.99) of the five losses (:657-658), updated when they are read

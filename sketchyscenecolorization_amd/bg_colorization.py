@@ -16,6 +16,7 @@ statistics, the loss means and the masked-L1 count run over the whole batch -- w
 (tests/test_gpu_residual.py holds the trainer to it at N = 2).  The command line (bg_colorization_main.py of this repository)
 drives ``train_step_u8`` at ``--batch_size N`` and writes test-mode PNGs through ``hip.bg_finish_u8``.
 """
+import contextlib
 import numpy as np
 import os
 
@@ -23,6 +24,7 @@ import torch
 
 from . import hip
 from .params import Buffers, ParamStore
+from .pinned_ring import PinnedRing
 from .residual import ResidualGenerator
 from .step_graphs import FAILED, StepGraphs
 
@@ -73,6 +75,16 @@ def create_residual_generator(generator_inputs, generator_outputs_channels, voca
 # ---------------------------------------------------------------------------------------------------------------
 # training (create_model in train mode, bg_colorization_main.py:516-726)
 # ---------------------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def _beside(side):
+    """The block is issued on the stream ``side``, behind what the current stream holds so far -- or in line when ``side`` is
+    None.  The caller joins: ``main.wait_stream(side)`` where the block's results are read."""
+    if side is not None:
+        side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):       # (of None: the current stream stays)
+        yield
+
+
 class BGTrainer(object):
     """Generator + residual discriminator of the BG module with the reference's losses and optimizer:
 
@@ -147,43 +159,29 @@ class BGTrainer(object):
         M = N * H * W
         L = self.losses
         L.zero_()
-        def real_pass():
+        main = torch.cuda.current_stream()
+        side = self._real_stream if hip.PROFILE is None else None      # per-kernel timing runs everything in line
+        with _beside(side):     # D(real), beside the generator forward
             cr = self.D.forward(xd_real if xd_real is not None else self._pack('xd_real', inputs, targets), 'dr')
             nz = cr['z'].numel()
             dz_r = B.get('dz_r', cr['z'].shape)
             hip.call('ssc_bg_gan_loss', cr['z'], nz, 0, 1.0 / nz, L[0:1], dz_r, 1.0 / nz)
             self.D.backward(cr, dz_r, True, False, accumulate=False)
-            return cr
-
-        side = self._real_stream if hip.PROFILE is None else None      # per-kernel timing runs everything in line
-        if side is not None:
-            main = torch.cuda.current_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                cr = real_pass()
         gctx = self.G.forward(inputs, text, None, 'bg')
         image, logits = gctx['image'], gctx['region_logits']
-        if side is None:
-            cr = real_pass()
         cf = self.D.forward(self._pack('xd_fake', inputs, image), 'df')
-        nz = cr['z'].numel()
         ws = hip.workspace()
         # ---- discriminator loss and gradients (the fake term adds to the loss word and the gradient buffer the real pass wrote)
         if side is not None:
             main.wait_stream(side)
         dz_f = B.get('dz_f', cf['z'].shape)
         hip.call('ssc_bg_gan_loss', cf['z'], nz, 1, 1.0 / nz, L[0:1], dz_f, 1.0 / nz)
-        if side is not None:
-            # the fake pair's backward into the discriminator's gradient buffer is off the critical path (nothing reads it before
-            # the optimizer): on the side stream, beside the generator's loss terms and backward pass.  The two passes through
-            # the same forward context then need gradient scratch of their own: the generator's pass takes the 'dg' set.
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                self.D.backward(cf, dz_f, True, False, accumulate=True)
-            cfg = dict(cf, tag='dg', tape=[dict(rec, tag='dg') for rec in cf['tape']])
-        else:
+        # the fake pair's backward into the discriminator's gradient buffer is off the critical path (nothing reads it before
+        # the optimizer): on the side stream, beside the generator's loss terms and backward pass.  The two passes through
+        # the same forward context then need gradient scratch of their own: the generator's pass takes the 'dg' set.
+        with _beside(side):
             self.D.backward(cf, dz_f, True, False, accumulate=True)
-            cfg = cf
+        cfg = cf if side is None else dict(cf, tag='dg', tape=[dict(rec, tag='dg') for rec in cf['tape']])
         # ---- generator loss and gradients
         dz_g = B.get('dz_g', cf['z'].shape)
         hip.call('ssc_bg_gan_loss', cf['z'], nz, 0, 1.0 / nz, L[2:3], dz_g, self.w_gan / nz)
@@ -192,10 +190,8 @@ class BGTrainer(object):
             count = B.get('l1_count', (1,))
             hip.call('ssc_count_nonzero_i32', labels, M, count, ws, ws.numel() * 4)
         dpre = B.get('dpre', (N, H, W, 4))
-        hip.call('ssc_bg_output_grad', image, targets, labels, count, 1.0, dgan, L[3:4], dpre, M)
-        if self.w_l1 != 1.0:        # the kernel folds the weight into the gradient: run it with the real weight
-            L[3:4].zero_()
-            hip.call('ssc_bg_output_grad', image, targets, labels, count, float(self.w_l1), dgan, L[3:4], dpre, M)
+        # (the kernel folds the weight into the gradient and writes every element of dpre)
+        hip.call('ssc_bg_output_grad', image, targets, labels, count, float(self.w_l1), dgan, L[3:4], dpre, M)
         dlog = B.get('dlog', (N, H, W, 4), zero_on_alloc=True)
         hip.call('ssc_seg_ce_loss', logits, self.seg, labels, M, float(self.w_seg), L[4:5], dlog, 4)
         self.G.backward(gctx, dpre, None, dlogits=dlog)
@@ -232,28 +228,42 @@ class BGTrainer(object):
     def train_step(self, inputs, targets, text, labels_gt):
         """One ``sess.run(model.train)``.  The first call of a shape runs eagerly (it allocates), the second is captured
         into a hipGraph, later ones replay it on the inputs copied into the graph's static tensors."""
-        if not self.use_graphs or hip.PROFILE is not None:
-            gctx = self.gradients(inputs, targets, text, labels_gt)
-            self.apply_gradients()
-            return gctx
-        skey = tuple(inputs.shape)
-        st = self._static.get(skey)
-        if st is None:
-            st = {'inputs': torch.empty_like(inputs.contiguous()), 'targets': torch.empty_like(targets.contiguous()),
-                  'labels': torch.empty(tuple(labels_gt.shape), dtype=torch.int32, device=inputs.device)}
-            self._static[skey] = st
+        key = tuple(inputs.shape)
+        st = self._statics(key, key)
         st['inputs'].copy_(inputs)
         st['targets'].copy_(targets)
         st['labels'].copy_(labels_gt)
-        prep = text if isinstance(text, dict) else self.G.text.prepare(text, 'bg')
-        return self._step(skey + (prep['S'],), lambda: self.gradients(st['inputs'], st['targets'], prep, st['labels']))
+        return self._run(key, st, text)
 
-    def _stage_u8(self, st):
-        """The fused uint8 stage on the static tensors of a shape -> the keyword arguments of ``gradients``."""
-        xd = self.bufs.get('xd_real', tuple(st['fg'].shape[:3]) + (8,), zero_on_alloc=True)
-        count = self.bufs.get('l1_count', (1,))
-        hip.bg_stage_u8(st['fg'], st['bg'], st['labels'], st['inputs'], st['targets'], xd, count)
-        return {'xd_real': xd, 'count': count}
+    def _statics(self, key, shape, extra=dict):
+        """The static tensors of ``key``, made the first time it is seen: what every step reads -- the float ``inputs`` and
+        ``targets`` [N,H,W,3] and the int32 ``labels`` [N,H,W] (zero until written) -- and what ``extra()`` adds for its caller."""
+        if key not in self._static:
+            dev = self.losses.device
+            self._static[key] = dict(extra(), inputs=torch.empty(shape, dtype=torch.float32, device=dev),
+                                     targets=torch.empty(shape, dtype=torch.float32, device=dev),
+                                     labels=torch.zeros(shape[:3], dtype=torch.int32, device=dev))
+        return self._static[key]
+
+    def _run(self, key, st, text, stage=None):
+        """One step on the static tensors ``st`` (inputs, targets, labels): filled by the caller, or made inside the step by the
+        one launch ``stage(st, xd_real, count)``, which also writes the two arrays ``gradients`` then need not make.  Eager when
+        graphs are off and under per-kernel timing; otherwise through ``_step``, one graph per ``key`` and live caption steps."""
+        prep = text if isinstance(text, dict) else self.G.text.prepare(text, 'bg')
+
+        def gradients():
+            made = {}
+            if stage is not None:
+                made = {'xd_real': self.bufs.get('xd_real', tuple(st['inputs'].shape[:3]) + (8,), zero_on_alloc=True),
+                        'count': self.bufs.get('l1_count', (1,))}
+                stage(st, **made)
+            return self.gradients(st['inputs'], st['targets'], prep, st['labels'], **made)
+
+        if not self.use_graphs or hip.PROFILE is not None:
+            gctx = gradients()
+            self.apply_gradients()
+            return gctx
+        return self._step(key + (prep['S'],), gradients)
 
     def train_step_u8(self, fg_u8, bg_u8, text, labels):
         """``train_step`` fed with what the loader produces: fg_u8 / bg_u8 uint8 [N,H,W,3] (foreground = generator input,
@@ -265,50 +275,26 @@ class BGTrainer(object):
         assert fg_u8.dtype == torch.uint8 and bg_u8.dtype == torch.uint8 and fg_u8.shape == bg_u8.shape
         assert fg_u8.dim() == 4 and fg_u8.shape[3] == 3 and tuple(labels.shape) == tuple(fg_u8.shape[:3]), \
             'labels %s for images %s' % (tuple(labels.shape), tuple(fg_u8.shape))
-        dev = self.losses.device
-        skey = ('u8',) + tuple(fg_u8.shape)
-        st = self._static.get(skey)
-        if st is None:
-            st = {'fg': torch.empty(tuple(fg_u8.shape), dtype=torch.uint8, device=dev), 'bg': torch.empty(tuple(fg_u8.shape), dtype=torch.uint8, device=dev),
-                  'labels': torch.empty(tuple(labels.shape), dtype=torch.int32, device=dev),
-                  'inputs': torch.empty(tuple(fg_u8.shape), dtype=torch.float32, device=dev),
-                  'targets': torch.empty(tuple(fg_u8.shape), dtype=torch.float32, device=dev)}
-            self._static[skey] = st
+        dev, shape = self.losses.device, tuple(fg_u8.shape)
+        key = ('u8',) + shape
+        st = self._statics(key, shape, lambda: {'fg': torch.empty(shape, dtype=torch.uint8, device=dev),
+                                                'bg': torch.empty(shape, dtype=torch.uint8, device=dev)})
         st['fg'].copy_(fg_u8, non_blocking=True)
         st['bg'].copy_(bg_u8, non_blocking=True)
         st['labels'].copy_(labels, non_blocking=True)
-        if not self.use_graphs or hip.PROFILE is not None:
-            gctx = self.gradients(st['inputs'], st['targets'], text, st['labels'], **self._stage_u8(st))
-            self.apply_gradients()
-            return gctx
-        prep = text if isinstance(text, dict) else self.G.text.prepare(text, 'bg')
-        return self._step(skey + (prep['S'],),
-                          lambda: self.gradients(st['inputs'], st['targets'], prep, st['labels'], **self._stage_u8(st)))
-
-    def _stage_cached(self, cache, st):
-        """The cached stage on the static tensors of a batch shape -> the keyword arguments of ``gradients``."""
-        xd = self.bufs.get('xd_real', tuple(st['inputs'].shape[:3]) + (8,), zero_on_alloc=True)
-        count = self.bufs.get('l1_count', (1,))
-        hip.bg_stage_cached_u8(cache.fg, cache.bg, cache.seg, st['slot'], st['recolor'], st['inputs'], st['targets'], xd,
-                               st['labels'], count)
-        return {'xd_real': xd, 'count': count}
+        return self._run(key, st, text, lambda st, xd_real, count: hip.bg_stage_u8(
+            st['fg'], st['bg'], st['labels'], st['inputs'], st['targets'], xd_real, count))
 
     @staticmethod
-    def _small_upload(st, name, values, dtype):
-        """values (NumPy array or host tensor of the static tensor's shape) -> st[name], without a host wait: through one of
-        four pinned buffers used in turn, each written again only when the copy that last read it has happened."""
+    def _small_upload(st, name, values):
+        """values (NumPy array or host tensor of the static tensor's shape) -> st[name], without a host wait: through the
+        pinned ring st['ring_' + name], unless the values are on the device or pinned already."""
         if torch.is_tensor(values) and (values.is_cuda or values.is_pinned()):
-            st[name].copy_(values, non_blocking=True)
-            return
-        ring = st.setdefault('ring_' + name, [])
-        turn = st['turn_' + name] = st.get('turn_' + name, -1) + 1
-        if turn < 4:
-            ring.append((torch.empty(tuple(st[name].shape), dtype=dtype).pin_memory(), torch.cuda.Event()))
-        buf, ev = ring[turn % 4]
-        ev.synchronize()        # (an event that was never recorded does not wait)
+            return st[name].copy_(values, non_blocking=True)
+        buf = st['ring_' + name].next()
         buf.copy_(values if torch.is_tensor(values) else torch.from_numpy(np.ascontiguousarray(values, dtype=buf.numpy().dtype)))
         st[name].copy_(buf, non_blocking=True)
-        ev.record()
+        st['ring_' + name].queued()
 
     def train_step_cached(self, cache, slots, recolor, text):
         """``train_step_u8`` on scenes that live on the device already: cache.fg / cache.bg uint8 [S,H,W,3] and cache.seg uint8
@@ -321,30 +307,21 @@ class BGTrainer(object):
         assert cache.fg.device == dev and cache.fg.dtype == torch.uint8 and cache.fg.dim() == 4
         N, (H, W) = len(slots), cache.fg.shape[1:3]
         assert tuple(slots.shape) == (N, 3) and (recolor is None or tuple(recolor.shape) == (N, 8))
-        skey = ('cached', N, H, W, cache.fg.data_ptr(), cache.bg.data_ptr(), cache.seg.data_ptr(),
-                cache.fg.shape[0], cache.bg.shape[0], cache.seg.shape[0])
-        st = self._static.get(skey)
-        if st is None:
-            st = {'slot': torch.zeros((N, 3), dtype=torch.int32, device=dev),
-                  'recolor': torch.zeros((N, 8), dtype=torch.uint8, device=dev), 'painted': False,
-                  'labels': torch.empty((N, H, W), dtype=torch.int32, device=dev),
-                  'inputs': torch.empty((N, H, W, 3), dtype=torch.float32, device=dev),
-                  'targets': torch.empty((N, H, W, 3), dtype=torch.float32, device=dev)}
-            self._static[skey] = st
-        self._small_upload(st, 'slot', slots, torch.int32)
+        key = ('cached', N, H, W, cache.fg.data_ptr(), cache.bg.data_ptr(), cache.seg.data_ptr(),
+               cache.fg.shape[0], cache.bg.shape[0], cache.seg.shape[0])
+        st = self._statics(key, (N, H, W, 3), lambda: {
+            'slot': torch.zeros((N, 3), dtype=torch.int32, device=dev), 'ring_slot': PinnedRing((N, 3), torch.int32),
+            'recolor': torch.zeros((N, 8), dtype=torch.uint8, device=dev), 'ring_recolor': PinnedRing((N, 8), torch.uint8),
+            'painted': False})
+        self._small_upload(st, 'slot', slots)
         if recolor is not None:
-            self._small_upload(st, 'recolor', recolor, torch.uint8)
+            self._small_upload(st, 'recolor', recolor)
             st['painted'] = True
         elif st['painted']:         # the static record still enables a colour pair of an earlier step
             st['recolor'].zero_()
             st['painted'] = False
-        if not self.use_graphs or hip.PROFILE is not None:
-            gctx = self.gradients(st['inputs'], st['targets'], text, st['labels'], **self._stage_cached(cache, st))
-            self.apply_gradients()
-            return gctx
-        prep = text if isinstance(text, dict) else self.G.text.prepare(text, 'bg')
-        return self._step(skey + (prep['S'],),
-                          lambda: self.gradients(st['inputs'], st['targets'], prep, st['labels'], **self._stage_cached(cache, st)))
+        return self._run(key, st, text, lambda st, xd_real, count: hip.bg_stage_cached_u8(
+            cache.fg, cache.bg, cache.seg, st['slot'], st['recolor'], st['inputs'], st['targets'], xd_real, st['labels'], count))
 
     def _step(self, key, gradients):
         """The optimizer step around ``gradients()`` (which reads static tensors only), eager the first time ``key`` is seen,
@@ -363,3 +340,15 @@ class BGTrainer(object):
                 self._real_stream = torch.cuda.Stream()
             impl()
         return self._gctx
+
+    def color_foreground(self, fg_u8, tok):
+        """Test mode's forward pass: fg_u8 uint8 [1,H,W,3] on the device and its token row int [1,T] (host) -> the generator
+        context of ``G.forward`` on u8 / 255 * 2 - 1 (``['image']``: the tanh image, valid until the next pass under tag 'bg').
+        One image, whatever the batch of training: the norms are batch statistics."""
+        shape, dev = tuple(fg_u8.shape), fg_u8.device
+        st = self._statics(('fg',) + shape, shape, lambda: {'xd': torch.empty(shape[:3] + (8,), dtype=torch.float32, device=dev),
+                                                            'count': torch.empty(1, device=dev)})
+        # the forward pass reads the stage's float inputs only: the foreground stands in for the background and the constant zero
+        # labels, so nothing but the foreground is uploaded (targets, xd and count are the kernel's other outputs, unread)
+        hip.bg_stage_u8(fg_u8, fg_u8, st['labels'], st['inputs'], st['targets'], st['xd'], st['count'])
+        return self.G.forward(st['inputs'], tok, None, 'bg')

@@ -150,12 +150,7 @@ def colorize_background(trainer, scene, text, previous_image=None, previous_text
         sketch_d, inner_d = torch.from_numpy(sketch).cuda(), torch.from_numpy(inner).cuda()
         grass_d = torch.from_numpy(grass_table(scene['class_ids'])).cuda()
     fg_d = hip.bg_scene_crop_u8(previous_image if previous_on_device else torch.from_numpy(previous_image).cuda(), inner_d)
-    x = torch.empty((1, h, w, 3), dtype=torch.float32, device='cuda')
-    y, xd, cnt = torch.empty_like(x), torch.empty((1, h, w, 8), dtype=torch.float32, device='cuda'), torch.empty(1, device='cuda')
-    lab0 = torch.zeros((1, h, w), dtype=torch.int32, device='cuda')
-    fg4 = fg_d.view(1, h, w, 3)
-    hip.bg_stage_u8(fg4, fg4, lab0, x, y, xd, cnt)      # as test mode: only the float inputs are read
-    gctx = trainer.G.forward(x, tok, None, 'bg')
+    gctx = trainer.color_foreground(fg_d.view(1, h, w, 3), tok)
     out_d, marked_d = hip.bg_scene_compose_u8(gctx['image'], fg_d, inner_d, grass_d, sketch_d)
     found = {'sky_color': None, 'sky_bottom': None, 'start_height': None}
     if color_gradient:
