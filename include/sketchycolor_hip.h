@@ -72,7 +72,9 @@ typedef struct ssc_conv_desc {
     int32_t ky0, kx0, kstep;  /* filter row = ky0 + ty*kstep */
     int32_t KH, KW, wC0, wC1;
     int32_t bmode;        /* 0: k->wC0, n->wC1 ("KN"); 1: n->wC0, k->wC1 ("NK") */
-    int32_t k_real;       /* real K channels in the filter (<= x.C0+x.C1) */
+    int32_t k_real;       /* real K channels in the filter (<= x.C0+x.C1).  The stored channels past k_real (padding lanes) must
+                             hold FINITE values: the tiled kernels, narrow and tr4_tiny mask the lane, but fewchan, fewchan7 and
+                             tr4n16 multiply it by a zero filter row, so a NaN or an infinity there would reach the output */
     int32_t n_off, Nn;    /* first filter n index, number of real outputs */
     int32_t Nstore;       /* columns stored (>= Nn; extra ones are written 0) */
     int32_t OH, OW, ldc;
@@ -226,7 +228,8 @@ int ssc_conv_narrow_forward(const ssc_conv_desc* d, void* stream);
 /* the 1x1 expansion conv of the bottleneck blocks (K = 16 .. 128 input channels, N = 4 K outputs): streaming kernel (pw1x1.hip) */
 int ssc_conv_pw1x1_supported(const ssc_conv_desc* d);
 /* the 3x3 stride-1 conv of the bottleneck blocks at 16 / 32 channels and its data gradient (residual_util.py:92-96): streaming
-   kernel (c3x3.hip); the batch statistics (ssc_conv_forward_bn) / norm-backward sums (ssc_conv_forward_bnbwd) ride as per-lane sums */
+   kernel (c3x3.hip); the batch statistics (ssc_conv_forward_bn) / norm-backward sums (ssc_conv_forward_bnbwd) ride as per-lane sums.
+   At most as many outputs as channels (4 .. C): the kernels stage C columns of the filter */
 int ssc_conv_c3x3_supported(const ssc_conv_desc* d);
 /* the 4x4 stride-2 conv 64 -> <= 16 channels (block_1 of the first encoder bottleneck, residual_util.py:87-91) on the 16-column
    MFMA with K split over the four wavefronts (s2n16.hip) */
@@ -292,6 +295,23 @@ int ssc_conv_wgrad128_plan(const ssc_wgrad_desc* d, int64_t ws_bytes, int* out7)
  * alone; otherwise all tiles), K slices per remaining tile}: ten values.  ws_bytes <= 0 stands for a NULL workspace.  Computed by
  * the functions that make the launch. */
 int ssc_conv_bf_plan(const ssc_conv_desc* d, int64_t ws_bytes, int* out10);
+/* the launch plan of a forward conv / data gradient on one of the seven streaming kernels ssc_conv_forward dispatches before the
+ * tiled ones (fewchan.hip, pw1x1.hip, c3x3.hip, s2n16.hip, tr4tiny.hip, fewchan7.hip, tr4n16.hip; host only, launches nothing):
+ * -10 when none of them takes the descriptor, ssc_conv_forward's own error for a descriptor it rejects, else 0 and out4 = {the
+ * kernel in the dispatch order (the ids of ssc_conv_rider_plan: 4 fewchan, 5 pw1x1, 6 c3x3, 7 s2n16, 8 tr4_tiny, 9 fewchan7,
+ * 10 tr4n16), the instantiation within that kernel, tiles, workgroups launched}.  Instantiations:
+ *   fewchan   0 fewchan_conv_kernel<4>, 1 fewchan_conv_kernel<8> (stored input channels)
+ *   pw1x1     2 * log2(K / 16) + NARROW of pw1x1_kernel<K, NARROW>: K = 16, 32, 64, 128 input channels; NARROW = 1 at 64 outputs
+ *             (two row blocks x two column blocks per workgroup), 0 above (column groups of 128 on the grid's second axis)
+ *   c3x3      0 c3x3n16_kernel (16 channels -> <= 16 on the 4 x 32 tile), 1 c3x3_kernel<16, 16>, 2 c3x3_kernel<32, 32>,
+ *             3 c3x3_kernel<32, 16> (<channels, tile width>: the 8 x 16 tile where it wastes fewer pixels than 4 x 32)
+ *   s2n16     0 s2n16_kernel<2> (stride 2), 1 s2n16_kernel<1> (stride 1)
+ *   tr4_tiny, fewchan7, tr4n16   0
+ * tiles: row tiles of 64 over the column groups (pw1x1: a column group per grid row), output tiles (fewchan, c3x3, s2n16,
+ * fewchan7), blocks of 256 lattice pixels (tr4_tiny: nothing is walked, tiles == workgroups), lattice tiles over the four phases
+ * (tr4n16: a phase per grid row).  tiles > workgroups means that some persistent workgroup walks two tiles or more.  Computed
+ * by the functions that make the launch. */
+int ssc_conv_stream_plan(const ssc_conv_desc* d, int* out4);
 
 /* --- layout (elementwise.hip) --- */
 /* dst[n,hw,coff+c] = src[n,c,hw]; tf.transpose NCHW->NHWC (models_collection.py:381) */

@@ -411,7 +411,8 @@ extern "C" int ssc_conv_c3x3_supported(const ssc_conv_desc* dp) {
         d.out_stride != 1 || d.ooff_y != 0 || d.ooff_x != 0)
         return 0;
     if (!((d.ky0 == 0 && d.kx0 == 0 && d.kstep == 1) || (d.ky0 == 2 && d.kx0 == 2 && d.kstep == -1))) return 0;
-    if (d.bias != nullptr || d.epi != 0 || d.accumulate || d.Nn < 4 || d.Nn > 32 || d.Nn != d.Nstore || d.Nstore > d.ldc) return 0;
+    // Nn <= C: the kernels stage K * C filter elements ([K][C] columns; block_2 is C/4 -> C/4)
+    if (d.bias != nullptr || d.epi != 0 || d.accumulate || d.Nn < 4 || d.Nn > C || d.Nn != d.Nstore || d.Nstore > d.ldc) return 0;
     if ((d.bmode == 0 && (d.wC0 != C || d.n_off + d.Nn > d.wC1)) || (d.bmode == 1 && (d.wC1 != C || d.n_off + d.Nn > d.wC0))) return 0;
     if (d.x.act != SSC_ACT_NONE && d.x.act != SSC_ACT_RELU && d.x.act != SSC_ACT_LRELU) return 0;
     if (d.OH != d.PH || d.OW != d.PW || d.x.H != d.PH || d.x.W != d.PW) return 0;
@@ -429,37 +430,33 @@ static int c3_tcw(const ssc_conv_desc& d) {          // 16: the 8 x 16 tile wast
     return c16 < c32 ? 16 : 32;
 }
 
-// persistent workgroups (= rows of partial sums)
-int ssc_conv_c3x3_walkers(const ssc_conv_desc* dp) {
+// the launch: instantiation 0 c3x3n16_kernel (16 channels on the 4 x 32 tile), 1 c3x3_kernel<16, 16>, 2 c3x3_kernel<32, 32>,
+// 3 c3x3_kernel<32, 16>; persistent workgroups (= rows of partial sums)
+ssc_stream_plan ssc_conv_c3x3_plan(const ssc_conv_desc* dp) {
     const ssc_conv_desc& d = *dp;
     const int tcw = c3_tcw(d), tr = 4 * (32 / tcw);
-    const long tiles = (long)d.NB * ((d.PH + tr - 1) / tr) * ((d.PW + tcw - 1) / tcw);
+    const int tiles_x = (d.PW + tcw - 1) / tcw, tiles_y = (d.PH + tr - 1) / tr;
+    const long tiles = (long)d.NB * tiles_y * tiles_x;
     const int per_cu = d.x.C0 == 32 ? 2 : 3;        // LDS: 2 patch images per workgroup; K / 2 filter registers
     const long g = (long)ssc_num_cu() * per_cu;
-    return (int)(tiles < g ? tiles : g);
+    const int inst = d.x.C0 == 16 ? (tcw == 32 ? 0 : 1) : (tcw == 32 ? 2 : 3);
+    return {inst, (int)tiles, tiles_x, tiles_y, (int)(tiles < g ? tiles : g), 1};
 }
+int ssc_conv_c3x3_walkers(const ssc_conv_desc* dp) { return ssc_conv_c3x3_plan(dp).grid_x; }
 
 int ssc_conv_c3x3_forward(const ssc_conv_desc* dp, float* stat, void* stream) {
     if (!ssc_conv_c3x3_supported(dp)) return -1;
     const ssc_conv_desc& d = *dp;
-    const int tcw = c3_tcw(d), tr = 4 * (32 / tcw);
-    const int tiles_x = (d.PW + tcw - 1) / tcw, tiles_y = (d.PH + tr - 1) / tr;
-    const int tiles = d.NB * tiles_y * tiles_x;
-    const int G = ssc_conv_c3x3_walkers(dp);
+    const ssc_stream_plan p = ssc_conv_c3x3_plan(dp);
+    const int tcw = (p.inst == 1 || p.inst == 3) ? 16 : 32, tr = 4 * (32 / tcw);
+    const int tiles = p.tiles, tiles_x = p.tiles_x, tiles_y = p.tiles_y, G = p.grid_x;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)2 * (tr + 2) * (tcw + 2) * (d.x.C0 + 1) * sizeof(float);
-    if (d.x.C0 == 16 && d.Nn <= 16 && tcw == 32) {
-        hipLaunchKernelGGL(c3x3n16_kernel, dim3(G), dim3(256), 0, st, d, tiles, tiles_x, tiles_y, stat);
-    } else if (d.x.C0 == 16) {
-        if (tcw == 32)
-            hipLaunchKernelGGL((c3x3_kernel<16, 32>), dim3(G), dim3(256), lds, st, d, tiles, tiles_x, tiles_y, stat);
-        else
-            hipLaunchKernelGGL((c3x3_kernel<16, 16>), dim3(G), dim3(256), lds, st, d, tiles, tiles_x, tiles_y, stat);
-    } else {
-        if (tcw == 32)
-            hipLaunchKernelGGL((c3x3_kernel<32, 32>), dim3(G), dim3(256), lds, st, d, tiles, tiles_x, tiles_y, stat);
-        else
-            hipLaunchKernelGGL((c3x3_kernel<32, 16>), dim3(G), dim3(256), lds, st, d, tiles, tiles_x, tiles_y, stat);
+    switch (p.inst) {
+        case 0: hipLaunchKernelGGL(c3x3n16_kernel, dim3(G), dim3(256), 0, st, d, tiles, tiles_x, tiles_y, stat); break;
+        case 1: hipLaunchKernelGGL((c3x3_kernel<16, 16>), dim3(G), dim3(256), lds, st, d, tiles, tiles_x, tiles_y, stat); break;
+        case 2: hipLaunchKernelGGL((c3x3_kernel<32, 32>), dim3(G), dim3(256), lds, st, d, tiles, tiles_x, tiles_y, stat); break;
+        default: hipLaunchKernelGGL((c3x3_kernel<32, 16>), dim3(G), dim3(256), lds, st, d, tiles, tiles_x, tiles_y, stat); break;
     }
     return (int)hipGetLastError();
 }

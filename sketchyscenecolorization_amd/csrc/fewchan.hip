@@ -151,8 +151,8 @@ extern "C" int ssc_conv_fewchan_supported(const ssc_conv_desc* dp) {
     return 1;
 }
 
-int ssc_conv_fewchan_forward(const ssc_conv_desc* dp, int num_cu, void* stream) {
-    if (!ssc_conv_fewchan_supported(dp)) return -1;
+// the launch: instantiation 0 fewchan_conv_kernel<4>, 1 fewchan_conv_kernel<8>; 4 x 32 output tiles
+ssc_stream_plan ssc_conv_fewchan_plan(const ssc_conv_desc* dp, int num_cu) {
     const ssc_conv_desc& d = *dp;
     const int tiles_x = d.PW / FC_TC, tiles_y = d.PH / FC_TR;
     const int tiles = d.NB * tiles_y * tiles_x;
@@ -161,11 +161,17 @@ int ssc_conv_fewchan_forward(const ssc_conv_desc* dp, int num_cu, void* stream) 
     // of the ids walks 5 and the second half 4, and the dispatcher pairs one of each on a CU (9 tiles per CU; equal counts on
     // fewer workgroups left a fifth of the CUs with one workgroup: 10)
     const int slots = num_cu * (d.x.C0 == 8 ? 2 : 3);
-    const int G = tiles < slots ? tiles : slots;
+    return {d.x.C0 == 8 ? 1 : 0, tiles, tiles_x, tiles_y, tiles < slots ? tiles : slots, 1};
+}
+
+int ssc_conv_fewchan_forward(const ssc_conv_desc* dp, int num_cu, void* stream) {
+    if (!ssc_conv_fewchan_supported(dp)) return -1;
+    const ssc_conv_desc& d = *dp;
+    const ssc_stream_plan p = ssc_conv_fewchan_plan(dp, num_cu);
     hipStream_t st = (hipStream_t)stream;
-    if (d.x.C0 == 8)
-        hipLaunchKernelGGL(fewchan_conv_kernel<8>, dim3(G), dim3(256), 0, st, d, tiles, tiles_x, tiles_y);
+    if (p.inst == 1)
+        hipLaunchKernelGGL(fewchan_conv_kernel<8>, dim3(p.grid_x), dim3(256), 0, st, d, p.tiles, p.tiles_x, p.tiles_y);
     else
-        hipLaunchKernelGGL(fewchan_conv_kernel<4>, dim3(G), dim3(256), 0, st, d, tiles, tiles_x, tiles_y);
+        hipLaunchKernelGGL(fewchan_conv_kernel<4>, dim3(p.grid_x), dim3(256), 0, st, d, p.tiles, p.tiles_x, p.tiles_y);
     return (int)hipGetLastError();
 }

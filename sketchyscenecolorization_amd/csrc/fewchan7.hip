@@ -165,12 +165,17 @@ int ssc_conv_fewchan7_walkers(const ssc_conv_desc* dp) {
     return (int)(tiles < g ? tiles : g);
 }
 
+// the launch: one instantiation (0), 4 x 32 output tiles
+ssc_stream_plan ssc_conv_fewchan7_plan(const ssc_conv_desc* dp) {
+    const ssc_conv_desc& d = *dp;
+    const int tiles_x = d.PW / F7_TC, tiles_y = d.PH / F7_TR;
+    return {0, d.NB * tiles_y * tiles_x, tiles_x, tiles_y, ssc_conv_fewchan7_walkers(dp), 1};
+}
+
 int ssc_conv_fewchan7_forward(const ssc_conv_desc* dp, float* stat, void* stream) {
     if (!ssc_conv_fewchan7_supported(dp)) return -1;
     const ssc_conv_desc& d = *dp;
-    const int tiles_x = d.PW / F7_TC, tiles_y = d.PH / F7_TR;
-    const int tiles = d.NB * tiles_y * tiles_x;
-    hipLaunchKernelGGL(fewchan7_conv_kernel, dim3(ssc_conv_fewchan7_walkers(dp)), dim3(256), 0, (hipStream_t)stream, d, tiles, tiles_x,
-                       tiles_y, stat);
+    const ssc_stream_plan p = ssc_conv_fewchan7_plan(dp);
+    hipLaunchKernelGGL(fewchan7_conv_kernel, dim3(p.grid_x), dim3(256), 0, (hipStream_t)stream, d, p.tiles, p.tiles_x, p.tiles_y, stat);
     return (int)hipGetLastError();
 }

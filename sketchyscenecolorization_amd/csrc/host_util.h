@@ -45,6 +45,15 @@ static inline int ssc_set_max_lds(const void* fn, int bytes, unsigned long long*
     return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
+// What the launcher of a streaming forward kernel (fewchan / pw1x1 / c3x3 / s2n16 / tr4tiny / fewchan7 / tr4n16 .hip) decides for a
+// descriptor its predicate admits: the launch reads it and ssc_conv_stream_plan reports it, so there is one copy of each choice.
+struct ssc_stream_plan {
+    int inst;               // instantiation index within the kernel (include/sketchycolor_hip.h at ssc_conv_stream_plan)
+    int tiles;              // tiles of the launch (tr4tiny: blocks; tr4n16: over the four phases; pw1x1: over the column groups)
+    int tiles_x, tiles_y;   // tiles across and down one image
+    int grid_x, grid_y;     // the grid: grid_x * grid_y workgroups
+};
+
 // compute units of the current device
 static inline int ssc_num_cu() {
     static int n[64] = {0};

@@ -59,6 +59,14 @@ int ssc_conv_s2n16_forward(const ssc_conv_desc* dp, float* stat, void* stream);
 extern "C" int ssc_conv_c3x3_supported(const ssc_conv_desc* dp);
 int ssc_conv_c3x3_walkers(const ssc_conv_desc* dp);
 int ssc_conv_c3x3_forward(const ssc_conv_desc* dp, float* stat, void* stream);
+// what each of those launchers decides (host_util.h): the launches read it and so does ssc_conv_stream_plan
+ssc_stream_plan ssc_conv_fewchan_plan(const ssc_conv_desc* dp, int num_cu);
+ssc_stream_plan ssc_conv_pw1x1_plan(const ssc_conv_desc* dp);
+ssc_stream_plan ssc_conv_c3x3_plan(const ssc_conv_desc* dp);
+ssc_stream_plan ssc_conv_s2n16_plan(const ssc_conv_desc* dp);
+ssc_stream_plan ssc_conv_tr4_tiny_plan(const ssc_conv_desc* dp);
+ssc_stream_plan ssc_conv_fewchan7_plan(const ssc_conv_desc* dp);
+ssc_stream_plan ssc_conv_tr4n16_plan(const ssc_conv_desc* dp);
 
 // igemm_bf16.hip
 bool ssc_bf_hk_enabled();       // igemm_bf16.hip
@@ -1916,6 +1924,26 @@ extern "C" int ssc_conv_bf_plan(const ssc_conv_desc* dp, int64_t ws_bytes, int* 
     const Plan p = plan_fwd(d, ws_bytes, have_ws);
     if (p.cfg < 0) return -4;
     return ssc_conv_bf_form(p.cfg, fwd_bf_plain(d), d, p.splitk, have_ws, p.ts_full, p.ts_s, ws_bytes, xcd_order(), out10);
+}
+
+extern "C" int ssc_conv_stream_plan(const ssc_conv_desc* dp, int* out4) {
+    // host only: {kernel (FWD_*), instantiation, tiles, workgroups} of a launch one of the seven streaming kernels takes
+    const int err = fwd_desc_error(*dp);
+    if (err != 0) return err;
+    ssc_stream_plan p;
+    const int k = fwd_early_kernel(dp, true, (int64_t)1 << 40);
+    switch (k) {
+        case FWD_FEWCHAN: p = ssc_conv_fewchan_plan(dp, num_cu()); break;
+        case FWD_PW1X1: p = ssc_conv_pw1x1_plan(dp); break;
+        case FWD_C3X3: p = ssc_conv_c3x3_plan(dp); break;
+        case FWD_S2N16: p = ssc_conv_s2n16_plan(dp); break;
+        case FWD_TR4_TINY: p = ssc_conv_tr4_tiny_plan(dp); break;
+        case FWD_FEWCHAN7: p = ssc_conv_fewchan7_plan(dp); break;
+        case FWD_TR4N16: p = ssc_conv_tr4n16_plan(dp); break;
+        default: return -10;
+    }
+    out4[0] = k; out4[1] = p.inst; out4[2] = p.tiles; out4[3] = p.grid_x * p.grid_y;
+    return 0;
 }
 
 extern "C" int ssc_conv_forward(const ssc_conv_desc* dp, float* ws, int64_t ws_bytes, void* stream) {

@@ -190,15 +190,28 @@ int ssc_conv_pw1x1_walkers(const ssc_conv_desc* dp) {
     return tiles < g ? tiles : g;
 }
 
+// the launch: instantiation 2 * log2(K / 16) + NARROW, walkers x column groups of 128; tiles_y 64-row tiles, which every column
+// group walks: tiles counts them over the column groups
+ssc_stream_plan ssc_conv_pw1x1_plan(const ssc_conv_desc* dp) {
+    const ssc_conv_desc& d = *dp;
+    const long M = (long)d.NB * d.PH * d.PW;
+    const int row_tiles = (int)((M + PW_TR - 1) / PW_TR);
+    const int colg = (d.Nn + PW_BN - 1) / PW_BN;
+    const int narrow = d.Nn <= 64 ? 1 : 0;
+    const int kidx = d.x.C0 == 16 ? 0 : (d.x.C0 == 32 ? 1 : (d.x.C0 == 64 ? 2 : 3));
+    return {2 * kidx + narrow, row_tiles * colg, 1, row_tiles, ssc_conv_pw1x1_walkers(dp), colg};
+}
+
 // stat != NULL: rows of [sum | sum of squares] of the output columns, one per walker (ssc_conv_pw1x1_walkers rows of 2 x Nstore)
 int ssc_conv_pw1x1_forward(const ssc_conv_desc* dp, float* stat, void* stream) {
     if (!ssc_conv_pw1x1_supported(dp)) return -1;
     const ssc_conv_desc& d = *dp;
     const long M = (long)d.NB * d.PH * d.PW;
-    const int tiles = (int)((M + PW_TR - 1) / PW_TR);
-    const dim3 grid((unsigned)ssc_conv_pw1x1_walkers(dp), (unsigned)((d.Nn + PW_BN - 1) / PW_BN));
+    const ssc_stream_plan p = ssc_conv_pw1x1_plan(dp);
+    const int tiles = p.tiles_y;
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
     hipStream_t st = (hipStream_t)stream;
-    const bool narrow = d.Nn <= 64;
+    const bool narrow = (p.inst & 1) != 0;
     const size_t lds = (size_t)2 * PW_TR * (d.x.C0 + 1) * sizeof(float);
 #define PW_LAUNCH(KK)                                                                                              \
     {                                                                                                              \
@@ -214,10 +227,10 @@ int ssc_conv_pw1x1_forward(const ssc_conv_desc* dp, float* stat, void* stream) {
             hipLaunchKernelGGL((pw1x1_kernel<KK, false>), grid, dim3(256), lds, st, d, M, tiles, stat);            \
         }                                                                                                          \
     }
-    switch (d.x.C0) {
-        case 16: PW_LAUNCH(16) break;
-        case 32: PW_LAUNCH(32) break;
-        case 64: PW_LAUNCH(64) break;
+    switch (p.inst >> 1) {
+        case 0: PW_LAUNCH(16) break;
+        case 1: PW_LAUNCH(32) break;
+        case 2: PW_LAUNCH(64) break;
         default: PW_LAUNCH(128) break;
     }
 #undef PW_LAUNCH

@@ -210,16 +210,21 @@ int ssc_conv_s2n16_walkers(const ssc_conv_desc* dp) {
     return (int)(tiles < g ? tiles : g);
 }
 
-int ssc_conv_s2n16_forward(const ssc_conv_desc* dp, float* stat, void* stream) {
-    if (!ssc_conv_s2n16_supported(dp)) return -1;
+// the launch: instantiation 0 s2n16_kernel<2> (stride 2, tiles of 2 rows x 16), 1 s2n16_kernel<1> (stride 1, 4 rows x 16)
+ssc_stream_plan ssc_conv_s2n16_plan(const ssc_conv_desc* dp) {
     const ssc_conv_desc& d = *dp;
     const int tr = d.in_stride == 2 ? 2 : 4;
     const int tiles_x = (d.PW + S2_TC - 1) / S2_TC, tiles_y = (d.PH + tr - 1) / tr;
-    const int tiles = d.NB * tiles_y * tiles_x;
-    const int G = ssc_conv_s2n16_walkers(dp);
-    if (d.in_stride == 2)
-        hipLaunchKernelGGL(s2n16_kernel<2>, dim3(G), dim3(256), 0, (hipStream_t)stream, d, tiles, tiles_x, tiles_y, stat);
+    return {d.in_stride == 2 ? 0 : 1, d.NB * tiles_y * tiles_x, tiles_x, tiles_y, ssc_conv_s2n16_walkers(dp), 1};
+}
+
+int ssc_conv_s2n16_forward(const ssc_conv_desc* dp, float* stat, void* stream) {
+    if (!ssc_conv_s2n16_supported(dp)) return -1;
+    const ssc_conv_desc& d = *dp;
+    const ssc_stream_plan p = ssc_conv_s2n16_plan(dp);
+    if (p.inst == 0)
+        hipLaunchKernelGGL(s2n16_kernel<2>, dim3(p.grid_x), dim3(256), 0, (hipStream_t)stream, d, p.tiles, p.tiles_x, p.tiles_y, stat);
     else
-        hipLaunchKernelGGL(s2n16_kernel<1>, dim3(G), dim3(256), 0, (hipStream_t)stream, d, tiles, tiles_x, tiles_y, stat);
+        hipLaunchKernelGGL(s2n16_kernel<1>, dim3(p.grid_x), dim3(256), 0, (hipStream_t)stream, d, p.tiles, p.tiles_x, p.tiles_y, stat);
     return (int)hipGetLastError();
 }

@@ -195,11 +195,17 @@ static int t16_walkers(const ssc_conv_desc& d) {
 }
 int ssc_conv_tr4n16_rows(const ssc_conv_desc* dp) { return 4 * t16_walkers(*dp); }
 
+// the launch: one instantiation (0); a phase per grid row, the same tiles walked in each: tiles counts them over the four phases
+ssc_stream_plan ssc_conv_tr4n16_plan(const ssc_conv_desc* dp) {
+    const ssc_conv_desc& d = *dp;
+    const int tiles_x = (d.PW + T16_TC - 1) / T16_TC, tiles_y = (d.PH + T16_TR - 1) / T16_TR;
+    return {0, 4 * d.NB * tiles_y * tiles_x, tiles_x, tiles_y, t16_walkers(d), 4};
+}
+
 int ssc_conv_tr4n16_forward(const ssc_conv_desc* dp, float* stat, void* stream) {
     if (!ssc_conv_tr4n16_supported(dp)) return -1;
     const ssc_conv_desc& d = *dp;
-    const int tiles_x = (d.PW + T16_TC - 1) / T16_TC, tiles_y = (d.PH + T16_TR - 1) / T16_TR;
-    const int tiles = d.NB * tiles_y * tiles_x;
-    hipLaunchKernelGGL(tr4n16_kernel, dim3(t16_walkers(d), 4), dim3(256), 0, (hipStream_t)stream, d, tiles, tiles_x, tiles_y, stat);
+    const ssc_stream_plan p = ssc_conv_tr4n16_plan(dp);
+    hipLaunchKernelGGL(tr4n16_kernel, dim3(p.grid_x, p.grid_y), dim3(256), 0, (hipStream_t)stream, d, p.tiles / 4, p.tiles_x, p.tiles_y, stat);
     return (int)hipGetLastError();
 }

@@ -119,10 +119,16 @@ int ssc_conv_tr4_tiny_blocks(const ssc_conv_desc* dp) {
     return (int)(((long)dp->NB * dp->PH * dp->PW + 255) / 256);
 }
 
+// the launch: one instantiation (0), a workgroup per block of 256 lattice pixels and nothing walked
+ssc_stream_plan ssc_conv_tr4_tiny_plan(const ssc_conv_desc* dp) {
+    const int blocks = ssc_conv_tr4_tiny_blocks(dp);
+    return {0, blocks, 1, blocks, blocks, 1};
+}
+
 int ssc_conv_tr4_tiny_forward(const ssc_conv_desc* dp, float* stat, void* stream) {
     if (!ssc_conv_tr4_tiny_supported(dp)) return -1;
     const ssc_conv_desc& d = *dp;
     const long npix = (long)d.NB * d.PH * d.PW;
-    hipLaunchKernelGGL(tr4_tiny_kernel, dim3((unsigned)ssc_conv_tr4_tiny_blocks(dp)), dim3(256), 0, (hipStream_t)stream, d, npix, stat);
+    hipLaunchKernelGGL(tr4_tiny_kernel, dim3((unsigned)ssc_conv_tr4_tiny_plan(dp).grid_x), dim3(256), 0, (hipStream_t)stream, d, npix, stat);
     return (int)hipGetLastError();
 }

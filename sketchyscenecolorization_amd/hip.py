@@ -174,6 +174,7 @@ SIGNATURES = {
     'ssc_conv_wgrad_plan': [C.POINTER(WgradDesc), _L, C.POINTER(C.c_int)],
     'ssc_conv_wgrad128_plan': [C.POINTER(WgradDesc), _L, C.POINTER(C.c_int)],
     'ssc_conv_bf_plan': [C.POINTER(ConvDesc), _L, C.POINTER(C.c_int)],
+    'ssc_conv_stream_plan': [C.POINTER(ConvDesc), C.POINTER(C.c_int)],
     'ssc_sk_configure': [_I, _I],
     'ssc_nchw_to_nhwc': [_P, _P, _I, _I, _I, _I, _I, _P],
     'ssc_nhwc_to_nchw': [_P, _P, _I, _I, _I, _I, _I, _P],

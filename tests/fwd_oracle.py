@@ -28,6 +28,11 @@ A case describes the launch the way the hip.py wrappers see it:
   co    output channels Nn of a forward op; ci / n_off / nn: the filter's input channels and the sub-range of a data gradient
   nstore, ldc, coff: stored columns (>= Nn, the rest zeros), row pitch of the output tensor, first column
   probe 'onehot': one non-zero gathered channel per pixel (K = 1 per tap); 'channel': one non-zero channel in the whole tensor
+  bn, bnbwd: riders a case of the second table carries on a second launch (see STREAM_CASES)
+
+A second table, STREAM_CASES, holds the cases of the seven streaming kernels ssc_conv_forward dispatches before the tiled ones
+(csrc/fewchan.hip, pw1x1.hip, c3x3.hip, s2n16.hip, tr4tiny.hip, fewchan7.hip, tr4n16.hip), which
+tests/test_gpu_fwd_stream_forms.py runs; the same two references serve it.
 """
 import torch
 
@@ -43,7 +48,7 @@ TWO_T = (True, 2, True, 1)          # two sources: norm + lrelu, norm + relu
 TWO_A = (False, 2, False, 1)        # two sources, activations only (keeps zeros: the probes)
 
 DEFAULTS = dict(k=1, stride=1, pad=0, tf=PLAIN, co=None, ci=None, n_off=0, nn=None, bias=False, epi=0, acc=False, nstore=None,
-                ldc=None, coff=0, nk=False, lane=PAD_LANE, probe=None, seed=None)
+                ldc=None, coff=0, nk=False, lane=PAD_LANE, probe=None, seed=None, bn=False, bnbwd=0)
 
 
 def _case(name, kind, n, h, w, src, **kw):
@@ -158,7 +163,131 @@ def all_cases():
     return CASES + [carrier(*f) for f in CARRIER_FORMS] + [probe(*f) for f in PROBE_FORMS]
 
 
+# --- the streaming kernels ssc_conv_forward dispatches before the tiled ones (tests/test_gpu_fwd_stream_forms.py): the smallest
+# shapes that still reach each form.  expect: kernel, the name ssc_conv_forward_kernel_name must give; inst, the instantiation
+# ssc_conv_stream_plan must report (None: none of the seven takes the launch, the query answers -10); walk, whether some
+# persistent workgroup takes two tiles or more on the MI355X's 256 CUs (tiles > workgroups in the query's words).
+# bn: a second launch carries the batch-statistics rider (conv_forward / deconv_forward(bn=...)); bnbwd: a second launch of the
+# data gradient carries the norm-backward sums for a consumer with that activation (conv_dgrad(bnbwd=...)).
+def _s(name, kind, n, h, w, src, kernel, inst, walk=False, **kw):
+    return _case(name, kind, n, h, w, src, kernel=kernel, inst=inst, walk=walk, **kw)
+
+
+def _pw(name, K, co, tf, shape=(2, 33, 35), **kw):      # M = 2310: 37 row tiles of 64, the last with 6 rows
+    inst = 2 * (16, 32, 64, 128).index(K) + int(co <= 64)
+    return _s(name, 'conv', shape[0], shape[1], shape[2], (K, 0, K), 'conv_pw1x1', inst, co=co, tf=tf, **kw)
+
+
+def _c3(name, shape, C, co, inst, tf, kind='conv', **kw):
+    orient = 'NK' if (kind == 'conv_dgrad' or kw.get('nk')) else 'KN'
+    geo = dict(pad=1) if kind == 'conv_dgrad' else dict(pad='same', co=co)
+    return _s(name, kind, shape[0], shape[1], shape[2], (C, 0, C), 'conv_c3x3<%s>' % orient, inst, k=3, tf=tf, **dict(geo, **kw))
+
+
+def _s2(name, co, tf, stride=2, **kw):
+    # stride 2: lattice (9, 63, 66), 1440 tiles of 2 x 16; stride 1 (4x4 SAME): (3, 101, 119), 624 tiles of 4 x 16; 512 walkers
+    n, h, w = (9, 126, 132) if stride == 2 else (3, 101, 119)
+    return _s(name, 'conv', n, h, w, (64, 0, 64), 'conv_s2n16', 0 if stride == 2 else 1, walk=True, co=co, k=4, stride=stride,
+              pad=1 if stride == 2 else 'same', tf=tf, **kw)
+
+
+def _t16(name, src, co, tf, **kw):      # lattice (4, 61, 70): 620 tiles of 2 x 16 per phase on 128 walkers
+    return _s(name, 'deconv', 4, 61, 70, src, 'deconv_tr4n16', 0, walk=True, co=co, tf=tf, **kw)
+
+
+def _f7(name, shape, ci, co, **kw):
+    return _s(name, 'conv', shape[0], shape[1], shape[2], (4, 0, ci), 'conv_fewchan7', 0, co=co, k=7, stride=2, pad='same', **kw)
+
+
+def _fc(name, shape, src, co, **kw):
+    return _s(name, 'conv', shape[0], shape[1], shape[2], src, 'conv_fewchan<%d>' % src[0], int(src[0] == 8), co=co, k=4, stride=2,
+              pad=1, **kw)
+
+
+def _tt(name, shape, ci, co, tf=PLAIN, **kw):
+    return _s(name, 'deconv', shape[0], shape[1], shape[2], (4, 0, ci), 'deconv_tr4_tiny', 0, co=co, nstore=4, tf=tf, **kw)
+
+
+STREAM_CASES = [
+    # --- pw1x1: all eight pw1x1_kernel<K, NARROW>; 96 and 160 outputs (a partly filled column block / column group); columns
+    # inside a wider row; the four source forms; walkers with two tiles (1055 row tiles on 1024 walkers, 149 on 128)
+    _pw('pw_k16_n64', 16, 64, PLAIN),
+    _pw('pw_k16_n96', 16, 96, LRELU),
+    _pw('pw_k32_n64', 32, 64, NORM_RELU),
+    _pw('pw_k32_n128_coff', 32, 128, NORM_LRELU, coff=4, ldc=136),
+    _pw('pw_k32_n160', 32, 160, LRELU),
+    _pw('pw_k64_n64', 64, 64, NORM_LRELU),
+    _pw('pw_k64_n256', 64, 256, PLAIN),
+    _pw('pw_k128_n64', 128, 64, LRELU),
+    _pw('pw_k128_n512', 128, 512, NORM_RELU),
+    _pw('pw_walk_k16_n64', 16, 64, NORM_LRELU, shape=(3, 149, 151), walk=True, bn=True),
+    _pw('pw_walk_k128_n512', 128, 512, NORM_RELU, shape=(2, 67, 71), walk=True, bn=True),
+    _pw('pw_probe_onehot', 64, 256, LRELU, probe='onehot'),
+    # --- c3x3: c3x3n16_kernel (16 -> <= 16 on the 4 x 32 tile), c3x3_kernel<16, 16>, <32, 32>, <32, 16> (the 8 x 16 tile where it wastes
+    # fewer pixels); once each at 17296 / 22500 pixels and once with tiles > walkers (768 at 16 channels, 512 at 32); KN, NK and
+    # the flipped NK of the data gradient with n_off > 0 and nn < ci
+    _c3('c3_n16_nn16', (2, 90, 125), 16, 16, 0, NORM_RELU),
+    _c3('c3_n16_nn12_coff', (2, 90, 125), 16, 12, 0, LRELU, coff=4, ldc=20),
+    _c3('c3_n16_nn4', (2, 90, 125), 16, 4, 0, PLAIN),
+    _c3('c3_16x16_nk', (8, 47, 46), 16, 16, 1, NORM_LRELU, nk=True),
+    _c3('c3_32x32', (2, 90, 125), 32, 32, 2, LRELU),
+    _c3('c3_32x16_nk', (8, 47, 46), 32, 32, 3, NORM_RELU, nk=True),
+    _c3('c3_32x32_dgrad_noff', (2, 90, 125), 32, None, 2, PLAIN, kind='conv_dgrad', ci=40, n_off=8, nn=20),
+    _c3('c3_walk_n16', (17, 61, 90), 16, 16, 0, NORM_LRELU, walk=True, bn=True),                 # 816 tiles
+    _c3('c3_walk_16x16', (43, 47, 46), 16, 16, 1, NORM_RELU, walk=True, bn=True),                # 774
+    _c3('c3_walk_32x32', (12, 61, 90), 32, 32, 2, NORM_RELU, walk=True, bn=True),                # 576
+    _c3('c3_walk_32x16', (29, 47, 46), 32, 32, 3, LRELU, walk=True, bn=True),                    # 522
+    _c3('c3_walk_n16_dgrad_noff', (17, 61, 90), 16, None, 0, PLAIN, kind='conv_dgrad', ci=24, n_off=4, nn=16, walk=True, bnbwd=2),
+    _c3('c3_probe_channel', (2, 90, 125), 16, 16, 0, LRELU, probe='channel'),
+    # 16 channels to more than 16: c3x3_kernel<16, *> stages 16 filter columns only, so the predicate refuses them and the
+    # exact-fp32 tiled kernel runs (at most 32 stored columns: the 128 x 32 tile, no bf16 form)
+    _s('c3_16_to_20', 'conv', 2, 90, 125, (16, 0, 16), 'conv_fwd<128x32,KN>', None, co=20, k=3, pad='same', tf=NORM_LRELU),
+    _s('c3_16_to_32', 'conv', 2, 90, 125, (16, 0, 16), 'conv_fwd<128x32,KN>', None, co=32, k=3, pad='same', tf=NORM_LRELU),
+    # --- s2n16: both strides, 16 / 10 / 4 columns, the data gradient of a transposed conv with 24 input channels
+    _s2('s2_nn16', 16, NORM_LRELU, bn=True),
+    _s2('s2_nn10_coff', 10, LRELU, coff=3, ldc=16),
+    _s2('s2_nn4', 4, PLAIN),
+    _s2('s2_stride1_nn16', 16, NORM_RELU, stride=1, bn=True),
+    _s2('s2_stride1_nn10', 10, PLAIN, stride=1),
+    _s('s2_deconv_dgrad_noff', 'deconv_dgrad', 9, 126, 132, (64, 0, 64), 'conv_s2n16', 0, walk=True, ci=24, n_off=8, nn=16),
+    _s2('s2_probe_channel', 16, LRELU, probe='channel'),
+    # --- tr4n16: two sources with a norm and an activation each, one, 100 + 156; two padding lanes; 16 / 10 / 4 columns
+    _t16('t16_two', (128, 128, 256), 16, TWO_T, bn=True),
+    _t16('t16_one_nn10', (256, 0, 256), 10, NORM_LRELU),
+    _t16('t16_100_156_nn4_coff', (100, 156, 256), 4, TWO_A, coff=4, ldc=12),
+    _t16('t16_kreal254', (128, 128, 254), 16, TWO_T),
+    _t16('t16_probe_channel', (256, 0, 256), 16, LRELU, probe='channel'),
+    # --- fewchan7: one tile, eight, 544 on 512 walkers; 64 / 48 / 33 columns; 1 to 4 filter input channels
+    _f7('f7_one_tile_ci2', (1, 8, 64), 2, 64),
+    _f7('f7_eight_ci4_nn48', (2, 16, 128), 4, 48),
+    _f7('f7_ci1_nn33_coff', (2, 16, 128), 1, 33, coff=2, ldc=40),
+    _f7('f7_walk', (17, 128, 128), 3, 64, walk=True, bn=True),
+    _f7('f7_probe_channel', (2, 16, 128), 3, 64, probe='channel'),
+    # --- fewchan: <4> with 3 real channels, <8> with 6 and 8; 64 and 33 columns, 36 stored over 33; 576 tiles on 512 walkers
+    # (<8>), 832 on 768 (<4>)
+    _fc('fc4_3', (1, 8, 64), (4, 0, 3), 64),
+    _fc('fc8_6_nn33_of_36', (1, 8, 64), (8, 0, 6), 33, nstore=36),
+    _fc('fc8_8_coff', (1, 8, 64), (8, 0, 8), 64, coff=4, ldc=72),
+    _fc('fc8_walk', (9, 128, 256), (8, 0, 6), 64, walk=True),
+    _fc('fc4_walk', (13, 128, 256), (4, 0, 3), 64, walk=True),
+    _fc('fc_probe_channel', (2, 16, 128), (8, 0, 6), 64, probe='channel'),
+    # --- tr4tiny: 126 pixels in one block and 5883 in 23; 1..4 columns of 4 stored, 1..4 filter input channels, every epilogue
+    _tt('tt_one_block', (2, 9, 7), 3, 3),
+    _tt('tt_23_blocks_bn', (3, 37, 53), 3, 3, NORM_RELU, bn=True),
+    _tt('tt_ci1_co4_tanh', (2, 9, 7), 1, 4, LRELU, epi=1),
+    _tt('tt_ci4_co1_lrelu', (3, 37, 53), 4, 1, epi=2),
+    _tt('tt_ci2_co2_coff', (2, 9, 7), 2, 2, NORM_LRELU, coff=2, ldc=8),
+    _tt('tt_probe_channel', (3, 37, 53), 3, 3, LRELU, probe='channel'),
+]
+for _i, _c in enumerate(STREAM_CASES):
+    _c['seed'] = 8000 + _i
+STREAM_BY_NAME = {c['name']: c for c in STREAM_CASES}
+assert len(STREAM_BY_NAME) == len(STREAM_CASES)
+
+
 def lookup(name):
+    if name in STREAM_BY_NAME:
+        return STREAM_BY_NAME[name]
     for c in all_cases():
         if c['name'] == name:
             return c

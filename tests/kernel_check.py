@@ -54,6 +54,22 @@ def all_nan(t):
     return bool(torch.isnan(t).all().item())
 
 
+GUARD = 16384           # floats on either side of a guarded tensor: more than a K-tile of the widest source
+
+
+def bits(t):
+    """The tensor's float32 bit patterns (NaN compares equal to the same NaN)."""
+    return t.view(torch.int32)
+
+
+def inside(t, fill):
+    """(buffer, view): a copy of the CPU tensor t inside a device buffer that holds `fill` on both sides."""
+    buf = torch.full((GUARD + t.numel() + GUARD,), fill, device='cuda')
+    view = buf[GUARD:GUARD + t.numel()].view(t.shape)
+    view.copy_(t)
+    return buf, view
+
+
 def _f64(t):
     return t.detach().cpu().double()
 

@@ -118,6 +118,7 @@ NOT_KERNEL_TESTED = {
     'ssc_conv_wgrad128_supported': 'host only: dispatch predicate',
     'ssc_conv_wgrad128_plan': 'host only: the launch plan of the 128 x 128 filter-gradient kernels',
     'ssc_conv_bf_plan': 'host only: the launch plan of the bf16x6 forward conv kernels',
+    'ssc_conv_stream_plan': 'host only: the launch plan of the streaming forward conv kernels',
     'ssc_head1_forward_supported': 'host only: dispatch predicate',
 }
 # Arithmetic entry points that ssc_conv_forward / ssc_conv_wgrad call themselves when the launch qualifies (the header says

@@ -43,11 +43,11 @@ import torch
 
 import fwd_oracle as O
 from conftest import parity_log
-from kernel_check import NAN, U_FP32, all_nan, check_dot
+from kernel_check import GUARD, NAN, U_FP32, all_nan, check_dot
+from kernel_check import bits as _bits, inside as _inside
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 16384           # floats on either side of a tensor: more than a K-tile of the widest source
 TILE = {0: (128, 128), 1: (64, 128), 2: (128, 64), 4: (64, 64)}
 NAMES = {0: 'conv_bf16x6<128x128>', 1: 'conv_bf16x6<64x128>', 2: 'conv_bf16x6<128x64>', 4: 'conv_bf16x6<64x64>'}
 _CARRIERS = [O.carrier(*f)['name'] for f in O.CARRIER_FORMS]
@@ -97,18 +97,6 @@ def _reference(c):
         inp = O.make_inputs(c)
         _REF[c['name']] = (inp,) + O.ref_taps(c, inp)
     return _REF[c['name']]
-
-
-def _bits(t):
-    return t.view(torch.int32)
-
-
-def _inside(t, fill):
-    """(buffer, view): a copy of the CPU tensor t inside a device buffer that holds `fill` on both sides."""
-    buf = torch.full((GUARD + t.numel() + GUARD,), fill, device='cuda')
-    view = buf[GUARD:GUARD + t.numel()].view(t.shape)
-    view.copy_(t)
-    return buf, view
 
 
 def _plan(hip, d, ws_bytes):
