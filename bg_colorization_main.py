@@ -28,6 +28,11 @@ forward pass, on the device.  A line per pass goes to ``log/validation.jsonl``: 
 the region branch's pixel accuracy and IoU (sketchyscenecolorization_amd/bg_validation.py).  Training itself is the run of
 --val_freq 0, bit for bit.  Without captions/val.json one line says so and the run trains on.
 
+--color_metrics 1 adds colour scores where the two flags above score: CIELAB dE76 with its chroma and lightness parts, the
+intersection of the ab histograms and colourfulness of output and target (hip.color_metrics_u8 / _bg_f32, under the same mask).
+Test mode (with --metrics 1) also writes ``results/color_metrics.json``; train mode (with --val_freq F) adds the key "color" to
+every line of ``log/validation.jsonl``.  It is refused where neither scores, and changes nothing when 0.
+
 --mode scene --resume_from <stamp> --image_id <id> --instruction 'the sky is ...' colours the background of one user scene as the
 reference's scene pipeline does (Pipeline_utils/bg_utils.py::build_background_colorization): ``<scene_dir>/sketches/<id>.png``,
 ``inner_masks/<id>.mat`` and ``seg_data/<id>_datas.npz`` are read, the instruction is spliced into --previous_text, the instances
@@ -81,6 +86,10 @@ FLAGS = [
     ('val_preview', int, 0, None, 'every held-out pass (needs --val_freq F > 0) also writes log/previews/step_<n>.png and .json: a '
                                   'row for each of the first K scenes with its foreground, the output of the pass as --mode test '
                                   'would write it, and its background, made on the GPU; at most 32; 0 = none'),
+    ('color_metrics', int, 0, [0, 1], '1: colour scores beside MAE / PSNR / SSIM, made on the GPU: CIELAB dE76, its chroma and '
+                                      'lightness parts, the intersection of the ab histograms, colourfulness of output and target.  '
+                                      '--mode test (needs --metrics 1) writes results/color_metrics.json; --mode train (needs '
+                                      '--val_freq F > 0) adds a "color" key to every line of log/validation.jsonl'),
     ('scene_dir', str, 'examples', None, '--mode scene: directory with sketches/, inner_masks/ and seg_data/'),
     ('image_id', str, None, None, '--mode scene: the scene, <id> of sketches/<id>.png'),
     ('instruction', str, None, None, "--mode scene: what to paint, e.g. 'the sky is pink'"),
@@ -285,7 +294,7 @@ def bg_colorization(**p):
         os.makedirs(res_dir, exist_ok=True)
         from sketchyscenecolorization_amd import hip
         size = p['image_size']
-        names, rows = [], []
+        names, rows, color_rows = [], [], []
         # one image per forward pass whatever --batch_size says: the norms are batch statistics
         for i in range(len(scenes)):
             print('Processing', i, '/', len(scenes))
@@ -299,8 +308,10 @@ def bg_colorization(**p):
             out_d = hip.bg_finish_u8(gctx['image'], fg_d, inner)
             out = out_d.cpu().numpy()
             if p.get('metrics', 0):     # out_d holds the bytes that are written below; the mask is the paste-back's
-                rows.append(hip.image_metrics_u8(out_d, torch.from_numpy(bg).cuda(),
-                                                 None if inner is None else inner.reshape(1, size, size)).cpu().numpy())
+                bg_d, mask_d = torch.from_numpy(bg).cuda(), None if inner is None else inner.reshape(1, size, size)
+                rows.append(hip.image_metrics_u8(out_d, bg_d, mask_d).cpu().numpy())
+                if p.get('color_metrics', 0):
+                    color_rows.append(hip.color_metrics_u8(out_d, bg_d, mask_d).cpu().numpy())
                 names.append(bg_name[:-4])
             for kind, arr in (('inputs', fg), ('outputs', out), ('targets', bg)):
                 Image.fromarray(arr[0], 'RGB').save(os.path.join(res_dir, bg_name[:-4] + '_' + kind + '.png'), 'PNG')
@@ -310,6 +321,11 @@ def bg_colorization(**p):
             with open(os.path.join(res_dir, 'metrics.json'), 'w') as fp:
                 fp.write(M.dumps(summary))
             print(M.all_line(summary))
+            if p.get('color_metrics', 0):
+                csum = M.summarise_color(names, ['all'] * len(names), np.concatenate(color_rows, 0))
+                with open(os.path.join(res_dir, 'color_metrics.json'), 'w') as fp:
+                    fp.write(M.dumps(csum))
+                print(M.color_line(csum))
         return
 
     log_dir = os.path.join(out_dir, 'log')
@@ -414,7 +430,9 @@ def main(argv=None):
                          % args.val_freq)
     from sketchyscenecolorization_amd import preview
     preview.checked_count(args.val_preview, args.val_freq, args.mode)
-    defaults = {name: default for name, _t, default, _c, _h in FLAGS}
+    from sketchyscenecolorization_amd import metrics
+    metrics.checked_color_flag(args.color_metrics, args.metrics, args.val_freq, args.mode)
+    defaults ={name: default for name, _t, default, _c, _h in FLAGS}
     if args.mode == 'scene':
         if args.resume_from == '':
             raise ValueError('--mode scene needs --resume_from <stamp>: the run whose snapshot colours the scene')

@@ -395,6 +395,40 @@ int ssc_image_metrics_f32(const float* a, int lda, int coff_a, const float* b, i
  * -3 for a misaligned pointer (img: 4 bytes; win11, out: 8); nothing is launched and out is not written then. */
 int ssc_image_metrics_bg_f32(const float* img, int ldc, const uint8_t* fg, const uint8_t* target, const uint8_t* mask, int N, int H,
                              int W, const double* win11, double* out, void* ws, int64_t ws_bytes, void* stream);
+/* --- colour scores of the same images (color_metrics.hip) ---
+ * a, b, mask and the rule that counts a pixel as for ssc_image_metrics_u8.  A byte colour goes to CIELAB in double: c = byte/255,
+ * lin = c/12.92 where c <= 0.04045, else ((c+0.055)/1.055)^2.4 -- lin256 double [256] (device), that table, made once by the host
+ * in float64, so the device evaluates no pow --, XYZ = [[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169],
+ * [0.019334, 0.119193, 0.950227]] lin, each component divided by the white point (0.95047, 1, 1.08883), f(t) = cbrt(t) where
+ * t > (6/29)^3, else t / (3 (6/29)^2) + 4/29, L = 116 f(Y) - 16, a* = 500 (f(X) - f(Y)), b* = 200 (f(Y) - f(Z)).
+ * out double [N,13], per image, over the counted pixels:
+ *   0  sum dE = sqrt(dL^2 + da^2 + db^2) (CIE76) between a and b      1  sum dab = sqrt(da^2 + db^2)      2  sum |dL|
+ *   3  the number of counted pixels
+ *   4..7   of image a: sum rg, sum rg^2, sum yb2, sum yb2^2 with rg = R - G, yb2 = R + G - 2 B on the bytes (what colourfulness,
+ *          Hasler & Suesstrunk 2003, is made of; the host forms it)              8..11  the same four sums of image b
+ *   12 sum over the 23 x 23 cells of min(hist_a, hist_b): the histograms of (a*, b*), cells of width 10, the cell of a coordinate
+ *      v = clamp(floor((v + 115) / 10), 0, 22), cell number = cell(a*) * 23 + cell(b*)
+ * 3..12 are integers and exact: no byte colour lies within 4e-8 of a cell boundary, far above any rounding of the double formulas.
+ * hist int64 [N,2,529] or NULL: the counts of image a and of image b.  Every operation of the float formulas is rounded on its
+ * own (no contraction).  One workgroup per run of 1024 pixels writes its twelve sums to ws and adds its cell counts to the
+ * image's with integer atomics; a second launch adds an image's runs in a fixed order: no floating-point atomics, the same bits
+ * from run to run.  ws: N * ceil(H*W/1024) * 12 doubles + N * 2 * 529 int64, 8-byte aligned.
+ * Returns -1 for sizes out of range, -2 for a workspace that is too small or misaligned, -3 for a misaligned lin256 / out / hist;
+ * nothing is launched and out is not written then. */
+int ssc_color_metrics_u8(const uint8_t* a, const uint8_t* b, const uint8_t* mask, int N, int H, int W, const double* lin256,
+                         double* out, int64_t* hist, void* ws, int64_t ws_bytes, void* stream);
+/* The same thirteen numbers for two FLOAT images, the arguments and the quantisation of ssc_image_metrics_f32 (the arithmetic of
+ * ssc_image_postprocess_u8, NHWC with lda / ldb and channel offsets, or a planar b): out and hist are bit-identical to
+ * ssc_color_metrics_u8 of the two postprocessed images.  Returns as ssc_color_metrics_u8; -3 also for a, b off 4 bytes. */
+int ssc_color_metrics_f32(const float* a, int lda, int coff_a, const float* b, int ldb, int coff_b, int b_planar, int N, int H,
+                          int W, const double* lin256, double* out, int64_t* hist, void* ws, int64_t ws_bytes, void* stream);
+/* The same thirteen numbers for the Background generator's FLOAT image against a uint8 target, the arguments and the quantisation
+ * of ssc_image_metrics_bg_f32: out and hist are bit-identical to ssc_color_metrics_u8(ssc_bg_finish_u8(img, fg, mask), target,
+ * mask).  ssc_bg_finish_u8 writes a pixel of fg exactly where the mask leaves the pixel uncounted, so fg is never read; it is
+ * an argument for the sake of the pair, and a mask without it is refused as there.
+ * Returns as ssc_color_metrics_u8; -1 also for ldc < 3 and a mask without fg, -3 also for img off 4 bytes. */
+int ssc_color_metrics_bg_f32(const float* img, int ldc, const uint8_t* fg, const uint8_t* target, const uint8_t* mask, int N, int H,
+                             int W, const double* lin256, double* out, int64_t* hist, void* ws, int64_t ws_bytes, void* stream);
 /* Confusion counts of the region branch (metrics.hip): logits float rows of ld >= K floats, 1 <= K <= 4 (ssc_seg_ce_loss's limit),
  * labels int32 [N,P] -> out int64 [N][K*K+1]: out[n][t*K+p] = the pixels of sample n with label t and prediction p; the last slot
  * = the pixels whose label lies outside [0, K), which are in no other cell.  The prediction is the lowest index among the largest

@@ -21,6 +21,8 @@ It draws nothing from ``random`` or a torch generator and writes no parameter, o
 --val_preview K: the first K scenes also go into a preview sheet -- the foreground, hip.bg_finish_u8 of the pass's own float image
 (the bytes --mode test would write) and the background (preview.BackgroundPreview) -- written as
 log/previews/step_<n>.png and .json; it reads the pass's buffers and writes only its own.
+--color_metrics 1: one more launch per scene, hip.color_metrics_bg_f32 on the arguments of hip.image_metrics_bg_f32, fills [S,13]
+rows of colour sums; they become the line's "color" key.
 """
 import json
 import os
@@ -70,11 +72,15 @@ def scene_names(scenes, keep):
     return [scenes.records[i]['bg_name'][:-4] for i in keep]
 
 
-def validation_line(step, names, rows, conf, seconds):
-    """(the log/validation.jsonl entry of one pass, the metrics.summarise summary it was cut from)."""
+def validation_line(step, names, rows, conf, seconds, color_rows=None):
+    """(the log/validation.jsonl entry of one pass, the metrics.summarise summary it was cut from).  color_rows ([S,13], the
+    pass's colour sums under --color_metrics 1) adds the key 'color': the all and group levels of metrics.summarise_color."""
     summary = metrics.summarise(names, ['all'] * len(names), rows)
     line = {'step': int(step), 'images': len(names), 'all': summary['all'], 'groups': summary['groups'],
             'region': metrics.region_scores(conf), 'seconds': float(seconds)}
+    if color_rows is not None:
+        c = metrics.summarise_color(names, ['all'] * len(names), color_rows)
+        line['color'] = {'all': c['all'], 'groups': c['groups']}
     return line, summary
 
 
@@ -92,8 +98,9 @@ def printed_line(line, summary):
 class HeldOutEvaluator(object):
     """``run(trainer)`` is one pass over ``cache``; the slot rows are uploaded once, here."""
 
-    def __init__(self, cache, names, seg_classes, preview=0):
+    def __init__(self, cache, names, seg_classes, preview=0, color=False):
         assert len(names) == len(cache)
+        self.color_rows = self.color_host = None        # --color_metrics 1: the [S,13] colour sums, on the device and of the last pass
         self.preview = None
         if preview:
             from .preview import BackgroundPreview
@@ -109,6 +116,8 @@ class HeldOutEvaluator(object):
         self.labels = torch.empty((1, H, W), dtype=torch.int32, device=dev)
         self.rows = torch.empty((S, 5), dtype=torch.float64, device=dev)
         self.conf = torch.empty((S, self.K * self.K + 1), dtype=torch.int64, device=dev)
+        if color:
+            self.color_rows = torch.empty((S, 13), dtype=torch.float64, device=dev)
 
     def run(self, tr):
         """-> ([S,5] float64 rows, [S,K*K+1] int64 counts, seconds), on the host.  Everything is launched on the current stream,
@@ -122,10 +131,15 @@ class HeldOutEvaluator(object):
             sf, sb, ss = (int(v) for v in c.slots[i])
             hip.image_metrics_bg_f32(gctx['image'], c.fg[sf:sf + 1], c.bg[sb:sb + 1], c.seg[ss:ss + 1], out=self.rows[i:i + 1])
             hip.seg_confusion(gctx['region_logits'], self.labels, self.K, out=self.conf[i:i + 1])
+            if self.color_rows is not None:
+                hip.color_metrics_bg_f32(gctx['image'], c.fg[sf:sf + 1], c.bg[sb:sb + 1], c.seg[ss:ss + 1],
+                                         out=self.color_rows[i:i + 1])
             if self.preview is not None:
                 self.preview.scene(i, gctx['image'])
         rows = self.rows.cpu().numpy()      # the two copies to the host (the first waits for the pass)
         conf = self.conf.cpu().numpy()
+        if self.color_rows is not None:
+            self.color_host = self.color_rows.cpu().numpy()
         return rows, conf, time.time() - t0
 
 
@@ -135,17 +149,20 @@ def open_held_out(p, scenes_class, tr, beside=0):
     if scenes is None:
         return None
     cache = build_cache(scenes, keep, tr.losses.device, beside)
-    return HeldOutEvaluator(cache, scene_names(scenes, keep), p['seg_classes'], preview=p.get('val_preview', 0))
+    return HeldOutEvaluator(cache, scene_names(scenes, keep), p['seg_classes'], preview=p.get('val_preview', 0),
+                            color=bool(p.get('color_metrics', 0)))
 
 
 def run_pass(ev, tr, log_dir):
     """One pass behind a finished step: a line appended to log/validation.jsonl and one printed."""
     tr.loss_values()        # the step has finished (its losses are on the host) before the pass is queued behind it
     rows, conf, seconds = ev.run(tr)
-    line, summary = validation_line(tr.global_step, ev.names, rows, conf, seconds)
+    line, summary = validation_line(tr.global_step, ev.names, rows, conf, seconds, getattr(ev, 'color_host', None))
     with open(os.path.join(log_dir, 'validation.jsonl'), 'a') as fp:
         fp.write(dumps_line(line))
     if ev.preview is not None:      # the sheet comes to the host behind the rows
         ev.preview.write(log_dir, tr.global_step, ev.names)
     print(printed_line(line, summary))
+    if 'color' in line:     # --color_metrics 1
+        print('held-out pass at step %d: %s' % (line['step'], metrics.color_line(line['color'])))
     return line

@@ -16,7 +16,7 @@ NO_PACKED_FP32 = {'narrow.hip': []}
 # MFMA results in VGPRs instead of AGPRs for the bf16-split kernels: fewer registers in total (no copies between the files), 1-2 %
 VGPR_FORM = ['-mllvm', '-amdgpu-mfma-vgpr-form=1']
 LAST_BUILD = None       # 'rebuilt' | 'reused' after build_library()
-SOURCES = ['igemm.hip', 'igemm_bf16.hip', 'wgrad128.hip', 'wgrad128_bf16.hip', 'wgn16.hip', 'narrow.hip', 'head1.hip', 'fewchan.hip', 'fewchan7.hip', 'pw1x1.hip', 'c3x3.hip', 's2n16.hip', 'tr4tiny.hip', 'tr4n16.hip', 'elementwise.hip', 'text_lstm.hip', 'losses_optim.hip', 'mru_ops.hip', 'bg_io.hip', 'bg_scene.hip', 'fg_scene.hip', 'metrics.hip', 'matching.hip', 'match_eval.hip', 'match_train.hip', 'match_val.hip', 'match_backbone_train.hip', 'match_attn.hip', 'match_segnet.hip', 'scene_system.hip', 'preview.hip']
+SOURCES = ['igemm.hip', 'igemm_bf16.hip', 'wgrad128.hip', 'wgrad128_bf16.hip', 'wgn16.hip', 'narrow.hip', 'head1.hip', 'fewchan.hip', 'fewchan7.hip', 'pw1x1.hip', 'c3x3.hip', 's2n16.hip', 'tr4tiny.hip', 'tr4n16.hip', 'elementwise.hip', 'text_lstm.hip', 'losses_optim.hip', 'mru_ops.hip', 'bg_io.hip', 'bg_scene.hip', 'fg_scene.hip', 'metrics.hip', 'color_metrics.hip', 'matching.hip', 'match_eval.hip', 'match_train.hip', 'match_val.hip', 'match_backbone_train.hip', 'match_attn.hip', 'match_segnet.hip', 'scene_system.hip', 'preview.hip']
 
 
 def _hipcc():

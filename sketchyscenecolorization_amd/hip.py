@@ -192,6 +192,9 @@ SIGNATURES = {
     'ssc_image_metrics_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_image_metrics_f32': [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     'ssc_image_metrics_bg_f32': [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
+    'ssc_color_metrics_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P],
+    'ssc_color_metrics_f32': [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P],
+    'ssc_color_metrics_bg_f32': [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P],
     'ssc_seg_confusion': [_P, _I, _I, _P, _L, _L, _P, _P, _L, _P],
     'ssc_resample_u8': [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'ssc_decode_paired_u8': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
@@ -1821,6 +1824,87 @@ def image_metrics_bg_f32(image, fg_u8, target_u8, mask_u8=None, out=None):
     ws = workspace(max(image_metrics_workspace_bytes(n, h, w), 256 << 20))
     check(lib().ssc_image_metrics_bg_f32(ptr(image), ldc, ptr(fg_u8), ptr(target_u8), ptr(mask_u8), n, h, w, ptr(win), ptr(out),
                                          ptr(ws), ws.numel() * 4, stream_ptr()), 'image_metrics_bg_f32')
+    return out
+
+
+COLOR_CHUNK = 1024           # pixels one workgroup of ssc_color_metrics_u8 / _f32 / _bg_f32 owns (csrc/color_metrics.hip)
+COLOR_CELLS = 23 * 23        # cells of an ab histogram
+_lab_lin = {}
+
+
+def color_metrics_workspace_bytes(n, h, w):
+    """What ssc_color_metrics_u8 / _f32 / _bg_f32 need: twelve doubles per run of 1024 pixels and image, and the two histograms
+    of every image as int64."""
+    return (n * ((h * w + COLOR_CHUNK - 1) // COLOR_CHUNK) * 12 + n * 2 * COLOR_CELLS) * 8
+
+
+def _color_buffers(n, h, w, device, out, hist):
+    """(lin table -- metrics.lab_lin_table, float64, uploaded once per device --, out, workspace) of a colour-score call."""
+    if out is None:
+        out = torch.empty((n, 13), dtype=torch.float64, device=device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (n, 13) and out.is_contiguous() and out.device == device
+    if hist is not None:
+        assert hist.dtype == torch.int64 and tuple(hist.shape) == (n, 2, COLOR_CELLS) and hist.is_contiguous()
+        assert hist.device == device
+    lin = _lab_lin.get(device)
+    if lin is None:
+        from .metrics import lab_lin_table
+        lin = _lab_lin[device] = torch.from_numpy(lab_lin_table()).to(device)
+    return lin, out, workspace(max(color_metrics_workspace_bytes(n, h, w), 256 << 20))
+
+
+def color_metrics_u8(a_u8, b_u8, mask_u8=None, out=None, hist=None):
+    """Two uint8 [N,H,W,3] batches (device), mask_u8 uint8 [N,H,W] or None (a pixel counts where its mask byte is not 0) ->
+    float64 [N,13] on the device, per image: the sums of dE (CIE76), dab and |dL| in CIELAB, counted pixels, the four integer
+    sums of colourfulness of a and of b, and the intersection count of the two 23 x 23 ab histograms (metrics.color_scores turns a
+    row into scores).  ``hist`` int64 [N,2,529]: filled with the histograms.  The same bits from run to run."""
+    n, h, w, c = a_u8.shape
+    assert c == 3 and a_u8.dtype == torch.uint8 and b_u8.dtype == torch.uint8 and a_u8.is_cuda and b_u8.device == a_u8.device
+    assert tuple(b_u8.shape) == tuple(a_u8.shape) and a_u8.is_contiguous() and b_u8.is_contiguous()
+    if mask_u8 is not None:
+        assert mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (n, h, w) and mask_u8.is_contiguous()
+        assert mask_u8.device == a_u8.device
+    lin, out, ws = _color_buffers(n, h, w, a_u8.device, out, hist)
+    check(lib().ssc_color_metrics_u8(ptr(a_u8), ptr(b_u8), ptr(mask_u8), n, h, w, ptr(lin), ptr(out), ptr(hist), ptr(ws),
+                                     ws.numel() * 4, stream_ptr()), 'color_metrics_u8')
+    return out
+
+
+def color_metrics_f32(a, coff_a, b, coff_b=None, out=None, hist=None):
+    """``color_metrics_u8(image_postprocess_u8(a), image_postprocess_u8(b))`` bit for bit, without the uint8 images; the
+    arguments of ``image_metrics_f32`` -> float64 [N,13] on the device, the rows of ``color_metrics_u8``; no mask."""
+    n, h, w, lda = a.shape
+    planar = b.dim() == 4 and coff_b is None
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_cuda and b.device == a.device
+    assert a.is_contiguous() and b.is_contiguous() and 0 <= coff_a and coff_a + 3 <= lda
+    if planar:
+        assert tuple(b.shape) == (n, 3, h, w)
+        ldb, coff_b = 0, 0
+    else:
+        assert b.dim() == 4 and tuple(b.shape[:3]) == (n, h, w) and 0 <= coff_b and coff_b + 3 <= b.shape[3]
+        ldb = b.shape[3]
+    lin, out, ws = _color_buffers(n, h, w, a.device, out, hist)
+    check(lib().ssc_color_metrics_f32(ptr(a), lda, coff_a, ptr(b), ldb, coff_b, int(planar), n, h, w, ptr(lin), ptr(out),
+                                      ptr(hist), ptr(ws), ws.numel() * 4, stream_ptr()), 'color_metrics_f32')
+    return out
+
+
+def color_metrics_bg_f32(image, fg_u8, target_u8, mask_u8=None, out=None, hist=None):
+    """``color_metrics_u8(bg_finish_u8(image, fg_u8, mask_u8), target_u8, mask_u8)`` bit for bit, without the uint8 image; the
+    arguments of ``image_metrics_bg_f32`` -> float64 [N,13] on the device, the rows of ``color_metrics_u8``."""
+    n, h, w, ldc = image.shape
+    assert image.dtype == torch.float32 and image.is_cuda and image.is_contiguous() and ldc >= 3
+    assert target_u8.dtype == torch.uint8 and tuple(target_u8.shape) == (n, h, w, 3) and target_u8.is_contiguous()
+    assert target_u8.device == image.device
+    if mask_u8 is not None:
+        assert fg_u8 is not None and mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (n, h, w)
+        assert mask_u8.is_contiguous() and mask_u8.device == image.device
+    if fg_u8 is not None:
+        assert fg_u8.dtype == torch.uint8 and tuple(fg_u8.shape) == (n, h, w, 3) and fg_u8.is_contiguous()
+        assert fg_u8.device == image.device
+    lin, out, ws = _color_buffers(n, h, w, image.device, out, hist)
+    check(lib().ssc_color_metrics_bg_f32(ptr(image), ldc, ptr(fg_u8), ptr(target_u8), ptr(mask_u8), n, h, w, ptr(lin), ptr(out),
+                                         ptr(hist), ptr(ws), ws.numel() * 4, stream_ptr()), 'color_metrics_bg_f32')
     return out
 
 

@@ -248,7 +248,8 @@ def train(**kwargs):
             from ..train_validation import HeldOutEvaluator
             val_cache = get_record_cache(val_dir, img, distance_map, device='cuda:%d' % torch.cuda.current_device(),
                                          max_records=(int(getattr(Config, 'val_records', 0) or 0) or None))
-            evaluator = HeldOutEvaluator(val_cache, batch_size, preview=int(getattr(Config, 'val_preview', 0) or 0))
+            evaluator = HeldOutEvaluator(val_cache, batch_size, preview=int(getattr(Config, 'val_preview', 0) or 0),
+                                         color=bool(getattr(Config, 'color_metrics', 0)))
             print('held-out cache: %d records, %d bytes (%.1f MB%s) on %s, built in %.1f s; a pass of %d batches every %d iterations'
                   % (len(val_cache), val_cache.nbytes, val_cache.nbytes / 1e6, ', distance maps included' if distance_map else '',
                      val_cache.device, val_cache.build_seconds, len(evaluator.plan), val_freq))
@@ -340,12 +341,15 @@ def train(**kwargs):
                 from .. import metrics as M
                 from ..train_validation import validation_line
                 rows, seconds = evaluator.run(tower.tr)
-                line, summary = validation_line(i, evaluator.names, evaluator.groups, rows, seconds)
+                line, summary = validation_line(i, evaluator.names, evaluator.groups, rows, seconds,
+                                                color_rows=getattr(evaluator, 'color_host', None))
                 val_f.write(json.dumps(line, sort_keys=True) + '\n')
                 val_f.flush()
                 if evaluator.preview is not None:       # --val_preview K: the sheet comes to the host behind the rows
                     evaluator.preview.write(log_dir, i, evaluator.names, evaluator.groups)
                 print('held-out pass at iteration %d (%.2f s): %s' % (i, seconds, M.all_line(summary)))
+                if 'color' in line:     # --color_metrics 1
+                    print('held-out pass at iteration %d: %s' % (i, M.color_line(line['color'])))
             if num_gpu > 1:     # the other ranks wait for rank 0's pass, as they do for its snapshot
                 import torch.distributed as dist
                 dist.barrier()
@@ -537,7 +541,8 @@ def validation(**kwargs):
     out_dir = os.path.join(Config.results_dir, 'with_text' if Config.LSTM_hybrid != 0 else 'without_text')
     os.makedirs(out_dir, exist_ok=True)
     metrics = getattr(Config, 'metrics', 0) != 0
-    scored = {'names': [], 'groups': [], 'rows': []}
+    color = metrics and getattr(Config, 'color_metrics', 0) != 0     # --color_metrics 1: color_metrics.json beside metrics.json
+    scored = {'names': [], 'groups': [], 'rows': [], 'color': []}
 
     def run(images_, sketches_, class_id_, text_, stems, cats):
         gen, images, sketches = build_single_graph(images_, sketches_, None, class_id_, None, text_,
@@ -554,7 +559,10 @@ def validation(**kwargs):
             from .. import hip
             k = len(stems)
             dev = lambda u8: torch.from_numpy(np.ascontiguousarray(u8[:k])).cuda()      # noqa: E731
-            scored['rows'].append(hip.image_metrics_u8(dev(out_u8), dev(target_u8)).cpu().numpy())
+            a_d, b_d = dev(out_u8), dev(target_u8)
+            scored['rows'].append(hip.image_metrics_u8(a_d, b_d).cpu().numpy())
+            if color:
+                scored['color'].append(hip.color_metrics_u8(a_d, b_d).cpu().numpy())
             scored['names'] += list(stems)
             scored['groups'] += list(cats)
 
@@ -566,6 +574,11 @@ def validation(**kwargs):
         with open(os.path.join(out_dir, 'metrics.json'), 'w') as fp:
             fp.write(M.dumps(summary))
         print(M.all_line(summary))
+        if color:
+            csum = M.summarise_color(scored['names'], scored['groups'], np.concatenate(scored['color'], 0))
+            with open(os.path.join(out_dir, 'color_metrics.json'), 'w') as fp:
+                fp.write(M.dumps(csum))
+            print(M.color_line(csum))
 
     if os.path.isdir(os.path.join('data', 'tfrecord', 'val')):      # the reference's validation set (:262-272)
         from .input_pipeline import build_input_queue_paired_test

@@ -18,6 +18,8 @@ The pass, which is the definition of the numbers it writes:
 own ``tower.infer_nhwc`` rows, the conversion that makes --mode val's PNGs -- into a preview sheet beside the records' sketches
 and targets (preview.ForegroundPreview).  No second forward pass, no draw from a generator, and nothing
 written but the preview's own buffers.
+--color_metrics 1: one more launch per batch, hip.color_metrics_f32 on the same two buffers, fills [S,13] rows of colour sums
+(DESIGN.md section 8.17); they come to the host behind the five-sum rows and become the line's "color" key.
 """
 import time
 
@@ -48,19 +50,25 @@ def pass_noise(gen, n, device):
     return torch.randn((n, NOISE_DIM), device=device, generator=gen)
 
 
-def validation_line(step, names, groups, rows, seconds):
-    """(the log/validation.jsonl entry of one pass, the metrics.summarise summary it was cut from)."""
+def validation_line(step, names, groups, rows, seconds, color_rows=None):
+    """(the log/validation.jsonl entry of one pass, the metrics.summarise summary it was cut from).  color_rows ([S,13], the
+    pass's colour sums under --color_metrics 1) adds the key 'color': the all and per-category levels of
+    metrics.summarise_color."""
     summary = metrics.summarise(names, groups, rows)
     line = {'step': int(step), 'images': len(names), 'all': summary['all'], 'groups': summary['groups'],
             'seconds': float(seconds)}
+    if color_rows is not None:
+        c = metrics.summarise_color(names, groups, color_rows)
+        line['color'] = {'all': c['all'], 'groups': c['groups']}
     return line, summary
 
 
 class HeldOutEvaluator(object):
     """``run(tower)`` is one pass; the record numbers and class ids are uploaded once, here."""
 
-    def __init__(self, cache, batch_size, preview=0):
+    def __init__(self, cache, batch_size, preview=0, color=False):
         self.cache, self.batch_size = cache, int(batch_size)
+        self.color_rows = self.color_host = None        # --color_metrics 1: the [S,13] colour sums, on the device and of the last pass
         self.preview = None
         if preview:
             from .preview import ForegroundPreview
@@ -72,6 +80,8 @@ class HeldOutEvaluator(object):
         self.class_id = torch.from_numpy(np.ascontiguousarray(cache.class_id, dtype=np.int32)).to(dev)
         self.rows = torch.empty((len(cache), 5), dtype=torch.float64, device=dev)
         self.gen = torch.Generator(device=dev)
+        if color:
+            self.color_rows = torch.empty((len(cache), 13), dtype=torch.float64, device=dev)
 
     def run(self, tower):
         """-> ([S,5] float64 rows on the host, seconds).  Everything is launched on the current stream, behind whatever
@@ -88,8 +98,12 @@ class HeldOutEvaluator(object):
             tower.generate(sketch, cache.text[a:b], noise_vec, labels=self.class_id[a:b], clone=False)
             out, coff = tower.infer_nhwc
             hip.image_metrics_f32(out, coff, target, out=self.rows[a:b])
+            if self.color_rows is not None:
+                hip.color_metrics_f32(out, coff, target, out=self.color_rows[a:b])
             if pv is not None:
                 pv.batch(out, coff, a, b)
         rows = self.rows.cpu().numpy()      # the one copy to the host (it waits for the pass)
+        if self.color_rows is not None:
+            self.color_host = self.color_rows.cpu().numpy()
         hip.check_sk('held-out pass')
         return rows, time.time() - t0
